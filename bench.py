@@ -16,11 +16,15 @@ steps (barrier + synchronize on both sides, max over ranks).  The updated-voxel 
 identical *untimed* replay of the same K steps from a device snapshot (the diff kernel would otherwise sit
 inside the timed region).
 
+A plain run sets up, warms up, times the K steps, replays them for the count and prints the line.  --full adds what the
+headline does not need (scatter_full_update, verify, parity, cpu_baseline); --dump-outputs DIR writes the last timed step's
+field (a seeded sample, dump_outputs()).
+
 Extra objects on the JSON line:
   roofline      algorithmic bytes (16 B per updated voxel) over the SUM of the durations of every kernel
                 of UpdateESDF (bulk path: k_ft_rows + k_ft_plane + k_ft_x; frontier rounds: the k_relax_q launches),
                 measured live with HIP events on the map's own stream; `dominant_kernel` quotes k_ft_x alone.
-  cpu_baseline  the CPU oracle (verbatim-compiled reference when oracle/_ref is present, else the pinned
+  cpu_baseline  (--full) the CPU oracle (verbatim-compiled reference when oracle/_ref is present, else the pinned
                 restatement) timed on one host core on a bounded sample of the same workload (same obstacle
                 density on a 224^3 grid, --cpu-grid); rank 0, N=1 only.  The one-off measurement of the reference
                 at the full 512^3 size (profiles/r02_cpu_512.json, ~2 min per UpdateESDF) is quoted beside it.
@@ -85,6 +89,13 @@ def parse():
     ap.add_argument("--force-sharded", action="store_true", help="run the sharded driver even with one rank (smoke test)")
     ap.add_argument("--replicas", action="store_true",
                     help="with --gpus N: N independent maps instead of one spatially sharded map")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: the scatter insert's own figures, the k-d tree self-check (verify), "
+                         "the parity quote of the committed fixtures and the CPU baseline (off: set up, warm up, time the steps, "
+                         "print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64): "
+                         "distances and occupancy of a fixed seeded sample of voxels, and the distances of the middle z-plane")
     return ap.parse_args()
 
 
@@ -101,7 +112,7 @@ class Workload:
         srng = np.random.RandomState(4242)  # the surfaces themselves are the same for every rank / step
         self.planes = [(int(a), int(srng.randint(g // 8, g - g // 8))) for a in range(3)]
         self.spheres = [(srng.randint(g // 8, g - g // 8, 3), float(srng.uniform(8, 40))) for _ in range(20)]
-        self.live = self._fresh(n_obs, set())
+        self.live = self._fresh(n_obs, np.empty((0, 3), np.int64))
         self.step_id = 0
 
     def _sample(self, k):
@@ -123,15 +134,30 @@ class Workload:
         return out
 
     def _fresh(self, k, taken):
-        out = []
-        seen = set(taken)
-        while len(out) < k:
-            c = self._sample(k - len(out))
-            for v in map(tuple, c):
-                if v not in seen:
-                    seen.add(v)
-                    out.append(v)
-        return np.array(out, dtype=np.int32)
+        """k voxels not in `taken` and distinct from each other: the draws in order, a voxel kept at its first occurrence
+        unless taken, more drawn until k are kept (array operations: the stage of a long run is not a Python loop per voxel)."""
+        g = self.grid
+        lin = lambda c: (c[:, 0].astype(np.int64) * g + c[:, 1]) * g + c[:, 2]   # noqa: E731
+        seen = np.sort(lin(np.asarray(taken).reshape(-1, 3)))
+        shift = max(1, int(k).bit_length())
+        assert (g ** 3 - 1).bit_length() + shift < 63
+        out, n = [], 0
+        while n < k:
+            c = self._sample(k - n)
+            key = np.sort((lin(c) << shift) | np.arange(len(c)))    # by voxel, then by draw order
+            code, idx = key >> shift, key & ((1 << shift) - 1)
+            first = np.ones(len(c), bool)
+            first[1:] = code[1:] != code[:-1]                        # first occurrence within the draw
+            if len(seen):
+                pos = np.minimum(np.searchsorted(seen, code), len(seen) - 1)
+                first &= seen[pos] != code                           # not taken
+            keep = np.zeros(len(c), bool)
+            keep[idx[first]] = True
+            out.append(c[keep])
+            n += int(keep.sum())
+            if n < k:
+                seen = np.sort(np.concatenate([seen, code[first]]))
+        return np.concatenate(out).astype(np.int32) if out else np.empty((0, 3), np.int32)
 
     def initial(self):
         return self.live.copy()
@@ -140,7 +166,7 @@ class Workload:
         """(new voxels to occupy, old voxels to free); the oldest half leaves."""
         old = self.live[: self.half]
         keep = self.live[self.half:]
-        new = self._fresh(self.half, set(map(tuple, self.live)))
+        new = self._fresh(self.half, self.live)
         self.live = np.concatenate([keep, new])
         self.step_id += 1
         return new, old.copy()
@@ -727,6 +753,8 @@ def main():
         args.grid = 512 if int(os.environ.get("WORLD_SIZE", "1")) == 1 else 1024
     if args.obstacles is None:
         args.obstacles = int(round(50000 * (args.grid / 512.0) ** 3))
+    if args.dump_outputs and (args.delta_sweep or args.workload != "c2"):
+        raise SystemExit("bench.py --dump-outputs: the headline workload (c2) only")
     if args.delta_sweep:
         args.steps = min(args.steps, 5)
         return run_delta_sweep(args)
@@ -819,12 +847,13 @@ def main():
     for _ in range(3):
         observe(init)
         top.UpdateOccupancy(True)
-    m.snapshot_save(0)
+    if args.full:
+        m.snapshot_save(0)
     t_sc = time.perf_counter()
     st_scatter = top.UpdateESDF()
     st_scatter.setdefault("host_ms", (time.perf_counter() - t_sc) * 1e3)
     st_scatter.setdefault("device_ms", st_scatter["host_ms"])
-    scatter_updated = m.snapshot_count_updated(0)
+    scatter_updated = m.snapshot_count_updated(0) if args.full else None
 
     # ---- pre-stage every step's input in HBM
     nsteps = args.warmup + args.steps
@@ -877,6 +906,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:   # the field the last timed step left, before the replay below touches the map
+        dump_outputs(args.dump_outputs, m, box_lo, G, rank if world > 1 else None)
+
     # ---- untimed accounting replay of the same K steps
     m.snapshot_restore(1)
     replay = [step(args.warmup + k, account=True) for k in range(args.steps)]
@@ -890,7 +922,7 @@ def main():
     # ---- self-check of the run (every rank): sampled owned voxels against a k-d tree over the GLOBAL obstacle list --
     # what makes an N > 1 line evidence, not just a number (the field now is the one the K timed steps produced)
     verify = None
-    if args.verify_samples > 0 and args.unobserved <= 0:   # (a partially observed map is not the exact transform: SURVEY.md 7.3-B)
+    if args.full and args.verify_samples > 0 and args.unobserved <= 0:   # (a partially observed map is not the exact transform: SURVEY.md 7.3-B)
         # the occupied set as the map holds it (the workload's own list is not it: a voxel that left and was drawn again
         # carries more log-odds than a fresh one and survives the single miss that frees the others)
         mine = np.ascontiguousarray(m.GetOccupiedVoxels(), dtype=np.int32)
@@ -929,7 +961,7 @@ def main():
                             "integers); a third of the samples within 3 voxels of the owned box's faces",
                   "seconds": time.perf_counter() - t_v}
 
-    if args.verify_samples > 0 and args.unobserved > 0:
+    if args.full and args.verify_samples > 0 and args.unobserved > 0:
         # A partially observed map is not the exact transform: what CAN be checked on every sampled voxel is the
         # lower bound -- no propagated distance is smaller than the distance to the nearest obstacle -- and how many of them
         # reach it; the full-size comparison with the reference is the committed envelope (parity, below).
@@ -1050,11 +1082,6 @@ def main():
             "updated_voxels_per_step": my_updated / args.steps,
             "update_esdf_voxels_per_sec": my_updated / (sum(s["host_ms"] for s in timed) * 1e-3),
             "rounds_per_update": statistics.mean(s["rounds"] for s in timed),
-            "scatter_full_update": {"updated_voxels": scatter_updated, "device_ms": st_scatter["device_ms"],
-                                    "host_ms": st_scatter["host_ms"], "rounds": st_scatter["rounds"],
-                                    "relax_ms": st_scatter["relax_ms"],
-                                    "voxels_per_sec": scatter_updated / (st_scatter["host_ms"] * 1e-3),
-                                    "roofline_frac": scatter_updated * 16 / (st_scatter["relax_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS},
             # frac: algorithmic bytes of one UpdateESDF / the CALL's p50 (host wall time of fiesta_hip_update_esdf: every
             # kernel, every gap between them, the final synchronisation) -- VERDICT r3: not the sum of the kernels' own events,
             # which flatters it; that number stays as frac_kernels_only
@@ -1071,10 +1098,16 @@ def main():
                 "phases_p50_ms": phases, "dominant_kernel": dominant, "ring_overflows": overflow, "engine_steps": engine_steps,
             },
             "revision": revision(),
-            "verify": verify,
-            "parity": parity_summary(args, G, world) if args.unobserved <= 0 else parity_partial(args, G, world, timed),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["scatter_full_update"] = {"updated_voxels": scatter_updated, "device_ms": st_scatter["device_ms"],
+                                          "host_ms": st_scatter["host_ms"], "rounds": st_scatter["rounds"],
+                                          "relax_ms": st_scatter["relax_ms"],
+                                          "voxels_per_sec": scatter_updated / (st_scatter["host_ms"] * 1e-3),
+                                          "roofline_frac": scatter_updated * 16 / (st_scatter["relax_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            out["verify"] = verify
+            out["parity"] = parity_summary(args, G, world) if args.unobserved <= 0 else parity_partial(args, G, world, timed)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if sharded_map is None:
                 m.close()   # (the GPU side is finished; the CPU legs get the host to themselves)
             out["cpu_baseline"] = run_cpu_baseline(args)
@@ -1101,6 +1134,23 @@ def main():
     if dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, m, box_lo, G, rank=None):
+    """--dump-outputs: what a caller reads from the map after the last timed step, for comparing two builds output for output.
+    The whole field is 4 B x G^3 (512 MB at 512^3), so a fixed seeded sample of 2^20 voxels of the owned box (their coordinates,
+    GetDistance in metres, GetOccupancy) and GetSlice of the middle z-plane (single map, up to 16 MB); about 26 MB at 512^3.
+    With --gpus N every rank writes its own box, the names suffixed _rank<r>."""
+    os.makedirs(path, exist_ok=True)
+    lo = np.asarray(box_lo, np.int64)
+    v = (lo + np.random.RandomState(4711).randint(0, G, (1 << 20, 3))).astype(np.int32)
+    arrays = {"sample_voxels": v.astype(np.float32),
+              "sample_distance": np.asarray(m.GetDistance(v), np.float64),
+              "sample_occupancy": np.asarray(m.GetOccupancy(v)).astype(np.float32)}
+    if rank is None and G * G * 8 <= 16 << 20:
+        arrays["mid_plane_distance"] = np.asarray(m.GetSlice(G // 2), np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ("" if rank is None else f"_rank{rank}") + ".npy"), a)
 
 
 def parity_partial(args, G, world, timed):

@@ -60,3 +60,27 @@ def test_c4_stream_frames_are_deterministic_and_inside_their_window():
     a, b = c4_frame(10)[2], c4_frame(11)[2]
     sa, sb = set(map(tuple, a.tolist())), set(map(tuple, b.tolist()))
     assert 0.7 < len(sa & sb) / len(sa) < 1.0                           # overlapping windows, moving content
+
+
+def test_workload_draws_follow_the_voxel_by_voxel_rule():
+    """Workload._fresh works on whole draws; it must keep exactly what the rule says voxel by voxel (a voxel of the draw is
+    kept at its first occurrence unless taken, more are drawn until k are kept) -- grids small enough for many collisions."""
+    b = _bench()
+
+    class VoxelByVoxel(b.Workload):
+        def _fresh(self, k, taken):
+            out, seen = [], set(map(tuple, np.asarray(taken).reshape(-1, 3).tolist()))
+            while len(out) < k:
+                for v in map(tuple, self._sample(k - len(out)).tolist()):
+                    if v not in seen:
+                        seen.add(v)
+                        out.append(v)
+            return np.array(out, dtype=np.int32).reshape(-1, 3)
+
+    for grid, n, scene, delta in ((12, 900, "scatter", None), (40, 1500, "surfaces", None), (64, 3000, "scatter", 800)):
+        fast, slow = b.Workload(grid, n, scene=scene, delta=delta), VoxelByVoxel(grid, n, scene=scene, delta=delta)
+        assert np.array_equal(fast.initial(), slow.initial())
+        for _ in range(6):
+            (fn, fo), (sn, so) = fast.next_step(), slow.next_step()
+            assert fn.dtype == sn.dtype == np.int32
+            assert np.array_equal(fn, sn) and np.array_equal(fo, so)

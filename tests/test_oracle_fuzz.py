@@ -2,7 +2,8 @@
 
 Same generator idea as tests/test_gpu_fuzz.py, but here BOTH sides follow the reference's FIFO order, so everything must
 be identical including closest-obstacle ids, the expansion counters the reference prints and (hash flavour) the internal
-slot order.  Skipped where oracle/_ref is not built; tests/golden/ carries the pin there.
+slot order.  Where oracle/_ref is not built, the reference's side is replayed from tests/golden/ref_call_digests.json
+(test_oracle_port_vs_ref.pair_factory).
 """
 import numpy as np
 import pytest

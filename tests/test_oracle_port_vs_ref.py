@@ -1,33 +1,126 @@
 """Pins the CPU restatement (oracle/esdf_port.cpp) against the reference's own sources compiled verbatim
-(oracle/_ref, built by oracle/Makefile from /root/reference).  Runs only where oracle/_ref exists (this
-container, or a GPU box that received the prebuilt binaries); the committed fixtures under tests/golden/
-carry the same pin to machines that have neither (tests/test_oracle_golden.py).
+(oracle/_ref, built by oracle/Makefile from the reference's sources where they are present).
+
+Where oracle/_ref is not built, the reference's side of every test is REPLAYED: a second instance of the restatement
+stands in for it, and every value it hands the test (each method result and attribute read, in call order) must have the
+digest the verbatim reference produced for the same call, committed in tests/golden/ref_call_digests.json
+(tests/golden/make_golden_ref_calls.py).  So the pin runs on every machine; the committed fixtures of
+tests/test_oracle_golden.py pin the full arrays of other programs.
 
 The restatement follows the reference's FIFO order literally, so -- unlike the GPU engine -- it must match
 the reference bit for bit INCLUDING closest-obstacle ids, log-odds, counters and the expansion counters the
 reference prints (src/ESDFMap.cpp:277,394).
 """
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
 from scenarios import P_DEFAULT, all_voxels, depth_to_points, render_depth, yaw_pose, INTRINSICS
 
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_call_digests.json")
+RECORD_ENV = "FIESTA_RECORD_REF_CALLS"   # (set by make_golden_ref_calls.py: record the live reference's calls)
+REPLAY_ENV = "FIESTA_REPLAY_REF_CALLS"   # (=1: replay even where oracle/_ref is built, to check the fixture itself)
 
-@pytest.fixture(scope="module")
-def pair_factory(oracle_libs):
-    if not oracle_libs.available("ref", "array"):
-        pytest.skip("oracle/_ref is not built on this machine (needs /root/reference)")
+
+def _canon(h, v):
+    """Feeds a canonical byte form of a returned value to the hash (the wall-clock 'seconds' of the stats excluded)."""
+    if isinstance(v, dict):
+        h.update(b"{")
+        for k in sorted(v):
+            if k != "seconds":
+                h.update(k.encode() + b":")
+                _canon(h, v[k])
+    elif isinstance(v, (list, tuple)):
+        h.update(b"(%d" % len(v))
+        for x in v:
+            _canon(h, x)
+    elif isinstance(v, np.ndarray):
+        h.update(f"a{v.dtype.str}{v.shape}".encode())
+        h.update(np.ascontiguousarray(v).tobytes())
+    else:
+        h.update(repr(v.item() if isinstance(v, np.generic) else v).encode())
+
+
+class _CallLog:
+    """The reference's side of one test as (name, digest) per call: recorded from the live reference, or checked in replay."""
+
+    def __init__(self, entries=None):
+        self.replay, self.entries, self.i, self.broken = entries is not None, list(entries or []), 0, False
+
+    def note(self, name, value):
+        h = hashlib.sha256()
+        _canon(h, value)
+        got = [name, h.hexdigest()[:20]]
+        if not self.replay:
+            self.entries.append(got)
+            return value
+        assert self.i < len(self.entries), f"call {self.i} ({name}): the recorded reference made fewer calls"
+        want = self.entries[self.i]
+        self.broken = got != want
+        assert got == want, f"call {self.i} ({name}): the restatement differs from the recorded reference ({want[0]})"
+        self.i += 1
+        return value
+
+
+class _Observed:
+    """A map whose every attribute read and method result passes through a _CallLog."""
+
+    def __init__(self, m, log):
+        self._m, self._log = m, log
+
+    def __getattr__(self, name):
+        v = getattr(self._m, name)
+        if not callable(v):
+            return self._log.note(name, v)
+
+        def call(*a, **k):
+            try:
+                r = v(*a, **k)
+            except Exception as e:
+                self._log.note(name, ("raise", type(e).__name__))
+                raise
+            return self._log.note(name, r)
+        return call
+
+
+@pytest.fixture
+def pair_factory(oracle_libs, request):
+    key = f"{request.node.module.__name__}::{request.node.name}"
+    live = oracle_libs.available("ref", "array") and not os.environ.get(REPLAY_ENV)
+    if live:
+        log = _CallLog()
+    else:
+        recorded = json.load(open(DIGESTS)) if os.path.exists(DIGESTS) else {}
+        if key not in recorded:
+            pytest.skip(f"oracle/_ref is not built on this machine and {os.path.basename(DIGESTS)} has no record of {key}")
+        log = _CallLog(recorded[key])
 
     def make(origin, res, size=None, mode="array", reserve=0):
-        if mode == "hash" and not oracle_libs.available("ref", "hash"):
+        if live and mode == "hash" and not oracle_libs.available("ref", "hash"):
             pytest.skip("hash flavour of the reference is not built")
-        ms = [oracle_libs.OracleMap(origin, res, size, reserve_size=reserve, mode=mode, kind=k)
-              for k in ("ref", "port")]
+        ref = oracle_libs.OracleMap(origin, res, size, reserve_size=reserve, mode=mode, kind="ref" if live else "port")
+        ms = [_Observed(ref, log), oracle_libs.OracleMap(origin, res, size, reserve_size=reserve, mode=mode, kind="port")]
         for m in ms:
             m.SetParameters(*P_DEFAULT)
             m.SetOriginalRange()
         return ms
-    return make
+
+    def ref_raycast(start, end, lo, hi):
+        """the reference's free Raycast (src/raycast.cpp), through the same log"""
+        return _Observed(oracle_libs, log).raycast(start, end, lo, hi, kind="ref" if live else "port")
+    make.ref_raycast = ref_raycast
+    yield make
+    if log.replay and not log.broken:
+        assert log.i == len(log.entries), f"the recorded reference made {len(log.entries)} calls, the replay {log.i}"
+    path = os.environ.get(RECORD_ENV)
+    if live and path:
+        rec = json.load(open(path)) if os.path.exists(path) else {}
+        rec[key] = log.entries
+        with open(path, "w") as f:   # (one line per test)
+            f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v, separators=(',', ':'))}" for k, v in sorted(rec.items())) + "\n}\n")
 
 
 def both(ms, fn):
@@ -175,11 +268,11 @@ def test_raycast_free_function(oracle_libs, pair_factory):
             b[rng.randint(3)] = a[rng.randint(3)]
         if k % 11 == 0:
             a = np.round(a)
-        assert np.array_equal(oracle_libs.raycast(a, b, lo, hi, kind="ref"), oracle_libs.raycast(a, b, lo, hi, kind="port"))
+        assert np.array_equal(pair_factory.ref_raycast(a, b, lo, hi), oracle_libs.raycast(a, b, lo, hi, kind="port"))
     a, b = np.array([0.5, 0.5, 0.5]), np.array([1900.5, 3.5, 0.5])
-    for kind in ("ref", "port"):
+    for fn in (pair_factory.ref_raycast, lambda *x: oracle_libs.raycast(*x, kind="port")):
         with pytest.raises(IndexError):  # std::out_of_range past 1500 voxels (src/raycast.cpp:127-130)
-            oracle_libs.raycast(a, b, [-1e4] * 3, [1e4] * 3, kind=kind)
+            fn(a, b, [-1e4] * 3, [1e4] * 3)
 
 
 def test_raycast_frames_depth(pair_factory):

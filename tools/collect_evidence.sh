@@ -15,10 +15,10 @@ python -m pytest tests -q -m gpu --junitxml="$R/pytest_gpu.xml" > "$R/pytest_gpu
 grep -aE "^(FAILED|ERROR)|[0-9]+ (passed|failed)" "$R/pytest_gpu.log" > "$R/pytest_gpu.txt"
 unset FIESTA_ENVELOPE_LOG
 # C2 headline as the driver runs it (the JSON line carries roofline + cpu_baseline incl. the full-size CPU leg, ~4 min) ...
-python bench.py > "$R/bench_default.log" 2>&1
+python bench.py --full > "$R/bench_default.log" 2>&1
 grep '^{"metric' "$R/bench_default.log" > "$R/bench_default.json"
 # ... and the same GPU work under the kernel trace (without the 4-minute CPU leg)
-rocprofv3 --kernel-trace --stats --output-format csv -d "$R/stats" -o bench -- python bench.py --no-cpu-full > "$R/bench_default_profiled.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$R/stats" -o bench -- python bench.py --full --no-cpu-full > "$R/bench_default_profiled.log" 2>&1
 grep '^{"metric' "$R/bench_default_profiled.log" > "$R/bench_default_profiled.json"
 # HBM traffic of UpdateESDF's kernels: two PMC passes, calibrated inside the same runs (tools/pmc_traffic.py)
 for C in FETCH_SIZE WRITE_SIZE; do
@@ -38,16 +38,16 @@ rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SA
 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE \
   --output-format csv -d "$R/pmc_LDS" -o bench -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$R/pmc_LDS.log" 2>&1
 # the other scene, the other engine, the other configurations
-python bench.py --engine envelope --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c2_envelope.json"
+python bench.py --full --engine envelope --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c2_envelope.json"
 python bench.py --workload queries 2>&1 | grep '^{"metric' > "$R/bench_queries.json"
-python bench.py --scene surfaces --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c2_surfaces.json"
-python bench.py --engine rounds --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c2_rounds.json"
-python bench.py --engine rounds --scene surfaces --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c2_surfaces_rounds.json"
-python bench.py --engine levels --no-cpu-baseline --steps 3 --warmup 1 2>&1 | grep '^{"metric' > "$R/bench_c2_levels.json"
+python bench.py --full --scene surfaces --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c2_surfaces.json"
+python bench.py --full --engine rounds --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c2_rounds.json"
+python bench.py --full --engine rounds --scene surfaces --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c2_surfaces_rounds.json"
+python bench.py --full --engine levels --no-cpu-baseline --steps 3 --warmup 1 2>&1 | grep '^{"metric' > "$R/bench_c2_levels.json"
 # C2-partial: 27 % of the map (32^3 blocks) never observed -> r06: the masked transform (mask_kernels.hpp); the frontier rounds pinned beside it
-python bench.py --unobserved 0.27 --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c2_partial.json"
-python bench.py --unobserved 0.27 --engine rounds --no-cpu-baseline --steps 5 2>&1 | grep '^{"metric' > "$R/bench_c2_partial_rounds.json"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$R/stats_partial" -o partial -- python bench.py --unobserved 0.27 --no-cpu-baseline --steps 10 > "$R/c2_partial_profiled.log" 2>&1
+python bench.py --full --unobserved 0.27 --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c2_partial.json"
+python bench.py --full --unobserved 0.27 --engine rounds --no-cpu-baseline --steps 5 2>&1 | grep '^{"metric' > "$R/bench_c2_partial_rounds.json"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$R/stats_partial" -o partial -- python bench.py --full --unobserved 0.27 --no-cpu-baseline --steps 10 > "$R/c2_partial_profiled.log" 2>&1
 python tools/density_range.py > "$R/density_range.json" 2> "$R/density_range.err"
 python bench.py --workload c3 --steps 20 --warmup 4 2>&1 | grep '^{"metric' > "$R/bench_c3.json"
 python bench.py --workload c3 --steps 20 --warmup 4 --engine rounds --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_c3_rounds.json"
@@ -57,10 +57,10 @@ python tools/dev/floor_latency.py > "$R/floor_latency.txt" 2>&1
 # kernel stats of the sensor-rate configurations (level engine: k_level_run; hand-over: k_relax_q)
 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/stats_c3" -o c3 -- python bench.py --workload c3 --steps 20 --warmup 4 --no-cpu-baseline > "$R/c3_profiled.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/stats_c4" -o c4 -- python bench.py --workload c4 --steps 40 --warmup 5 --no-cpu-baseline > "$R/c4_profiled.log" 2>&1
-python bench.py --gpus 1 --force-sharded --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_sharded_1rank.json"
+python bench.py --full --gpus 1 --force-sharded --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_sharded_1rank.json"
 python bench.py --delta-sweep --no-cpu-baseline 2>&1 | grep -E "^\{" > "$R/delta_sweep.json"
 # config-5-sized pieces on one GPU: one 1024^3 shard through the native group, two of them multiplexed (2048 x 1024 x 1024)
-python bench.py --gpus 1 --force-sharded --grid 1024 --steps 5 --warmup 1 --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_1024_one_shard.json"
+python bench.py --full --gpus 1 --force-sharded --grid 1024 --steps 5 --warmup 1 --no-cpu-baseline 2>&1 | grep '^{"metric' > "$R/bench_1024_one_shard.json"
 python tools/c5_smoke.py > "$R/c5_two_shards_bulk.json" 2> "$R/c5_smoke.err"
 # the parity suite twice more (ties inside a level fall differently from run to run: is any test at its margin?)
 for k in 2; do python -m pytest tests -q -m gpu 2>&1 | grep -aE "^(FAILED|ERROR)|[0-9]+ (passed|failed)" >> "$R/pytest_gpu.txt"; done

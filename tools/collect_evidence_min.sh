@@ -12,9 +12,9 @@ python -m pytest tests -x -q -m gpu > "$R/pytest_gpu.log" 2>&1; echo "pytest rc=
 grep -aE "^(FAILED|ERROR)|[0-9]+ (passed|failed)|pytest rc" "$R/pytest_gpu.log" > "$R/pytest_gpu.txt"
 unset FIESTA_ENVELOPE_LOG
 python -c "import __graft_entry__ as g; g.smoke()" > "$R/smoke.txt" 2>&1; echo "smoke rc=$?" >> "$R/smoke.txt"
-python bench.py > "$R/bench_default.log" 2>&1
+python bench.py --full > "$R/bench_default.log" 2>&1
 grep '^{"metric' "$R/bench_default.log" > "$R/bench_default.json"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$R/stats" -o bench -- python bench.py --no-cpu-baseline > "$R/bench_default_profiled.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$R/stats" -o bench -- python bench.py --full --no-cpu-baseline > "$R/bench_default_profiled.log" 2>&1
 grep '^{"metric' "$R/bench_default_profiled.log" > "$R/bench_default_profiled.json"
 find "$R" -name "*.db" -delete 2>/dev/null
 echo "evidence for $TAG written"

@@ -13,11 +13,11 @@ COUNTS = [7000, 10000, 13000, 17000, 25000, 50000, 100000, 150000, 250000, 33000
 
 def main():
     counts = [int(a) for a in sys.argv[1:]] or COUNTS
-    out = {"command": "python bench.py --obstacles N --engine {auto,cells,envelope} --steps 8 --warmup 2 --no-cpu-baseline --verify-samples 2000",
+    out = {"command": "python bench.py --full --obstacles N --engine {auto,cells,envelope} --steps 8 --warmup 2 --no-cpu-baseline --verify-samples 2000",
            "runs": {}}
     for n in counts:
         for eng in ("auto", "cells", "envelope"):
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--obstacles", str(n), "--engine", eng, "--steps", "8", "--warmup", "2",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--obstacles", str(n), "--engine", eng, "--steps", "8", "--warmup", "2",
                                 "--no-cpu-baseline", "--verify-samples", "2000"], capture_output=True, text=True, cwd=ROOT)
             line = [l for l in r.stdout.splitlines() if l.startswith('{"metric')]
             if not line:
