@@ -1586,12 +1586,14 @@ bool DenseMap::run_cells(fiesta_hip_stats *st, int margin, bool publish, bool in
     a.chg[0] = ins_.p, a.chg[1] = del_.p, a.nchg[0] = (uint32_t)ni, a.nchg[1] = (uint32_t)nd;
     a.dirty_flag = nn_dirty_flag_.p, a.dirty_list = nn_dirty_list_.p, a.dirty_cap = (uint32_t)(ncells / 2);
   }
-  a.dirty_count = &counters_[C_NN_DIRTY];
+  // (the slot of the dirty count holds a full transform's count of cells served against every site: C_NN_SPARSE)
+  if (incremental) a.dirty_count = &counters_[C_NN_DIRTY];
   a.ticket = &counters_[C_FUSE_TICKET];
   if (!g.sharded && !a.g.big()) {  // cells without a list are served one by one (k_nn_close), up to a 64th of the cells
     a.fail_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(ncells / 64, 16), 4096);
     nn_fail_list_.ensure((size_t)a.fail_cap, stream_);
     a.fail_list = nn_fail_list_.p, a.nfail = &counters_[C_NN_BRUTE];
+    if (publish && !incremental) a.nsparse = &counters_[C_NN_SPARSE];
   }
   const unsigned close_blocks = nn_last_brute_ > 0 ? (unsigned)std::min<long long>(nn_last_brute_ + 8, 512) : 1u;
   a.cursor = &counters_[C_NN_CURSOR], a.failed = &counters_[C_NN_FAILED], a.entries = &counters_[C_NN_ENTRIES];
@@ -1606,7 +1608,7 @@ bool DenseMap::run_cells(fiesta_hip_stats *st, int margin, bool publish, bool in
     a.pub = h_counters_, a.queues = &counters_[C_INSERT], a.track_dst = track_ ? &counters_[C_MAXD2] : nullptr;
     a.tag = ++nn_tag_;
     a.pub_failed = C_NN_FAILED, a.pub_entries = C_NN_ENTRIES, a.pub_maxd2 = C_FT_MAXD2, a.pub_tag = C_NN_CURSOR, a.pub_dirty = C_NN_DIRTY;
-    a.pub_brute = C_NN_BRUTE;
+    a.pub_brute = C_NN_BRUTE, a.pub_sparse = C_NN_SPARSE;
   }
   if (!ft_counters_clean_)
     FIESTA_HIP_CHECK(hipMemsetAsync(&counters_[C_FT_OVF0], 0, 7 * sizeof(unsigned long long), stream_));  // + C_FT_MAXD2
@@ -1631,7 +1633,7 @@ bool DenseMap::run_cells(fiesta_hip_stats *st, int margin, bool publish, bool in
     FIESTA_HIP_CHECK(hipEventRecord(ft_ev_[3], stream_));
     if (publish) {
       NnArgs c = a;
-      c.nfail = nullptr;  // (an incremental transform fails on a cell without a list: the full one serves it)
+      c.nfail = nullptr, c.nsparse = nullptr;  // (an incremental transform fails on a cell without a list: the full one serves it)
       hipLaunchKernelGGL(k_nn_close, dim3(1), dim3(256), 0, stream_, c);
       FIESTA_HIP_CHECK(hipGetLastError());
     }
@@ -2321,7 +2323,9 @@ void DenseMap::update_esdf(fiesta_hip_stats *st, bool seed_only) {  // UpdateESD
       bulk_finish(st, h0, /*cells=*/true, /*published=*/true);
       if (h_counters_[C_NN_FAILED] == 0) {
         nn_fail_streak_ = 0;
-        nn_valid_ = !g_.sharded;
+        // A cell served against every site (nothing within its widest window) records a reach its winners lie beyond: a
+        // change out there would not dirty it.  The lists are trusted by the next update only if no such cell stands.
+        nn_valid_ = !g_.sharded && h_counters_[C_NN_SPARSE] == 0;
         return;
       }
       nn_fail_streak_ = std::min(nn_fail_streak_ + 1, 6);

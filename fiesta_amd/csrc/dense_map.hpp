@@ -75,6 +75,7 @@ enum Counter {
   C_NN_FAILED = C_FT_OVF0 + 2,   //   cells that got no list (non-zero: the update is served by the envelope passes instead),
   C_NN_BRUTE = C_FT_OVF0 + 0,    //   cells without a list that k_nn_close serves one by one,
   C_NN_DIRTY = C_FT_OVF0 + 3,    //   cells an incremental transform redoes,
+  C_NN_SPARSE = C_NN_DIRTY,      //   (a full transform, which has no dirty cells) the cells without a list served against every site,
   C_NN_ENTRIES = C_FT_OVF0 + 4,  //   list entries in total
   C_FUSE_TICKET = C_FT_OVF0 + 5,  // k_fuse: work-groups that have finished (the last one reports and clears it: zero between launches)
   C_FT_MAXD2,    // bulk path: largest d^2 written (2^30: a voxel found no obstacle in its region)

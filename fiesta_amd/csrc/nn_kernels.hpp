@@ -46,7 +46,7 @@ struct NnArgs {
   uint32_t *dump;  // 128 dwords nobody reads: lanes outside the array store here, so that every wave issues the same stores
   unsigned long long *pub, *queues, *track_dst;
   unsigned long long tag;
-  int pub_failed, pub_entries, pub_maxd2, pub_tag, pub_dirty, pub_brute;  // slots of pub
+  int pub_failed, pub_entries, pub_maxd2, pub_tag, pub_dirty, pub_brute, pub_sparse;  // slots of pub
   // an INCREMENTAL transform (k_nn_mark, k_nn_lists_dirty, k_nn_fill_dirty): the lists of the last transform are still valid except
   // in the cells whose search window holds a voxel that changed occupancy since -- only those get a new list and a new fill
   const uint32_t *chg[2];       // the insert and the delete queue: linear voxel indices of the array
@@ -60,6 +60,9 @@ struct NnArgs {
   uint32_t *fail_list;          // linear cell index
   unsigned long long *nfail;
   uint32_t fail_cap;
+  // (nullable) those of them served against EVERY site -- no site within the widest window (kWhySparse): their winners lie beyond
+  // the reach their records keep, so the lists of such a transform must not be trusted by an incremental one (dense_map.hip)
+  unsigned long long *nsparse;
   unsigned long long *ticket;   // k_nn_close: work-groups that have finished (zero between launches)
 };
 
@@ -814,6 +817,7 @@ __device__ __forceinline__ void nn_brute_cells(const NnArgs &a, uint32_t *s_site
     const uint32_t info = a.lists[(int64_t)c * nn::kStride + 1];
     const bool dense = ((info >> 8) & 255u) == (uint32_t)nn::kWhyDense;
     const int K = dense ? (int)(info >> 16) : 0;
+    if (!dense && a.nsparse && t == 0) atomicAdd(a.nsparse, 1ull);
     // this thread's two voxels of the cell: (x, y, z) and (x + 4, y, z)
     const int vx = nn::kB * cx + (t >> 6), vy = nn::kB * cy + ((t >> 3) & 7), vz = nn::kB * cz + (t & 7);
     uint32_t b0 = 0xFFFFFFFFu, b1 = 0xFFFFFFFFu, w0 = 0, w1 = 0;
@@ -897,7 +901,9 @@ __global__ __launch_bounds__(256) void k_nn_close(NnArgs a) {
   volatile unsigned long long *h = a.pub;
   h[a.pub_failed] = failed, h[a.pub_entries] = entries, h[a.pub_maxd2] = md;
   if (a.dirty_count) h[a.pub_dirty] = *a.dirty_count;
+  else h[a.pub_sparse] = a.nsparse ? *a.nsparse : 0ull;  // (a full transform has no dirty cells: the same slot)
   if (a.nfail) h[a.pub_brute] = min(*a.nfail, (unsigned long long)a.fail_cap), *a.nfail = 0;
+  if (a.nsparse) *a.nsparse = 0;
   if (a.track_dst && failed == 0) *a.track_dst = a.dirty_flag ? max(*a.track_dst, md) : md;  // (incremental: the cells left alone keep theirs)
   *a.cursor = 0, *a.failed = 0, *a.entries = 0, *a.ticket = 0;
   if (a.dirty_count) *a.dirty_count = 0;

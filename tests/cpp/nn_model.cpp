@@ -16,12 +16,21 @@ using namespace fiesta::nn;
 extern "C" {
 // occ: [nx][ny][nz] bytes (0 / 1).  out: [nx][ny][nz] words (the packed site; 0x80000000 where the cell had no list).
 // stats: [0] cells without a list (the kernels would hand the update to the envelope passes), [1] list entries in total,
-// [2] longest list, [3] sites.  Returns 0.
-static int run_region(const uint8_t *occG, const int *G, const Geom &g, const int *rlo, uint32_t *out, int64_t *stats);
+// [2] longest list, [3] sites.  rec1 (nullable): [ncx][ncy][ncz] words, dword 1 of each cell's record -- the reach an incremental
+// update marks dirty cells by (bits 0..7), and for a cell without a list why (bits 8..15) and its window's reach (bits 16..).
+// Returns 0.
+static int run_region(const uint8_t *occG, const int *G, const Geom &g, const int *rlo, uint32_t *out, int64_t *stats,
+                      uint32_t *rec1 = nullptr);
 
 int nn_model_run(const uint8_t *occ, int nx, int ny, int nz, uint32_t *out, int64_t *stats) {
   const int G[3] = {nx, ny, nz}, zero[3] = {0, 0, 0};
   return run_region(occ, G, whole_geom(nx, ny, nz), zero, out, stats);
+}
+
+// nn_model_run, and the records' dword 1 into rec1
+int nn_model_run_records(const uint8_t *occ, int nx, int ny, int nz, uint32_t *out, int64_t *stats, uint32_t *rec1) {
+  const int G[3] = {nx, ny, nz}, zero[3] = {0, 0, 0};
+  return run_region(occ, G, whole_geom(nx, ny, nz), zero, out, stats, rec1);
 }
 
 // A SHARD: the array at l0[] (extents ln[]) of the global grid G[], its region grown by mc voxels (nn_core.hpp: region_geom).
@@ -35,7 +44,7 @@ int nn_model_run_shard(const uint8_t *occ, const int *G, const int *l0, const in
 }
 }
 
-static int run_region(const uint8_t *occG, const int *G, const Geom &g, const int *rlo, uint32_t *out, int64_t *stats) {
+static int run_region(const uint8_t *occG, const int *G, const Geom &g, const int *rlo, uint32_t *out, int64_t *stats, uint32_t *rec1) {
   const int nx = g.nx, ny = g.ny, nz = g.nz;
   auto occ_at = [&](int x, int y, int z) { return occG[((int64_t)(x + rlo[0]) * G[1] + (y + rlo[1])) * G[2] + (z + rlo[2])]; };
   const int64_t nrows = (int64_t)g.ncx * g.ncy;
@@ -69,6 +78,7 @@ static int run_region(const uint8_t *occG, const int *G, const Geom &g, const in
           n = build_list(src, solo, cx, cy, cz, list.data(), false, kNone, 0xFFFFFFFFu, frame_of(g));
         }
         if ((int)list[0] != n) return 2;
+        if (rec1) rec1[((int64_t)cx * g.ncy + cy) * g.ncz + cz] = list[1];
         if (n == 0) ++failed;
         entries += n;
         if (n > longest) longest = n;

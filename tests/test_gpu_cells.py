@@ -378,10 +378,17 @@ def test_a_few_cells_without_a_list_are_served_one_by_one(hip_lib):
     st = m.UpdateESDF()
     assert st["bulk"] == 1 and st["cells"] == 1 and st["nn_failed"] == 0 and st["nn_brute_cells"] > sparse_cells, st
     check_exact(m, shape)
-    # a small delta next: the incremental transform meets the cells without a list again -- it fails on them, the same call runs
-    # in full (brute force included), and the one after that is incremental again if nothing of it touches such a cell
-    free(m, S[:1])
+    # a one-voxel delta next: free the corner's nearest obstacle, 8 cells from the corner cell -- beyond the 7 cells of
+    # reach its record keeps, so an incremental transform would not redo it.  A transform that served cells against every site
+    # leaves no lists an incremental one may trust: this update runs in full (brute force included) and is exact.
+    occ = m.download_field(("occ",))["occ"].reshape(shape)
+    idx = ndimage.distance_transform_edt(occ == 0, return_distances=False, return_indices=True)
+    w = np.array([int(idx[k][0, 0, 0]) for k in range(3)], np.int32)
+    assert (w // 8).max() > 7, w   # (beyond the widest reach a record keeps: kKmax = 7 cells)
+    free(m, w[None])
     st = m.UpdateESDF()
-    assert st["bulk"] == 1 and st["cells"] == 1 and st["nn_failed"] == 0, st
+    assert st["deleted"] == 1, st
     check_exact(m, shape)
+    assert st["bulk"] == 1 and st["cells"] == 1 and st["nn_failed"] == 0, st
+    assert st["nn_incremental"] == 0 and st["nn_brute_cells"] > 0, st
     m.close()

@@ -25,6 +25,8 @@ def model():
     lib = C.CDLL(LIB)
     lib.nn_model_run.restype = C.c_int
     lib.nn_model_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.nn_model_run_records.restype = C.c_int
+    lib.nn_model_run_records.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -228,3 +230,117 @@ def test_a_shards_region_starts_on_whole_bitmap_words_along_z(model):
     out, st = run_shard(model, occ, l0, ln, 40)
     assert st["failed"] == 0, st
     check_shard_exact(occ, out, l0, ln)
+
+
+# ---- the reach a cell's record keeps: what the incremental transform trusts ------------------------------------------------------
+# k_nn_mark (nn_kernels.hpp) redoes a cell only if a changed voxel lies within record[1] & 255 cells of it.  That is sound only if
+# no site outside the (2 R + 1)^3 cells around a cell can win in it: then an insert out there cannot be nearer than what the
+# cell holds, and a delete out there cannot remove what it holds.  A cell without a list for want of a site in reach
+# (kWhySparse) records kKmax, yet its winners lie farther: its reach is no bound, and the host must not trust it.
+KMAX, WHY_SPARSE, WHY_DENSE = 7, 1, 2
+
+
+def run_records(lib, occ):
+    nx, ny, nz = occ.shape
+    occ = np.ascontiguousarray(occ, dtype=np.uint8)
+    out = np.full(occ.shape, 0xDEADBEEF, np.uint32)
+    stats = np.zeros(4, np.int64)
+    rec1 = np.full(tuple((s + 7) // 8 for s in occ.shape), 0xDEADBEEF, np.uint32)
+    rc = lib.nn_model_run_records(occ.ctypes.data, nx, ny, nz, out.ctypes.data, stats.ctypes.data, rec1.ctypes.data)
+    assert rc == 0, rc
+    return out, dict(failed=int(stats[0]), sites=int(stats[3])), rec1
+
+
+def reach_violations(occ, reach):
+    """voxels of the cells with reach[c] >= 0 for which some in-grid voxel outside the (2 R + 1)^3 cells around their cell lies
+    strictly nearer than their nearest obstacle (scipy).  Along each axis the nearest voxel outside is at 8 (c - R) - 1 or
+    8 (c + R + 1), where that lies inside the grid; the other two coordinates stay the voxel's."""
+    shape = occ.shape
+    idx = ndimage.distance_transform_edt(occ == 0, return_distances=False, return_indices=True)
+    g = np.meshgrid(*[np.arange(s) for s in shape], indexing="ij")
+    want = sum((idx[k] - g[k]) ** 2 for k in range(3))
+    R = reach[g[0] // 8, g[1] // 8, g[2] // 8]
+    far = 1 << 20
+    gap = np.full(shape, far, np.int64)
+    for k in range(3):
+        c = g[k] // 8
+        lo, hi = 8 * (c - R) - 1, 8 * (c + R + 1)
+        gap = np.minimum(gap, np.where(lo >= 0, g[k] - lo, far))
+        gap = np.minimum(gap, np.where(hi < shape[k], hi - g[k], far))
+    return int(((R >= 0) & (gap * gap < want)).sum())
+
+
+def _corner_scene():
+    """test_gpu_cells.py: test_a_few_cells_without_a_list_are_served_one_by_one -- no site with every coordinate below 70"""
+    S = np.random.RandomState(31).randint(0, 128, (700, 3))
+    S = S[~np.all(S < 70, axis=1)]
+    occ = np.zeros((128, 128, 128), np.uint8)
+    occ[S[:, 0], S[:, 1], S[:, 2]] = 1
+    return occ
+
+
+def _slab_scene(shape, density, seed, z0, z1):
+    occ = scatter(shape, density, seed)
+    occ[:, :, z0:z1] = 0
+    return occ
+
+
+def _block_scene():
+    occ = scatter((64, 64, 64), 3.7e-4, 11)
+    occ[28:35, 28:35, 28:35] = 1
+    return occ
+
+
+def _plane_scene():
+    occ = np.zeros((61, 45, 83), np.uint8)
+    occ[30, :, :] = 1
+    return occ
+
+
+REACH_SCENES = [pytest.param(lambda c=c: scatter(*c), id="scatter-%dx%dx%d" % c[0]) for c in CASES] + [
+    pytest.param(_corner_scene, id="empty-corner"),
+    pytest.param(lambda: _slab_scene((61, 45, 83), 3e-3, 3, 12, 71), id="slab-61x45x83"),
+    pytest.param(lambda: _slab_scene((33, 17, 130), 4e-3, 5, 15, 115), id="slab-33x17x130"),
+    pytest.param(_block_scene, id="solid-block"),
+    pytest.param(_plane_scene, id="plane"),
+]
+
+
+@pytest.mark.parametrize("make", REACH_SCENES)
+def test_a_cells_recorded_reach_bounds_every_site_that_can_win_in_it(model, make):
+    """every listed cell, and every cell without a list for too many survivors (kWhyDense: its window's reach, bits 16..): no
+    in-grid voxel outside its reach is strictly nearer to any of its voxels than that voxel's nearest obstacle (ties may lie
+    outside: ids are tie-equivalent).  Cells without a list for want of a site in reach must say so (kWhySparse), and no more.
+    The check has teeth: one cell less of reach for the listed cells breaks it."""
+    occ = make()
+    if not occ.any():
+        occ[tuple(s // 2 for s in occ.shape)] = 1
+    out, st, rec1 = run_records(model, occ)
+    assert st["sites"] == int(occ.sum())
+    why = (rec1 >> 8) & 255
+    listed, dense, sparse = why == 0, why == WHY_DENSE, why == WHY_SPARSE
+    assert np.all(listed | dense | sparse), np.unique(why)        # (a whole grid has no open face)
+    assert int((~listed).sum()) == st["failed"]
+    r = (rec1 & 255).astype(np.int64)
+    assert np.all((r[listed] >= 1) & (r[listed] <= KMAX)), np.unique(r[listed])
+    assert np.all(r[~listed] == KMAX)                              # (what k_nn_mark reads for a cell without a list)
+    wr = (rec1 >> 16).astype(np.int64)
+    assert np.all((wr[dense] >= 1) & (wr[dense] <= KMAX)), np.unique(wr[dense])
+    reach = np.where(listed, r, np.where(dense, wr, -1))
+    assert reach_violations(occ, reach) == 0
+    if listed.any():
+        assert reach_violations(occ, np.where(listed, r - 1, -1)) > 0, "the reach check cannot tell a reach one cell short"
+    print(st, "listed", int(listed.sum()), "dense", int(dense.sum()), "sparse", int(sparse.sum()))
+
+
+def test_the_reach_scenes_cover_every_kind_of_cell(model):
+    """the scenes above hold cells of all three kinds the incremental transform must tell apart"""
+    out, st, rec1 = run_records(model, _corner_scene())
+    why = (rec1 >> 8) & 255
+    assert int((why == WHY_SPARSE).sum()) > 0 and int((why == WHY_DENSE).sum()) == 0
+    assert why[0, 0, 0] == WHY_SPARSE                              # (the corner cell: its winner lies 8 cells away)
+    out, st, rec1 = run_records(model, _block_scene())
+    why = (rec1 >> 8) & 255
+    assert int((why == WHY_DENSE).sum()) > 0 and int((why == 0).sum()) > 0
+    out, st, rec1 = run_records(model, _plane_scene())
+    assert int((((rec1 >> 8) & 255) == WHY_DENSE).sum()) > 0
