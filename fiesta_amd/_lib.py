@@ -67,6 +67,12 @@ class RaycastParams(C.Structure):
                 ("r_cornor", C.c_double * 3), ("dedup", C.c_int32), ("inverse", C.c_int32)]
 
 
+class PathResult(C.Structure):
+    """fiesta_hip_path_result: one array per output of fiesta_hip_path_clearance, every pointer nullable"""
+    _fields_ = [("min_dist", C.c_void_p), ("min_index", C.c_void_p), ("min_pos", C.c_void_p), ("min_grad", C.c_void_p),
+                ("first_below", C.c_void_p), ("first_below_pos", C.c_void_p), ("n_samples", C.c_void_p)]
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/fiesta_hip.h declares (used by the CPU export test)."""
     text = open(header_path).read()
@@ -158,6 +164,8 @@ def load():
         "fiesta_hip_get_dist_grad": (C.c_int, [vp, vp, i64, vp, vp]),
         "fiesta_hip_get_dist_grad_dev": (C.c_int, [vp, vp, i64, vp, vp]),
         "fiesta_hip_host_cache_fetches": (C.c_int, [vp, vp]),
+        "fiesta_hip_path_clearance": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
+        "fiesta_hip_path_clearance_dev": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
         "fiesta_hip_get_occupancy_vox": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_get_occupancy_pos": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_download_field": (C.c_int, [vp, vp, vp, vp, vp]),

@@ -1,6 +1,7 @@
 // fiesta_amd/csrc/c_api.hip -- the extern "C" boundary declared in include/fiesta_hip.h.
 // Every entry point converts C++ exceptions into a status code + thread-local message; nothing throws
 // across the ABI and no HIP / C++ type appears in a signature.
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -50,12 +51,23 @@ DenseMap &dense(fiesta_hip_map *m, const char *what) {
   if (!m->dense) throw Error(FIESTA_HIP_ERR_INVALID, std::string(what) + ": only available on array-mode maps");
   return *m->dense;
 }
+// the whole-call errors of fiesta_hip_path_clearance[_dev] (include/fiesta_hip.h); host_offsets: the CSR rules as well
+void path_args(fiesta_hip_map *m, const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+               const fiesta_hip_path_result *r, bool host_offsets) {
+  need(m && w && off && r, "null argument");
+  need(n_wp >= 0 && n_paths >= 0, "negative count");
+  need(std::isfinite(step) && step > 0, "path_clearance: step must be finite and > 0");
+  need(!std::isnan(margin), "path_clearance: margin is NaN");
+  if (!host_offsets) return;
+  need(off[0] == 0 && off[n_paths] == n_wp, "path_clearance: offsets[0] must be 0 and offsets[n_paths] = n_waypoints");
+  for (int64_t p = 0; p < n_paths; ++p) need(off[p] <= off[p + 1], "path_clearance: offsets must be non-decreasing");
+}
 }  // namespace
 
 extern "C" {
 
 const char *fiesta_hip_last_error(void) { return g_last_error.c_str(); }
-int fiesta_hip_version(void) { return 100; }
+int fiesta_hip_version(void) { return 101; }
 
 int fiesta_hip_device_count(void) {
   int n = 0;
@@ -365,6 +377,26 @@ int fiesta_hip_get_dist_grad_dev(fiesta_hip_map *m, const double *pos_dev, int64
   return guarded([&] {
     need(m && (n == 0 || (pos_dev && dist_dev)) && n >= 0, "bad argument");
     dense(m, "get_dist_grad_dev").get_dist_grad(pos_dev, n, dist_dev, grad_dev, true);
+  });
+}
+int fiesta_hip_path_clearance(fiesta_hip_map *m, const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step,
+                              double margin, const fiesta_hip_path_result *r) {
+  return guarded([&] {
+    path_args(m, w, n_wp, off, n_paths, step, margin, r, true);
+    if (m->dense)
+      m->dense->path_clearance(w, n_wp, off, n_paths, step, margin, *r, false);
+    else
+      m->hash->path_clearance(w, n_wp, off, n_paths, step, margin, *r, false);
+  });
+}
+int fiesta_hip_path_clearance_dev(fiesta_hip_map *m, const double *w_dev, int64_t n_wp, const int64_t *off_dev, int64_t n_paths,
+                                  double step, double margin, const fiesta_hip_path_result *r) {
+  return guarded([&] {
+    path_args(m, w_dev, n_wp, off_dev, n_paths, step, margin, r, false);
+    if (m->dense)
+      m->dense->path_clearance(w_dev, n_wp, off_dev, n_paths, step, margin, *r, true);
+    else
+      m->hash->path_clearance(w_dev, n_wp, off_dev, n_paths, step, margin, *r, true);
   });
 }
 int fiesta_hip_host_cache_fetches(fiesta_hip_map *m, int64_t *fetches) {

@@ -28,6 +28,7 @@
 #include "nn_kernels.hpp"
 #include "mask_kernels.hpp"
 #include "level_kernels.hpp"
+#include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
 #include <algorithm>
@@ -658,6 +659,15 @@ __global__ void k_query_trilinear(Geom g, const vox_t *coc, const double *pos, i
   dist[i] = query_trilinear(g, wd, p, grad ? gr : nullptr);
   if (grad) grad[3 * i] = gr[0], grad[3 * i + 1] = gr[1], grad[3 * i + 2] = gr[2];
 }
+// the sample evaluator of the path kernels (path_kernels.hpp): k_query_trilinear's arithmetic on the field itself
+struct DensePathEval {
+  Geom g;
+  const vox_t *coc;
+  __device__ double operator()(const double *p, double *grad) const {
+    FieldWords wd{g, coc};
+    return query_trilinear(g, wd, p, grad);
+  }
+};
 // GetOccupancy x2 (src/ESDFMap.cpp:452-465)
 __global__ void k_query_occ_vox(Geom g, const uint32_t *occbits, const int32_t *vox, int64_t n, int32_t *out) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -2497,6 +2507,19 @@ void DenseMap::get_dist_grad(const double *pos, int64_t n, double *dist, double 
   FIESTA_HIP_CHECK(hipMemcpyAsync(dist, stage_c_.p, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
   if (grad) FIESTA_HIP_CHECK(hipMemcpyAsync(grad, stage_b_.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+void DenseMap::path_clearance(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+                              const fiesta_hip_path_result &r, bool dev) {
+  if (n_paths <= 0) return;
+  if (!dev && path_host_samples(w, off, n_paths, step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
+    HostWords wd{this};
+    auto ev = [&](const double *p, double *grad) { return query_trilinear(g_, wd, p, grad); };
+    path_host(ev, w, off, n_paths, step, margin, r);
+    return;
+  }
+  use_device();
+  path_clearance_run(stream_, path_in_, path_tmp_, path_out_, DensePathEval{g_, (const vox_t *)coc_}, w, n_wp, off, n_paths, step,
+                     margin, r, dev);
 }
 void DenseMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n <= 0) return;

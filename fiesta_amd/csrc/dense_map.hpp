@@ -142,6 +142,9 @@ class DenseMap {
   void get_dist_grad(const double *pos, int64_t n, double *dist, double *grad, bool dev);
   void get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out);
   void get_occupancy_pos(const double *pos, int64_t n, int32_t *out);
+  // fiesta_hip_path_clearance[_dev] (path_kernels.hpp); arguments checked by the caller
+  void path_clearance(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+                      const fiesta_hip_path_result &r, bool dev);
   int64_t host_brick_fetches() const;  // bricks fetched for scalar queries so far (tests, bench)
 
   void download_field(int32_t *d2, int32_t *coc, uint8_t *occ, double *logodds);
@@ -327,6 +330,7 @@ class DenseMap {
 
   // staging
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_;
+  DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path clearance: staged inputs, plan / piece records, staged outputs
   // raycast front-end state (per-frame stamp arrays = Fiesta::set_occ_/set_free_, include/Fiesta.h:107-110;
   // per-ray traversal lists), lazily allocated by raycast.hip
   struct RaycastState;

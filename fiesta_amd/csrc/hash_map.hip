@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "level_kernels.hpp"
+#include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
 namespace fiesta {
@@ -481,6 +482,17 @@ __global__ void k_h_query_trilinear(Geom g, const int32_t *dir, PageTable tab, c
   auto corner = [&](int vx, int vy, int vz) { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); };
   dist[i] = h_trilinear(g, corner, p, grad ? grad + 3 * i : nullptr);
 }
+// the sample evaluator of the path kernels (path_kernels.hpp): k_h_query_trilinear's arithmetic over the same page-table corners
+struct HashPathEval {
+  Geom g;
+  const int32_t *dir;
+  PageTable tab;
+  const vox_t *coc;
+  __device__ double operator()(const double *p, double *grad) const {
+    auto corner = [&](int vx, int vy, int vz) { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); };
+    return h_trilinear(g, corner, p, grad);
+  }
+};
 // a brick of the host-side cache: the 16^3 distances and occupancy bits of map brick (bx, by, bz), straight into pinned memory
 __global__ __launch_bounds__(256) void k_h_fetch_brick(Geom g, const int32_t *dir, PageTable tab, const vox_t *coc, const uint32_t *occbits, int bx,
                                                        int by, int bz, double *dst) {
@@ -1434,6 +1446,19 @@ void HashMap::get_dist_grad(const double *pos, int64_t n, double *dist, double *
   FIESTA_HIP_CHECK(hipMemcpyAsync(dist, stage_c_.p, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
   if (grad) FIESTA_HIP_CHECK(hipMemcpyAsync(grad, stage_b_.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+void HashMap::path_clearance(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+                             const fiesta_hip_path_result &r, bool dev) {
+  if (n_paths <= 0) return;
+  if (!dev && path_host_samples(w, off, n_paths, step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
+    auto corner = [&](int vx, int vy, int vz) { return host_distance(vx, vy, vz); };
+    auto ev = [&](const double *p, double *grad) { return h_trilinear(g_, corner, p, grad); };
+    path_host(ev, w, off, n_paths, step, margin, r);
+    return;
+  }
+  use_device();
+  path_clearance_run(stream_, path_in_, path_tmp_, path_out_, HashPathEval{g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p}, w,
+                     n_wp, off, n_paths, step, margin, r, dev);
 }
 void HashMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n > 0 && n <= kHostQueries) {

@@ -78,6 +78,9 @@ class HashMap {
   void get_dist_grad(const double *pos, int64_t n, double *dist, double *grad);
   void get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out);
   void get_occupancy_pos(const double *pos, int64_t n, int32_t *out);
+  // fiesta_hip_path_clearance[_dev] (path_kernels.hpp); arguments checked by the caller
+  void path_clearance(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+                      const fiesta_hip_path_result &r, bool dev);
   // every voxel of every allocated page, page order: vox (map voxel coordinates), d2, coc, occ; returns the count
   int64_t download(int32_t *vox, int32_t *d2, int32_t *coc, uint8_t *occ);
   void download_counts(int32_t *num_hit, int32_t *num_miss);  // same order as download()
@@ -164,6 +167,7 @@ class HashMap {
   int64_t dropped_host_ = 0;  // voxels of observe_box() requests clipped away by the window (added to C_DROPPED in stats)
   unsigned long long *counters_ = nullptr, *h_counters_ = nullptr;
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_, stage_d_;
+  DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path clearance: staged inputs, plan / piece records, staged outputs
 };
 
 void raycast_single(const double *start, const double *end, const double *minv, const double *maxv, double *out,

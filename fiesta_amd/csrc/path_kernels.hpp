@@ -1,0 +1,405 @@
+// fiesta_amd/csrc/path_kernels.hpp -- batched path clearance: fiesta_hip_path_clearance / _dev (include/fiesta_hip.h).
+//
+// A planner asks "does this candidate path stay clear, and where is it tightest?" for thousands of paths per cycle.  Through the
+// point queries that is: materialise every sample position, query each one, move value + gradient back, reduce on the caller's
+// side (the reference's callers loop over GetDistWithGradTrilinear, src/ESDFMap.cpp:481-540).  Here the samples are generated
+// on chip by the header's sample rule and reduced in registers; per path only a few words leave the device.
+//
+// The kernels are templated over the SAMPLE EVALUATOR -- the dense map's query_trilinear<FieldWords>, the hash-block map's
+// h_trilinear over its page-table corners -- so a sample's value is the point query's, bit for bit, by construction.
+//   k_path_check   (device variant only; one work-group) offsets against the CSR rules, per path
+//   k_path_plan    one wave per path: lanes stride over its segments, compute S, a wave prefix scan (int64, carried across chunks
+//                  of 64 segments) gives every waypoint's first sample index (`base`) and the path's n_samples; validates the path
+//   k_path_pieces  one work-group: piece counts scanned over the paths (piece offsets); the total stays on the device
+//   k_path_eval    persistent grid, one wave per piece: lane l takes samples base + l, base + l + 64, ... (neighbouring lanes read
+//                  neighbouring corner words).  64 consecutive samples lie on at most 64 consecutive segments: per group the wave
+//                  loads those segments' first sample indices (one coalesced load) and every lane finds its segment by a 6-step
+//                  binary search over them through __shfl (never a walk from the path's start, no dependent global loads); each
+//                  lane keeps a running (value, lowest index) minimum and a first-below index, a __shfl_xor reduction (value
+//                  compare, then index) leaves one record per piece
+//   k_path_finish  one lane per path: its piece records in index order, then the outputs; the gradient is computed ONCE per path,
+//                  at the winning sample, by the point query's code
+// No atomics at all: the result depends neither on the launch shape nor on the piece size nor on scheduling.  After k_path_check /
+// k_path_plan every kernel reads the path ranges they stored (`rng`), never the caller's offsets again: whatever the caller's
+// arrays hold, every index stays inside [0, n_waypoints).
+#pragma once
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <vector>
+
+#include "../../include/fiesta_hip.h"
+#include "common.hpp"
+#include "dense_map.hpp"
+
+namespace fiesta {
+namespace {  // (this header is included by two translation units)
+
+constexpr long long kPathPiece = 1024;        // samples per piece at least (16 per lane of the wave that evaluates it)
+constexpr int64_t kPathRecords = 1 << 18;     // piece records per call: a path gets at most max(1, kPathRecords / n_paths) pieces
+constexpr int kPathEvalBlocks = 1024;         // persistent grid of k_path_eval: 4 work-groups of 4 waves per CU
+constexpr double kPathMaxRatio = 16777216.0;  // 2^24: a segment with L / step above this makes its path invalid
+// The host variant answers a batch of at most this many samples from the host brick cache (the C++ facade's "check this one
+// segment" call): a launch + synchronise costs tens of microseconds, a brick-cache trilinear ~0.1 us, so below a few hundred
+// samples the host loop wins even when it has to fetch a brick or two.
+constexpr int64_t kHostPathSamples = 256;
+
+struct PathRec {  // one piece: its minimum, the minimum's sample index, the first index below the margin (LLONG_MAX: none)
+  double v;
+  long long i, fb;
+};
+
+// ---- the sample rule (include/fiesta_hip.h), shared by the kernels and the host loop --------------------------------------------
+// S of segment a -> b; false if L / step > 2^24 (or is not a number: a non-finite waypoint)
+__host__ __device__ inline bool path_segment_samples(const double *a, const double *b, double step, long long *S) {
+  const double d0 = b[0] - a[0], d1 = b[1] - a[1], d2 = b[2] - a[2];
+  const double L = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+  const double q = L / step;
+  if (!(q <= kPathMaxRatio)) return false;
+  const long long s = (long long)ceil(q);
+  *S = s < 1 ? 1 : s;
+  return true;
+}
+__host__ __device__ inline bool path_finite(const double *a) {
+  return __builtin_isfinite(a[0]) && __builtin_isfinite(a[1]) && __builtin_isfinite(a[2]);
+}
+// the waypoint whose segment holds sample s: the last j in [lo, hi] with base[j] <= s
+__host__ __device__ inline int64_t path_find(const int64_t *base, int64_t lo, int64_t hi, long long s) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (base[mid] <= s)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  return lo;
+}
+// sample k of S of the segment a -> a + 3
+__host__ __device__ inline void path_point(const double *a, long long k, long long S, double *p) {
+  const double t = (double)k / (double)S;
+  for (int c = 0; c < 3; ++c) p[c] = a[c] + (a[3 + c] - a[c]) * t;
+}
+// sample s of a path of nw waypoints w (x3) whose first sample indices are base; j = path_find(base, .., s)
+__host__ __device__ inline void path_sample(const double *w, const int64_t *base, int64_t nw, int64_t j, long long s, double *p) {
+  const double *a = w + 3 * j;
+  if (j == nw - 1) {  // the final sample: the last waypoint itself
+    p[0] = a[0], p[1] = a[1], p[2] = a[2];
+    return;
+  }
+  path_point(a, s - base[j], base[j + 1] - base[j], p);
+}
+// samples per piece of a path of n samples: at least kPathPiece, and at most max_pieces pieces
+__host__ __device__ inline long long path_piece_size(long long n, long long max_pieces) {
+  const long long ps = (n + max_pieces - 1) / max_pieces;
+  return ps < kPathPiece ? kPathPiece : ps;
+}
+// the outputs of path p (n: its n_samples; best / bi / fb: the minimum, its index, the first index below the margin or -1)
+template <class Eval>
+__host__ __device__ inline void path_write(Eval &ev, const fiesta_hip_path_result &r, int64_t p, long long n, double best, long long bi,
+                                           long long fb, const double *w, const int64_t *base, int64_t nw) {
+  const double nan = NAN;
+  double mp[3] = {nan, nan, nan}, g[3] = {0, 0, 0}, fp[3] = {nan, nan, nan};
+  double md = n < 0 ? nan : (double)INFINITY;
+  long long mi = -1, fi = -1;
+  if (n > 0) {
+    md = best, mi = bi;
+    path_sample(w, base, nw, path_find(base, 0, nw - 1, bi), bi, mp);
+    (void)ev(mp, g);  // the gradient of the point query at the winning sample (its value is `best`, bit for bit)
+    if (fb >= 0) {
+      fi = fb;
+      path_sample(w, base, nw, path_find(base, 0, nw - 1, fb), fb, fp);
+    }
+  }
+  if (r.n_samples) r.n_samples[p] = n;
+  if (r.min_dist) r.min_dist[p] = md;
+  if (r.min_index) r.min_index[p] = mi;
+  if (r.first_below) r.first_below[p] = fi;
+  for (int c = 0; c < 3; ++c) {
+    if (r.min_pos) r.min_pos[3 * p + c] = mp[c];
+    if (r.min_grad) r.min_grad[3 * p + c] = g[c];
+    if (r.first_below_pos) r.first_below_pos[3 * p + c] = fp[c];
+  }
+}
+
+// ---- kernels ---------------------------------------------------------------------------------------------------------------------
+// inclusive scan of one value per thread over a work-group of up to 16 waves; *total = the whole group's
+template <class Op>
+__device__ inline long long block_inclusive(long long v, long long ident, Op op, long long *lds, long long *total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long u = __shfl_up(v, o, 64);
+    if (lane >= o) v = op(v, u);
+  }
+  if (lane == 63) lds[wv] = v;
+  __syncthreads();
+  long long pre = ident, tot = ident;
+  for (int k = 0; k < nwv; ++k) {
+    if (k < wv) pre = op(pre, lds[k]);
+    tot = op(tot, lds[k]);
+  }
+  __syncthreads();
+  *total = tot;
+  return op(pre, v);
+}
+
+// Device variant: path p is flagged (nsamp = -1) when its range is reversed, leaves [0, n_wp], or starts below an earlier offset
+// that lies in [0, n_wp] (it could overlap an earlier path).  Valid paths therefore own disjoint waypoint ranges: k_path_plan's
+// writes never race.  Entries outside [0, n_wp] do not enter the running maximum: a garbage offset costs its own two paths only.
+// rng[2p], rng[2p + 1] = the range as checked (what every later kernel uses).
+__global__ __launch_bounds__(1024) void k_path_check(const int64_t *off, int64_t n_paths, int64_t n_wp, int64_t *nsamp, int64_t *rng) {
+  __shared__ long long lds[16];
+  long long carry = LLONG_MIN;  // max of the entries off[0 .. c - 1] that lie in [0, n_wp]
+  for (int64_t c = 0; c < n_paths; c += blockDim.x) {
+    const int64_t p = c + threadIdx.x;
+    const long long o0 = p < n_paths ? (long long)off[p] : LLONG_MIN;
+    long long tot;
+    long long m = block_inclusive(o0 >= 0 && o0 <= n_wp ? o0 : LLONG_MIN, LLONG_MIN, [](long long a, long long b) { return a > b ? a : b; },
+                                  lds, &tot);
+    m = m > carry ? m : carry;  // max of the in-range entries of off[0 .. p]
+    if (p < n_paths) {
+      const long long o1 = off[p + 1];
+      const bool ok = o0 >= 0 && o0 == m && o1 >= o0 && o1 <= n_wp;
+      nsamp[p] = ok ? 0 : -1;
+      rng[2 * p] = ok ? o0 : 0, rng[2 * p + 1] = ok ? o1 : 0;
+    }
+    carry = tot > carry ? tot : carry;
+  }
+}
+
+// one wave per path: base[i] = index of waypoint i's first sample in its path, nsamp[p] = n_samples (-1: invalid, 0: empty)
+// (host variant, offsets checked on the host: rng is written here)
+__global__ __launch_bounds__(256) void k_path_plan(const double *w, const int64_t *off, int64_t n_paths, double step, int checked,
+                                                   int64_t *base, int64_t *nsamp, int64_t *rng) {
+  const int64_t p = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (p >= n_paths) return;             // (uniform in the wave)
+  if (checked && nsamp[p] < 0) return;  // offsets out of order or out of range (k_path_check)
+  const int64_t o0 = checked ? rng[2 * p] : off[p], o1 = checked ? rng[2 * p + 1] : off[p + 1];
+  if (!checked && lane == 0) rng[2 * p] = o0, rng[2 * p + 1] = o1;
+  long long carry = 0;
+  int bad = 0;
+  for (int64_t c = o0; c < o1; c += 64) {
+    const int64_t i = c + lane;
+    long long S = 0;
+    int lane_bad = 0;
+    if (i < o1) {
+      const double *a = w + 3 * i;
+      lane_bad = !path_finite(a);
+      if (i + 1 < o1 && !path_segment_samples(a, a + 3, step, &S)) lane_bad = 1;
+    }
+    long long incl = S;
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long u = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += u;
+    }
+    if (i < o1) base[i] = carry + incl - S;
+    carry += __shfl(incl, 63, 64);
+    bad |= __any(lane_bad);
+  }
+  if (lane == 0) nsamp[p] = bad ? -1 : (o1 > o0 ? carry + 1 : 0);
+}
+
+// one work-group: poff[p] = first piece of path p, poff[n_paths] = pieces in total (read by k_path_eval, never by the host)
+__global__ __launch_bounds__(1024) void k_path_pieces(const int64_t *nsamp, int64_t n_paths, long long max_pieces, int64_t *poff) {
+  __shared__ long long lds[16];
+  long long carry = 0;
+  for (int64_t c = 0; c < n_paths; c += blockDim.x) {
+    const int64_t p = c + threadIdx.x;
+    long long k = 0;
+    if (p < n_paths) {
+      const long long n = nsamp[p];
+      if (n > 0) {
+        const long long ps = path_piece_size(n, max_pieces);
+        k = (n + ps - 1) / ps;
+      }
+    }
+    long long tot;
+    const long long incl = block_inclusive(k, 0ll, [](long long a, long long b) { return a + b; }, lds, &tot);
+    if (p < n_paths) poff[p] = carry + incl - k;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) poff[n_paths] = carry;
+}
+
+template <class Eval>
+__global__ __launch_bounds__(256) void k_path_eval(Eval ev, const double *w, const int64_t *rng, const int64_t *base, const int64_t *nsamp,
+                                                   const int64_t *poff, int64_t n_paths, long long max_pieces, double margin, PathRec *rec) {
+  const int lane = threadIdx.x & 63;
+  const int64_t total = poff[n_paths];
+  const int64_t stride = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t piece = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6; piece < total; piece += stride) {
+    const int64_t p = path_find(poff, 0, n_paths - 1, piece);  // the last path that starts at or before this piece (it has pieces)
+    const long long n = nsamp[p], ps = path_piece_size(n, max_pieces);
+    const long long s0 = (piece - poff[p]) * ps, s1 = s0 + ps < n ? s0 + ps : n;
+    const int64_t o0 = rng[2 * p], nw = rng[2 * p + 1] - o0;
+    const double *pw = w + 3 * o0;
+    const int64_t *pb = base + o0;
+    int64_t jw = path_find(pb, 0, nw - 1, s0);  // the segment of the group's first sample (uniform in the wave)
+    double best = INFINITY;
+    long long bi = LLONG_MAX, fb = LLONG_MAX;
+    for (long long sg = s0; sg < s1; sg += 64) {  // (every lane takes part in the shuffles, also past s1)
+      const long long s = sg + lane;
+      const long long bl = jw + lane < nw ? pb[jw + lane] : LLONG_MAX;  // first samples of segments jw .. jw + 63
+      const long long bn = jw + 64 < nw ? pb[jw + 64] : LLONG_MAX;
+      int i = 0;  // the last i with b_i <= s (b_0 <= sg <= s): exactly 6 halvings of [0, 63]
+      for (int h = 32; h > 0; h >>= 1) {
+        const long long bm = __shfl(bl, i + h, 64);
+        if (bm <= s) i += h;
+      }
+      const long long bj = __shfl(bl, i, 64), nx = __shfl(bl, i < 63 ? i + 1 : 63, 64);
+      const long long end = i < 63 ? nx : bn;  // first sample of segment j + 1
+      const int64_t j = jw + i;
+      if (s < s1) {
+        double q[3];
+        const double *a = pw + 3 * j;
+        if (j == nw - 1)
+          q[0] = a[0], q[1] = a[1], q[2] = a[2];  // the final sample: the last waypoint itself
+        else
+          path_point(a, s - bj, end - bj, q);
+        const double v = ev(q, nullptr);
+        if (bi == LLONG_MAX || v < best) best = v, bi = s;  // (indices grow: a tie keeps the lower one)
+        if (fb == LLONG_MAX && v < margin) fb = s;
+      }
+      // the next group's first sample sg + 64 lies in lane 63's segment, or in the one after it if that segment ends at sg + 63:
+      // its window must start exactly there (its 64 samples may cover 64 segments, S = 1 each)
+      jw = (int64_t)__shfl((long long)j, 63, 64) + (sg + 64 >= __shfl(end, 63, 64) ? 1 : 0);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const double ov = __shfl_xor(best, o, 64);
+      const long long oi = __shfl_xor(bi, o, 64), of = __shfl_xor(fb, o, 64);
+      if (oi != LLONG_MAX && (bi == LLONG_MAX || ov < best || (ov == best && oi < bi))) best = ov, bi = oi;
+      fb = of < fb ? of : fb;
+    }
+    if (lane == 0) rec[piece] = PathRec{best, bi, fb};
+  }
+}
+
+template <class Eval>
+__global__ __launch_bounds__(256) void k_path_finish(Eval ev, const double *w, const int64_t *rng, const int64_t *base, const int64_t *nsamp,
+                                                     const int64_t *poff, const PathRec *rec, int64_t n_paths, fiesta_hip_path_result r) {
+  const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (p >= n_paths) return;
+  const long long n = nsamp[p];
+  double best = INFINITY;
+  long long bi = -1, fb = -1;
+  if (n > 0) {
+    for (int64_t k = poff[p]; k < poff[p + 1]; ++k) {  // in index order: a strictly smaller value wins, a tie keeps the earlier piece
+      const PathRec e = rec[k];
+      if (bi < 0 || e.v < best) best = e.v, bi = e.i;
+      if (fb < 0 && e.fb != LLONG_MAX) fb = e.fb;
+    }
+  }
+  const int64_t o0 = n > 0 ? rng[2 * p] : 0;
+  path_write(ev, r, p, n, best, bi, fb, w + 3 * o0, base + o0, n > 0 ? rng[2 * p + 1] - o0 : 0);
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------
+// Samples of a host batch, counted until they exceed `limit` (a segment that makes its path invalid counts as one).
+inline int64_t path_host_samples(const double *w, const int64_t *off, int64_t n_paths, double step, int64_t limit) {
+  int64_t total = 0;
+  for (int64_t p = 0; p < n_paths && total <= limit; ++p) {
+    if (off[p + 1] > off[p]) ++total;
+    for (int64_t i = off[p]; i + 1 < off[p + 1] && total <= limit; ++i) {
+      long long S = 1;
+      if (!path_segment_samples(w + 3 * i, w + 3 * i + 3, step, &S)) S = 1;
+      total += S;
+    }
+  }
+  return total;
+}
+// The whole call on the host, sample by sample (small batches: the evaluator reads the host brick cache).
+template <class Eval>
+void path_host(Eval &ev, const double *w, const int64_t *off, int64_t n_paths, double step, double margin, const fiesta_hip_path_result &r) {
+  std::vector<int64_t> base;
+  for (int64_t p = 0; p < n_paths; ++p) {
+    const int64_t o0 = off[p], nw = off[p + 1] - o0;
+    const double *pw = w + 3 * o0;
+    base.assign((size_t)std::max<int64_t>(nw, 1), 0);
+    long long n = 0;
+    bool bad = false;
+    for (int64_t j = 0; j < nw; ++j) {
+      base[j] = n;
+      long long S = 0;
+      if (!path_finite(pw + 3 * j) || (j + 1 < nw && !path_segment_samples(pw + 3 * j, pw + 3 * j + 3, step, &S))) bad = true;
+      n += S;
+    }
+    n = bad ? -1 : (nw > 0 ? n + 1 : 0);
+    double best = INFINITY;
+    long long bi = -1, fb = -1;
+    int64_t j = 0;
+    for (long long s = 0; s < n; ++s) {
+      j = path_find(base.data(), j, nw - 1, s);
+      double q[3];
+      path_sample(pw, base.data(), nw, j, s, q);
+      const double v = ev(q, nullptr);
+      if (bi < 0 || v < best) best = v, bi = s;
+      if (fb < 0 && v < margin) fb = s;
+    }
+    path_write(ev, r, p, n, best, bi, fb, pw, base.data(), nw);
+  }
+}
+
+// The device pipeline.  w / off / r are device pointers (the host variant has staged them); tmp is the map's grow-only scratch.
+// Every grid size follows from n_paths alone: nothing is read back.  checked: run k_path_check (offsets resident on the device).
+template <class Eval>
+void path_launch(hipStream_t st, DevBuf<unsigned char> &tmp, const Eval &ev, const double *w, int64_t n_wp, const int64_t *off,
+                 int64_t n_paths, double step, double margin, bool checked, const fiesta_hip_path_result &r) {
+  const long long max_pieces = std::max<int64_t>(1, kPathRecords / n_paths);
+  const int64_t nrec = n_paths * max_pieces;  // <= max(kPathRecords, n_paths)
+  const size_t b_nsamp = (size_t)n_wp * 8, b_rng = b_nsamp + (size_t)n_paths * 8, b_poff = b_rng + (size_t)n_paths * 16,
+               b_rec = b_poff + (size_t)(n_paths + 1) * 8, bytes = b_rec + (size_t)nrec * sizeof(PathRec);
+  tmp.ensure(bytes, st);
+  int64_t *base = (int64_t *)tmp.p, *nsamp = (int64_t *)(tmp.p + b_nsamp), *rng = (int64_t *)(tmp.p + b_rng), *poff = (int64_t *)(tmp.p + b_poff);
+  PathRec *rec = (PathRec *)(tmp.p + b_rec);
+  if (checked) hipLaunchKernelGGL(k_path_check, dim3(1), dim3(1024), 0, st, off, n_paths, n_wp, nsamp, rng);
+  hipLaunchKernelGGL(k_path_plan, dim3((unsigned)((n_paths + 3) / 4)), dim3(256), 0, st, w, off, n_paths, step, checked ? 1 : 0, base, nsamp,
+                     rng);
+  hipLaunchKernelGGL(k_path_pieces, dim3(1), dim3(1024), 0, st, (const int64_t *)nsamp, n_paths, max_pieces, poff);
+  hipLaunchKernelGGL(k_path_eval<Eval>, dim3(kPathEvalBlocks), dim3(256), 0, st, ev, w, (const int64_t *)rng, (const int64_t *)base,
+                     (const int64_t *)nsamp, (const int64_t *)poff, n_paths, max_pieces, margin, rec);
+  hipLaunchKernelGGL(k_path_finish<Eval>, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, st, ev, w, (const int64_t *)rng,
+                     (const int64_t *)base, (const int64_t *)nsamp, (const int64_t *)poff, (const PathRec *)rec, n_paths, r);
+  FIESTA_HIP_CHECK(hipGetLastError());
+}
+
+// Both variants of the call on a map's stream.  Host variant: the inputs are staged into `in`, the requested outputs come back
+// through `out`, then the stream is synchronised.  Device variant: only enqueued.
+template <class Eval>
+void path_clearance_run(hipStream_t st, DevBuf<unsigned char> &in, DevBuf<unsigned char> &tmp, DevBuf<unsigned char> &out, const Eval &ev,
+                        const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+                        const fiesta_hip_path_result &r, bool dev) {
+  if (dev) {
+    path_launch(st, tmp, ev, w, n_wp, off, n_paths, step, margin, true, r);
+    return;
+  }
+  const size_t bw = (size_t)n_wp * 3 * sizeof(double), bo = (size_t)(n_paths + 1) * sizeof(int64_t);
+  in.ensure(bw + bo, st);
+  if (bw) FIESTA_HIP_CHECK(hipMemcpyAsync(in.p, w, bw, hipMemcpyHostToDevice, st));
+  FIESTA_HIP_CHECK(hipMemcpyAsync(in.p + bw, off, bo, hipMemcpyHostToDevice, st));
+  const size_t n = (size_t)n_paths;
+  out.ensure(n * 13 * 8, st);  // the 7 fields: 13 words per path
+  double *o = (double *)out.p;
+  fiesta_hip_path_result d{};
+  if (r.min_dist) d.min_dist = o;
+  if (r.min_index) d.min_index = (int64_t *)(o + n);
+  if (r.min_pos) d.min_pos = o + 2 * n;
+  if (r.min_grad) d.min_grad = o + 5 * n;
+  if (r.first_below) d.first_below = (int64_t *)(o + 8 * n);
+  if (r.first_below_pos) d.first_below_pos = o + 9 * n;
+  if (r.n_samples) d.n_samples = (int64_t *)(o + 12 * n);
+  path_launch(st, tmp, ev, (const double *)in.p, n_wp, (const int64_t *)(in.p + bw), n_paths, step, margin, false, d);
+  auto back = [&](void *dst, const void *src, size_t words) {
+    if (dst) FIESTA_HIP_CHECK(hipMemcpyAsync(dst, src, words * 8, hipMemcpyDeviceToHost, st));
+  };
+  back(r.min_dist, d.min_dist, n);
+  back(r.min_index, d.min_index, n);
+  back(r.min_pos, d.min_pos, 3 * n);
+  back(r.min_grad, d.min_grad, 3 * n);
+  back(r.first_below, d.first_below, n);
+  back(r.first_below_pos, d.first_below_pos, 3 * n);
+  back(r.n_samples, d.n_samples, n);
+  FIESTA_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+}  // namespace
+}  // namespace fiesta

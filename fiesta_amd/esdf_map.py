@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Config, FiestaHipError, RaycastParams, Stats, check
+from ._lib import Config, FiestaHipError, PathResult, RaycastParams, Stats, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -35,6 +35,52 @@ def _d3(v):
 
 
 ENGINES = {"auto": 0, "rounds": 1, "bulk": 2, "levels": 3, "envelope": 4, "cells": 5, "masked": 6}
+
+# fiesta_hip_path_result, in struct order: (name, dtype, per-path shape)
+PATH_FIELDS = (("min_dist", np.float64, ()), ("min_index", np.int64, ()), ("min_pos", np.float64, (3,)),
+               ("min_grad", np.float64, (3,)), ("first_below", np.int64, ()), ("first_below_pos", np.float64, (3,)),
+               ("n_samples", np.int64, ()))
+PATH_MAX_RATIO = 2.0 ** 24   # a segment with L / step above this makes its path invalid
+
+
+def path_samples(waypoints, offsets, step):
+    """The sample rule of fiesta_hip_path_clearance (include/fiesta_hip.h) in numpy, bit for bit: for each segment a -> b of a
+    path d = b - a, L = sqrt(d0*d0 + d1*d1 + d2*d2), S = max(1, ceil(L / step)), samples a + d * (k / S) for k < S; then the
+    last waypoint itself.  Returns (positions, n_samples): the samples of every valid path, path after path, as an (N, 3) f64
+    array, and per path its count (0: empty, -1: invalid -- a non-finite waypoint or a segment with L / step > 2^24; an invalid
+    path contributes no positions).  Sample i of path p is positions[sum(max(n_samples[:p], 0)) + i]."""
+    w = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    step = float(step)
+    if len(off) < 1 or off[0] != 0 or off[-1] != len(w) or np.any(np.diff(off) < 0):
+        raise ValueError("offsets: n_paths + 1 non-decreasing entries from 0 to n_waypoints")
+    if not (np.isfinite(step) and step > 0):
+        raise ValueError("step must be finite and > 0")
+    n_paths, nw = len(off) - 1, np.diff(off)
+    path_of = np.repeat(np.arange(n_paths), nw)                      # the path of every waypoint
+    last = np.zeros(len(w), bool)
+    last[off[1:][nw > 0] - 1] = True                                 # the last waypoint of its path: no segment starts there
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.zeros_like(w)
+        d[:-1] = w[1:] - w[:-1]
+        L = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
+        q = L / step
+        seg_ok = last | (q <= PATH_MAX_RATIO)
+        S = np.where(last, 1, np.maximum(1, np.ceil(np.where(seg_ok, q, 0.0)))).astype(np.int64)
+    bad_wp = ~np.all(np.isfinite(w), axis=1) | ~seg_ok
+    bad = np.zeros(n_paths, bool)
+    np.logical_or.at(bad, path_of, bad_wp)
+    S[bad[path_of]] = 0                                              # an invalid path has no samples
+    n_samples = np.zeros(n_paths, np.int64)
+    np.add.at(n_samples, path_of, S)
+    n_samples[bad] = -1
+    idx = np.repeat(np.arange(len(w)), S)                            # the waypoint each sample starts from, in sample order
+    k = np.arange(len(idx)) - np.repeat(np.cumsum(S) - S, S)
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = k.astype(np.float64) / S[idx].astype(np.float64)
+        pos = w[idx] + d[idx] * t[:, None]
+    pos = np.where(last[idx][:, None], w[idx], pos)                  # the final sample: the last waypoint itself
+    return np.ascontiguousarray(pos), n_samples
 
 
 class ESDFMap:
@@ -259,6 +305,30 @@ class ESDFMap:
         """device-resident batch (n x 3 f64 positions, n f64 distances, n x 3 f64 gradients or 0): the planner-side fast path"""
         check(self._lib.fiesta_hip_get_dist_grad_dev(self._h, C.c_void_p(pos_dev_ptr), n, C.c_void_p(dist_dev_ptr),
                                                      C.c_void_p(grad_dev_ptr) if grad_dev_ptr else None))
+
+    def PathClearance(self, waypoints, offsets, step, margin=0.0) -> dict:
+        """fiesta_hip_path_clearance: per path (CSR `offsets` over `waypoints`) the minimum of GetDistWithGradTrilinear over its
+        samples (path_samples), its first index, position and gradient, and the first sample below `margin` -- a dict of numpy
+        arrays named as the fields of fiesta_hip_path_result"""
+        w = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if len(off) < 1:
+            raise ValueError("offsets needs n_paths + 1 entries")
+        n = len(off) - 1
+        out = {name: np.empty((n,) + shape, dtype) for name, dtype, shape in PATH_FIELDS}
+        res = PathResult(*[out[name].ctypes.data for name, _, _ in PATH_FIELDS])
+        check(self._lib.fiesta_hip_path_clearance(self._h, _p(w), len(w), _p(off), n, float(step), float(margin), C.byref(res)))
+        return out
+
+    def PathClearanceDevice(self, waypoints_dev_ptr: int, n_waypoints: int, offsets_dev_ptr: int, n_paths: int, step, margin=0.0,
+                            out=None):
+        """fiesta_hip_path_clearance_dev: inputs and outputs resident on the device (n_waypoints x 3 f64, n_paths + 1 int64;
+        `out` maps field names of fiesta_hip_path_result to device pointers, missing fields are not written); only enqueued"""
+        out = out or {}
+        res = PathResult(*[int(out.get(name, 0)) or None for name, _, _ in PATH_FIELDS])
+        check(self._lib.fiesta_hip_path_clearance_dev(self._h, C.c_void_p(waypoints_dev_ptr), int(n_waypoints),
+                                                      C.c_void_p(offsets_dev_ptr), int(n_paths), float(step), float(margin),
+                                                      C.byref(res)))
 
     @property
     def host_cache_fetches(self) -> int:

@@ -136,6 +136,65 @@ class ESDFMap {
     ck(fiesta_hip_get_dist_grad(h_, pos, n, dist, grad));
   }
 
+  // Path clearance (fiesta_hip_path_clearance; no reference counterpart -- its callers loop over GetDistWithGradTrilinear).
+  // The minimum of GetDistWithGradTrilinear over the samples of the polyline `waypoints` (spacing `step`, the sample rule of
+  // include/fiesta_hip.h: PathSample below), and optionally the gradient at the first minimal sample and the first sample whose
+  // value is < margin (-1 / NaN position if none).  +inf for no waypoints, NaN for an invalid path (non-finite waypoint, a
+  // segment longer than 2^24 steps).  A path of at most 256 samples is answered from the host brick cache.
+  double GetMinDistanceAlongPath(const std::vector<Eigen::Vector3d> &waypoints, double step, double margin,
+                                 Eigen::Vector3d *grad_at_min = nullptr, int64_t *first_below = nullptr,
+                                 Eigen::Vector3d *first_below_pos = nullptr) {
+    std::vector<double> w(3 * waypoints.size() + 3);  // (one spare triple: never a null pointer)
+    for (size_t i = 0; i < waypoints.size(); ++i)
+      for (int c = 0; c < 3; ++c) w[3 * i + c] = waypoints[i](c);
+    const int64_t off[2] = {0, (int64_t)waypoints.size()};
+    double md = 0, g[3] = {0, 0, 0}, fp[3] = {0, 0, 0};
+    int64_t fb = -1;
+    const fiesta_hip_path_result r{&md, nullptr, nullptr, g, &fb, fp, nullptr};
+    ck(fiesta_hip_path_clearance(h_, w.data(), off[1], off, 1, step, margin, &r));
+    if (grad_at_min) *grad_at_min = Eigen::Vector3d(g[0], g[1], g[2]);
+    if (first_below) *first_below = fb;
+    if (first_below_pos) *first_below_pos = Eigen::Vector3d(fp[0], fp[1], fp[2]);
+    return md;
+  }
+  // The batch form: n_paths polylines in CSR form (path p = waypoints[offsets[p] .. offsets[p+1]-1], n_waypoints x 3), one
+  // entry per path in every non-null array of `result` (fiesta_hip_path_result: min_dist, min_index, min_pos, min_grad,
+  // first_below, first_below_pos, n_samples).
+  void PathClearanceBatch(const double *waypoints, int64_t n_waypoints, const int64_t *offsets, int64_t n_paths, double step,
+                          double margin, const fiesta_hip_path_result &result) {
+    ck(fiesta_hip_path_clearance(h_, waypoints, n_waypoints, offsets, n_paths, step, margin, &result));
+  }
+  // Sample `index` of the polyline by the header's rule, on the host (bit for bit what the library evaluates there); NaN if the
+  // path has no such sample or is invalid.  Header-only, so compiled with the includer's flags: the exactness include/fiesta_hip.h
+  // promises holds only without floating-point contraction -- build the including file with -ffp-contract=off.  g++'s default
+  // for C++ is "fast": on an FMA target (-march=native, -mfma, ...) it may fuse d0*d0 + d1*d1 or a + d*t, which can change S by
+  // one and move every later sample.
+  static Eigen::Vector3d PathSample(const std::vector<Eigen::Vector3d> &waypoints, double step, int64_t index) {
+    const double nan = std::nan("");
+    Eigen::Vector3d out(nan, nan, nan);
+    if (waypoints.empty() || index < 0) return out;
+    for (size_t i = 0; i < waypoints.size(); ++i) {
+      const Eigen::Vector3d &a = waypoints[i];
+      if (!std::isfinite(a(0)) || !std::isfinite(a(1)) || !std::isfinite(a(2))) return Eigen::Vector3d(nan, nan, nan);
+      if (i + 1 == waypoints.size()) {
+        if (index == 0) out = a;  // the final sample: the last waypoint itself
+        break;
+      }
+      const Eigen::Vector3d &b = waypoints[i + 1];
+      const double d0 = b(0) - a(0), d1 = b(1) - a(1), d2 = b(2) - a(2);
+      const double L = std::sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+      const double q = L / step;
+      if (!(q <= 16777216.0)) return Eigen::Vector3d(nan, nan, nan);  // L / step > 2^24 (or NaN): an invalid path
+      const int64_t S = std::max<int64_t>(1, (int64_t)std::ceil(q));
+      if (index >= 0 && index < S) {
+        const double t = (double)index / (double)S;
+        out = Eigen::Vector3d(a(0) + d0 * t, a(1) + d1 * t, a(2) + d2 * t);
+      }
+      index -= S;
+    }
+    return out;
+  }
+
   // Local Range (src/ESDFMap.cpp:792-824)
   void SetUpdateRange(Eigen::Vector3d min_pos, Eigen::Vector3d max_pos, bool new_vec = true) {
     Flush();  // pending observations were made under the old window

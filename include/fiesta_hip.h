@@ -129,6 +129,7 @@ typedef struct fiesta_hip_stats {
 #define FIESTA_HIP_NOTE_ENGINE_PINNED 0x4000      /* update_engine is not "auto" */
 
 const char *fiesta_hip_last_error(void);
+/* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev]. */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -285,6 +286,66 @@ int fiesta_hip_get_dist_grad_dev(fiesta_hip_map *m, const double *pos_dev, int64
  * with the same arithmetic, bit for bit.  UpdateOccupancy, UpdateESDF, a restore or load and the ghost exchange of a
  * shard invalidate the cache.  *fetches = bricks fetched so far (a statistic for tests and the benchmark). */
 int fiesta_hip_host_cache_fetches(fiesta_hip_map *m, int64_t *fetches);
+
+/* ---- path clearance, batched: minimum distance and first contact along polylines ----
+ * No reference counterpart: the reference's callers loop over GetDistWithGradTrilinear (src/ESDFMap.cpp:481-540) sample by
+ * sample.  Since fiesta_hip_version() 101.
+ * Input: n_paths polylines over n_waypoints waypoints (n_waypoints x 3 double, metres) in CSR form -- path p is
+ * waypoints[offsets[p] .. offsets[p+1]-1]; offsets holds n_paths + 1 int64 entries, offsets[0] = 0, non-decreasing,
+ * offsets[n_paths] = n_waypoints.  step: the sample spacing in metres, finite and > 0.  margin: metres, not NaN (+-inf allowed).
+ *
+ * The sample rule -- exact in f64, identical on the device, on the host, in fiesta_amd.path_samples (numpy) and in
+ * fiesta::ESDFMap::PathSample (C++); the library is built with -ffp-contract=off, numpy does not contract either:
+ *   for each segment a = w[i], b = w[i+1] of a path, in order:
+ *     d = b - a, per component;  L = sqrt(d0*d0 + d1*d1 + d2*d2), evaluated left to right;  S = max(1, (int64)ceil(L / step));
+ *     the samples are a[c] + d[c] * ((double)k / (double)S) for k = 0 .. S-1 (a zero-length segment: one sample, at a);
+ *   after the last segment one final sample: the last waypoint itself (a path of one waypoint has exactly that sample).
+ *   Sample indices run in this order from 0 to n_samples - 1.
+ * The value of a sample is bit for bit what fiesta_hip_get_dist_grad returns at that position on the same map (dense maps, a
+ * single shard, hash-block maps): -1 outside a dense map (PosInMap), unobserved corners read +10000.
+ *
+ * Outputs, one per path; every pointer of the result is nullable:
+ *   min_dist             the minimum sample value
+ *   min_index            the smallest sample index that attains it
+ *   min_pos (x3)         that sample's position by the rule
+ *   min_grad (x3)        fiesta_hip_get_dist_grad's gradient at that sample, bit for bit
+ *   first_below          the smallest sample index whose value is < margin (strictly), -1 if there is none.  A path that leaves a
+ *                        dense map "contacts" where it leaves (value -1): what the point query tells a planner there too.  A
+ *                        sphere robot of radius r asks with margin = r.
+ *   first_below_pos (x3) that sample's position, NaN if there is none
+ *   n_samples            the path's sample count
+ * Special paths:
+ *   empty (offsets[p] == offsets[p+1]): n_samples 0, min_dist +inf, indices -1, positions NaN, gradient 0;
+ *   invalid -- a non-finite waypoint, a segment with L / step > 2^24, or (device variant only) offsets out of order or out of
+ *   range: n_samples -1, min_dist NaN, indices -1, positions NaN, gradient 0.  The other paths are unaffected.  On the device
+ *   "out of order or out of range" means offsets[p+1] < offsets[p], a range outside [0, n_waypoints], or offsets[p] below an
+ *   earlier entry that lies inside [0, n_waypoints] (valid paths must not overlap).  An entry outside [0, n_waypoints] costs
+ *   only the two paths that share it; swapped entries offsets[q], offsets[q+1] flag paths q and q+1; but an entry inside the
+ *   range that is too LARGE (say offsets[q] = n_waypoints in the middle of the batch) flags every later path that starts below
+ *   it: which of two in-range entries is the wrong one cannot be told, and overlapping paths are never evaluated.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): step not finite or <= 0, margin NaN, the
+ * host variant's offsets breaking the CSR rules, a null waypoints / offsets / result pointer.  n_paths = 0 does nothing.
+ * Results depend neither on the launch shape nor on the scheduling of work-groups (no atomics in the min or its index).
+ * fiesta_hip_path_clearance      host pointers; stages the inputs, runs, synchronises (like fiesta_hip_get_dist_grad).  A batch
+ *                                of at most 256 samples is answered on the host from the brick cache above, same arithmetic.
+ * fiesta_hip_path_clearance_dev  every array (inputs and those of *result -- the struct itself is a host object) is a device
+ *                                pointer; only enqueued on the map's stream, no host round trip (like _get_dist_grad_dev; a
+ *                                hash-block map whose page set changed since its last query rebuilds its page table first, as
+ *                                every query does). */
+typedef struct fiesta_hip_path_result {
+  double *min_dist;
+  int64_t *min_index;
+  double *min_pos;
+  double *min_grad;
+  int64_t *first_below;
+  double *first_below_pos;
+  int64_t *n_samples;
+} fiesta_hip_path_result;
+int fiesta_hip_path_clearance(fiesta_hip_map *m, const double *waypoints, int64_t n_waypoints, const int64_t *offsets,
+                              int64_t n_paths, double step, double margin, const fiesta_hip_path_result *result);
+int fiesta_hip_path_clearance_dev(fiesta_hip_map *m, const double *waypoints_dev, int64_t n_waypoints,
+                                  const int64_t *offsets_dev, int64_t n_paths, double step, double margin,
+                                  const fiesta_hip_path_result *result);
 
 /* ---- whole-field access (tests, visualisation, checkpoints) ----
  * Dense dump in the reference's linear order; each output is nullable.
