@@ -73,6 +73,12 @@ class PathResult(C.Structure):
                 ("first_below", C.c_void_p), ("first_below_pos", C.c_void_p), ("n_samples", C.c_void_p)]
 
 
+class PathCostResult(C.Structure):
+    """fiesta_hip_path_cost_result: one array per output of fiesta_hip_path_cost, every pointer nullable"""
+    _fields_ = [("cost", C.c_void_p), ("grad", C.c_void_p), ("length", C.c_void_p), ("n_below", C.c_void_p),
+                ("n_samples", C.c_void_p)]
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/fiesta_hip.h declares (used by the CPU export test)."""
     text = open(header_path).read()
@@ -166,6 +172,8 @@ def load():
         "fiesta_hip_host_cache_fetches": (C.c_int, [vp, vp]),
         "fiesta_hip_path_clearance": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
         "fiesta_hip_path_clearance_dev": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
+        "fiesta_hip_path_cost": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
+        "fiesta_hip_path_cost_dev": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
         "fiesta_hip_get_occupancy_vox": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_get_occupancy_pos": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_download_field": (C.c_int, [vp, vp, vp, vp, vp]),

@@ -51,16 +51,17 @@ DenseMap &dense(fiesta_hip_map *m, const char *what) {
   if (!m->dense) throw Error(FIESTA_HIP_ERR_INVALID, std::string(what) + ": only available on array-mode maps");
   return *m->dense;
 }
-// the whole-call errors of fiesta_hip_path_clearance[_dev] (include/fiesta_hip.h); host_offsets: the CSR rules as well
+// the whole-call errors shared by fiesta_hip_path_clearance[_dev] and fiesta_hip_path_cost[_dev] (include/fiesta_hip.h; r: the
+// call's result struct); host_offsets: the CSR rules as well
 void path_args(fiesta_hip_map *m, const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-               const fiesta_hip_path_result *r, bool host_offsets) {
+               const void *r, bool host_offsets) {
   need(m && w && off && r, "null argument");
   need(n_wp >= 0 && n_paths >= 0, "negative count");
-  need(std::isfinite(step) && step > 0, "path_clearance: step must be finite and > 0");
-  need(!std::isnan(margin), "path_clearance: margin is NaN");
+  need(std::isfinite(step) && step > 0, "path query: step must be finite and > 0");
+  need(!std::isnan(margin), "path query: margin is NaN");
   if (!host_offsets) return;
-  need(off[0] == 0 && off[n_paths] == n_wp, "path_clearance: offsets[0] must be 0 and offsets[n_paths] = n_waypoints");
-  for (int64_t p = 0; p < n_paths; ++p) need(off[p] <= off[p + 1], "path_clearance: offsets must be non-decreasing");
+  need(off[0] == 0 && off[n_paths] == n_wp, "path query: offsets[0] must be 0 and offsets[n_paths] = n_waypoints");
+  for (int64_t p = 0; p < n_paths; ++p) need(off[p] <= off[p + 1], "path query: offsets must be non-decreasing");
 }
 }  // namespace
 
@@ -397,6 +398,28 @@ int fiesta_hip_path_clearance_dev(fiesta_hip_map *m, const double *w_dev, int64_
       m->dense->path_clearance(w_dev, n_wp, off_dev, n_paths, step, margin, *r, true);
     else
       m->hash->path_clearance(w_dev, n_wp, off_dev, n_paths, step, margin, *r, true);
+  });
+}
+int fiesta_hip_path_cost(fiesta_hip_map *m, const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+                         const fiesta_hip_path_cost_result *r) {
+  return guarded([&] {
+    path_args(m, w, n_wp, off, n_paths, step, margin, r, true);
+    need(std::isfinite(margin), "path_cost: margin must be finite");
+    if (m->dense)
+      m->dense->path_cost(w, n_wp, off, n_paths, step, margin, *r, false);
+    else
+      m->hash->path_cost(w, n_wp, off, n_paths, step, margin, *r, false);
+  });
+}
+int fiesta_hip_path_cost_dev(fiesta_hip_map *m, const double *w_dev, int64_t n_wp, const int64_t *off_dev, int64_t n_paths, double step,
+                             double margin, const fiesta_hip_path_cost_result *r) {
+  return guarded([&] {
+    path_args(m, w_dev, n_wp, off_dev, n_paths, step, margin, r, false);
+    need(std::isfinite(margin), "path_cost: margin must be finite");
+    if (m->dense)
+      m->dense->path_cost(w_dev, n_wp, off_dev, n_paths, step, margin, *r, true);
+    else
+      m->hash->path_cost(w_dev, n_wp, off_dev, n_paths, step, margin, *r, true);
   });
 }
 int fiesta_hip_host_cache_fetches(fiesta_hip_map *m, int64_t *fetches) {

@@ -28,6 +28,7 @@
 #include "nn_kernels.hpp"
 #include "mask_kernels.hpp"
 #include "level_kernels.hpp"
+#include "path_cost_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
@@ -2520,6 +2521,19 @@ void DenseMap::path_clearance(const double *w, int64_t n_wp, const int64_t *off,
   use_device();
   path_clearance_run(stream_, path_in_, path_tmp_, path_out_, DensePathEval{g_, (const vox_t *)coc_}, w, n_wp, off, n_paths, step,
                      margin, r, dev);
+}
+void DenseMap::path_cost(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+                         const fiesta_hip_path_cost_result &r, bool dev) {
+  if (n_paths <= 0) return;
+  if (!dev && path_host_samples(w, off, n_paths, step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
+    HostWords wd{this};
+    auto ev = [&](const double *p, double *grad) { return query_trilinear(g_, wd, p, grad); };
+    path_cost_host(ev, w, n_wp, off, n_paths, step, margin, r);
+    return;
+  }
+  use_device();
+  path_cost_run(stream_, path_in_, path_tmp_, path_out_, DensePathEval{g_, (const vox_t *)coc_}, w, n_wp, off, n_paths, step, margin, r,
+                dev);
 }
 void DenseMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n <= 0) return;

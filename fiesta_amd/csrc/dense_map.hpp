@@ -145,6 +145,9 @@ class DenseMap {
   // fiesta_hip_path_clearance[_dev] (path_kernels.hpp); arguments checked by the caller
   void path_clearance(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
                       const fiesta_hip_path_result &r, bool dev);
+  // fiesta_hip_path_cost[_dev] (path_cost_kernels.hpp); arguments checked by the caller
+  void path_cost(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+                 const fiesta_hip_path_cost_result &r, bool dev);
   int64_t host_brick_fetches() const;  // bricks fetched for scalar queries so far (tests, bench)
 
   void download_field(int32_t *d2, int32_t *coc, uint8_t *occ, double *logodds);

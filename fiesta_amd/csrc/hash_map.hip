@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "level_kernels.hpp"
+#include "path_cost_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
@@ -1459,6 +1460,19 @@ void HashMap::path_clearance(const double *w, int64_t n_wp, const int64_t *off, 
   use_device();
   path_clearance_run(stream_, path_in_, path_tmp_, path_out_, HashPathEval{g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p}, w,
                      n_wp, off, n_paths, step, margin, r, dev);
+}
+void HashMap::path_cost(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+                        const fiesta_hip_path_cost_result &r, bool dev) {
+  if (n_paths <= 0) return;
+  if (!dev && path_host_samples(w, off, n_paths, step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
+    auto corner = [&](int vx, int vy, int vz) { return host_distance(vx, vy, vz); };
+    auto ev = [&](const double *p, double *grad) { return h_trilinear(g_, corner, p, grad); };
+    path_cost_host(ev, w, n_wp, off, n_paths, step, margin, r);
+    return;
+  }
+  use_device();
+  path_cost_run(stream_, path_in_, path_tmp_, path_out_, HashPathEval{g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p}, w, n_wp,
+                off, n_paths, step, margin, r, dev);
 }
 void HashMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n > 0 && n <= kHostQueries) {

@@ -81,6 +81,9 @@ class HashMap {
   // fiesta_hip_path_clearance[_dev] (path_kernels.hpp); arguments checked by the caller
   void path_clearance(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
                       const fiesta_hip_path_result &r, bool dev);
+  // fiesta_hip_path_cost[_dev] (path_cost_kernels.hpp); arguments checked by the caller
+  void path_cost(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
+                 const fiesta_hip_path_cost_result &r, bool dev);
   // every voxel of every allocated page, page order: vox (map voxel coordinates), d2, coc, occ; returns the count
   int64_t download(int32_t *vox, int32_t *d2, int32_t *coc, uint8_t *occ);
   void download_counts(int32_t *num_hit, int32_t *num_miss);  // same order as download()

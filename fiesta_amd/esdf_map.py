@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Config, FiestaHipError, PathResult, RaycastParams, Stats, check
+from ._lib import Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, Stats, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -81,6 +81,94 @@ def path_samples(waypoints, offsets, step):
         pos = w[idx] + d[idx] * t[:, None]
     pos = np.where(last[idx][:, None], w[idx], pos)                  # the final sample: the last waypoint itself
     return np.ascontiguousarray(pos), n_samples
+
+
+# fiesta_hip_path_cost_result, in struct order: (name, dtype, one row per "path" or per "waypoint", row shape)
+PATH_COST_FIELDS = (("cost", np.float64, "path", ()), ("grad", np.float64, "waypoint", (3,)), ("length", np.float64, "path", ()),
+                    ("n_below", np.int64, "path", ()), ("n_samples", np.int64, "path", ()))
+
+
+def path_cost_model(query, waypoints, offsets, step, margin):
+    """The definition of fiesta_hip_path_cost (include/fiesta_hip.h) in numpy over path_samples: every per-sample and per-segment
+    TERM in the header's operation order (bit for bit what the library computes from the same (d, grad)), the sums over a segment's
+    interior samples in numpy's order.  `query(pos) -> (d, grad)` answers an (N, 3) batch: a map's GetDistWithGradTrilinear, or any
+    callable.  Returns a dict: the five outputs (cost, grad, length, n_below, n_samples) and, for the tolerance of a comparison with
+    another order of summation, per float output component the number of summed terms and the sum of their absolute values on the
+    output's own scale: cost_n / cost_abs and length_n / length_abs per path, grad_n per waypoint, grad_abs per waypoint and
+    component.  Two orders of summation differ by at most (n + 16) * 2^-52 * abs."""
+    w = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    step, margin = float(step), float(margin)
+    if not np.isfinite(margin):
+        raise ValueError("margin must be finite")
+    pos, ns = path_samples(w, off, step)
+    if len(pos):
+        d, g = query(pos)
+        d, g = np.asarray(d, np.float64).reshape(-1), np.asarray(g, np.float64).reshape(-1, 3)
+    else:
+        d, g = np.zeros(0), np.zeros((0, 3))
+    n_paths = len(ns)
+    below = d < margin
+    with np.errstate(invalid="ignore", over="ignore"):
+        e = np.where(below, margin - d, 0.0)
+        phi_all = e * e
+        gam_all = np.where(below[:, None], (-2.0 * e)[:, None] * g, 0.0)
+    out = {"cost": np.zeros(n_paths), "grad": np.zeros((len(w), 3)), "length": np.zeros(n_paths),
+           "n_below": np.zeros(n_paths, np.int64), "n_samples": ns.copy(),
+           "cost_n": np.zeros(n_paths, np.int64), "cost_abs": np.zeros(n_paths), "length_n": np.zeros(n_paths, np.int64),
+           "length_abs": np.zeros(n_paths), "grad_n": np.zeros(len(w), np.int64), "grad_abs": np.zeros((len(w), 3))}
+    at = 0
+    for p in range(n_paths):
+        n = int(ns[p])
+        if n < 0:
+            out["cost"][p] = out["length"][p] = np.nan
+            out["n_below"][p] = -1
+            continue
+        if n == 0:
+            continue
+        o0, o1 = int(off[p]), int(off[p + 1])
+        phi, gam = phi_all[at:at + n], gam_all[at:at + n]
+        out["n_below"][p] = int(np.count_nonzero(below[at:at + n]))
+        at += n
+        if o1 - o0 < 2:
+            continue
+        a = w[o0:o1]
+        dd = a[1:] - a[:-1]
+        L = np.sqrt(dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1] + dd[:, 2] * dd[:, 2])
+        S = np.maximum(1, np.ceil(L / step)).astype(np.int64)
+        first = np.concatenate([[0], np.cumsum(S)])           # sample 0 of every segment, then the final sample: the waypoints
+        assert first[-1] + 1 == n
+        sidx = np.repeat(np.arange(len(S)), S)
+        k = np.arange(n - 1) - first[sidx]
+        Sd = S.astype(np.float64)
+        t = k.astype(np.float64) / Sd[sidx]
+        r = 1.0 - t
+        inner = (k > 0)[:, None]
+        terms = np.where(inner, np.concatenate([phi[:-1, None], r[:, None] * gam[:-1], t[:, None] * gam[:-1]], 1), 0.0)
+        sums = np.add.reduceat(terms, first[:-1], axis=0)       # P, A[3], B[3] per segment
+        asums = np.add.reduceat(np.abs(terms), first[:-1], axis=0)
+        ra_phi, rb_phi, ra_gam, rb_gam = phi[first[:-1]], phi[first[1:]], gam[first[:-1]], gam[first[1:]]
+        ok = L > 0
+        with np.errstate(invalid="ignore", divide="ignore"):
+            h = L / Sd
+            Q = (ra_phi * 0.5 + sums[:, 0]) + rb_phi * 0.5
+            qs = Q / Sd
+            u = dd / L[:, None]
+            hq = np.where(ok, h * Q, 0.0)
+            N = np.where(ok[:, None], h[:, None] * (ra_gam * 0.5 + sums[:, 1:4]) - qs[:, None] * u, 0.0)
+            E = np.where(ok[:, None], h[:, None] * (sums[:, 4:7] + rb_gam * 0.5) + qs[:, None] * u, 0.0)
+            absN = np.where(ok[:, None], h[:, None] * (np.abs(ra_gam) * 0.5 + asums[:, 1:4]) + np.abs(qs[:, None] * u), 0.0)
+            absE = np.where(ok[:, None], h[:, None] * (asums[:, 4:7] + np.abs(rb_gam) * 0.5) + np.abs(qs[:, None] * u), 0.0)
+            absQ = np.where(ok, h * (np.abs(ra_phi) * 0.5 + asums[:, 0] + np.abs(rb_phi) * 0.5), 0.0)
+        zero = np.zeros((1, 3))
+        out["cost"][p] = np.cumsum(hq)[-1]                      # (cumsum adds in segment order)
+        out["length"][p] = np.cumsum(L)[-1]
+        out["grad"][o0:o1] = np.concatenate([N, zero]) + np.concatenate([zero, E])
+        out["cost_n"][p], out["cost_abs"][p] = int((S + 1).sum()), absQ.sum()
+        out["length_n"][p], out["length_abs"][p] = len(L), L.sum()
+        out["grad_abs"][o0:o1] = np.concatenate([absN, zero]) + np.concatenate([zero, absE])
+        out["grad_n"][o0:o1] = np.concatenate([S + 2, [0]]) + np.concatenate([[0], S + 2])
+    return out
 
 
 class ESDFMap:
@@ -329,6 +417,28 @@ class ESDFMap:
         check(self._lib.fiesta_hip_path_clearance_dev(self._h, C.c_void_p(waypoints_dev_ptr), int(n_waypoints),
                                                       C.c_void_p(offsets_dev_ptr), int(n_paths), float(step), float(margin),
                                                       C.byref(res)))
+
+    def PathCost(self, waypoints, offsets, step, margin) -> dict:
+        """fiesta_hip_path_cost: per path (CSR `offsets` over `waypoints`) the penalty (margin - d)^2 of GetDistWithGradTrilinear
+        below `margin`, integrated along the polyline by the trapezoid rule over path_samples, and its derivative with respect to
+        every waypoint -- a dict of numpy arrays named as the fields of fiesta_hip_path_cost_result (grad: one row per waypoint)"""
+        w = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if len(off) < 1:
+            raise ValueError("offsets needs n_paths + 1 entries")
+        n = len(off) - 1
+        out = {name: np.empty((n if per == "path" else len(w),) + shape, dtype) for name, dtype, per, shape in PATH_COST_FIELDS}
+        res = PathCostResult(*[out[name].ctypes.data for name, _, _, _ in PATH_COST_FIELDS])
+        check(self._lib.fiesta_hip_path_cost(self._h, _p(w), len(w), _p(off), n, float(step), float(margin), C.byref(res)))
+        return out
+
+    def PathCostDevice(self, waypoints_dev_ptr: int, n_waypoints: int, offsets_dev_ptr: int, n_paths: int, step, margin, out=None):
+        """fiesta_hip_path_cost_dev: inputs and outputs resident on the device (`out` maps field names of
+        fiesta_hip_path_cost_result to device pointers, missing fields are not written); only enqueued on the map's stream"""
+        out = out or {}
+        res = PathCostResult(*[int(out.get(name, 0)) or None for name, _, _, _ in PATH_COST_FIELDS])
+        check(self._lib.fiesta_hip_path_cost_dev(self._h, C.c_void_p(waypoints_dev_ptr), int(n_waypoints), C.c_void_p(offsets_dev_ptr),
+                                                 int(n_paths), float(step), float(margin), C.byref(res)))
 
     @property
     def host_cache_fetches(self) -> int:

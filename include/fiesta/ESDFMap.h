@@ -164,6 +164,34 @@ class ESDFMap {
                           double margin, const fiesta_hip_path_result &result) {
     ck(fiesta_hip_path_clearance(h_, waypoints, n_waypoints, offsets, n_paths, step, margin, &result));
   }
+  // Path cost (fiesta_hip_path_cost; no reference counterpart): the penalty (margin - d)^2 of GetDistWithGradTrilinear below
+  // `margin`, integrated along the polyline `waypoints` by the trapezoid rule over the samples of PathSample, and optionally its
+  // derivative with respect to every waypoint (grad->size() == waypoints.size(): the descent direction of a trajectory
+  // optimiser) and the number of samples below the margin.  0 for fewer than two waypoints, NaN for an invalid path.  A path of
+  // at most 256 samples is answered from the host brick cache.  The formulas: include/fiesta_hip.h.
+  double GetPathCost(const std::vector<Eigen::Vector3d> &waypoints, double step, double margin,
+                     std::vector<Eigen::Vector3d> *grad = nullptr, int64_t *n_below = nullptr) {
+    std::vector<double> w(3 * waypoints.size() + 3), g(3 * waypoints.size() + 3);  // (one spare triple: never a null pointer)
+    for (size_t i = 0; i < waypoints.size(); ++i)
+      for (int c = 0; c < 3; ++c) w[3 * i + c] = waypoints[i](c);
+    const int64_t off[2] = {0, (int64_t)waypoints.size()};
+    double cost = 0;
+    int64_t nb = 0;
+    const fiesta_hip_path_cost_result r{&cost, g.data(), nullptr, &nb, nullptr};
+    ck(fiesta_hip_path_cost(h_, w.data(), off[1], off, 1, step, margin, &r));
+    if (grad) {
+      grad->resize(waypoints.size());
+      for (size_t i = 0; i < waypoints.size(); ++i) (*grad)[i] = Eigen::Vector3d(g[3 * i], g[3 * i + 1], g[3 * i + 2]);
+    }
+    if (n_below) *n_below = nb;
+    return cost;
+  }
+  // The batch form: CSR polylines as PathClearanceBatch; `result` (fiesta_hip_path_cost_result) holds one entry per path in cost,
+  // length, n_below, n_samples and one row per WAYPOINT in grad; every pointer is nullable.
+  void PathCostBatch(const double *waypoints, int64_t n_waypoints, const int64_t *offsets, int64_t n_paths, double step, double margin,
+                     const fiesta_hip_path_cost_result &result) {
+    ck(fiesta_hip_path_cost(h_, waypoints, n_waypoints, offsets, n_paths, step, margin, &result));
+  }
   // Sample `index` of the polyline by the header's rule, on the host (bit for bit what the library evaluates there); NaN if the
   // path has no such sample or is invalid.  Header-only, so compiled with the includer's flags: the exactness include/fiesta_hip.h
   // promises holds only without floating-point contraction -- build the including file with -ffp-contract=off.  g++'s default

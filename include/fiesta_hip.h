@@ -129,7 +129,8 @@ typedef struct fiesta_hip_stats {
 #define FIESTA_HIP_NOTE_ENGINE_PINNED 0x4000      /* update_engine is not "auto" */
 
 const char *fiesta_hip_last_error(void);
-/* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev]. */
+/* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev].
+ * fiesta_hip_path_cost[_dev] came later without a new number: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -346,6 +347,61 @@ int fiesta_hip_path_clearance(fiesta_hip_map *m, const double *waypoints, int64_
 int fiesta_hip_path_clearance_dev(fiesta_hip_map *m, const double *waypoints_dev, int64_t n_waypoints,
                                   const int64_t *offsets_dev, int64_t n_paths, double step, double margin,
                                   const fiesta_hip_path_result *result);
+
+/* ---- path cost, batched: a smooth obstacle cost per polyline and its derivative with respect to every waypoint ----
+ * What a trajectory optimiser needs per iteration (path clearance above serves the search half of a planner; a minimum and its
+ * gradient at one sample is no descent direction).  No reference counterpart.  fiesta_hip_version() is still 101: detect these
+ * two calls by symbol lookup.
+ * Input: as path clearance -- CSR polylines, step, margin (here margin must be FINITE).  The samples are exactly path
+ * clearance's (same rule, same indices), and a sample's value d and gradient g are fiesta_hip_get_dist_grad's bit for bit
+ * (dense maps, a single shard, hash-block maps).  A sample outside a dense map has value -1 and gradient 0, the point query's
+ * answer: it is penalised by phi(-1), pulls nowhere, and n_below counts it.
+ *
+ * Per sample, in f64, each operation rounded once (the library is built with -ffp-contract=off), in exactly this order:
+ *   if d < margin:  e = margin - d;  phi = e * e;  psi = -2.0 * e;  gamma[c] = psi * g[c]      else phi = 0, gamma = 0.
+ * Per segment j of a path (a = w[j], b = w[j+1]; d[c], L, S as in the sample rule; Sd = (double)S):
+ *   the two end samples are the waypoints themselves: sample 0 of segment j is w[j]; w[j+1] is sample 0 of segment j+1 or the
+ *   path's final sample.  Interior samples k = 1 .. S-1:  t = (double)k / Sd;  r = 1.0 - t;  their seven terms are
+ *   phi,  r * gamma[c],  t * gamma[c];  P = sum phi, A[c] = sum r * gamma[c], B[c] = sum t * gamma[c] over the interior samples.
+ *   h = L / Sd;   Q = (phi(w[j]) * 0.5 + P) + phi(w[j+1]) * 0.5;   qs = Q / Sd;   u[c] = d[c] / L;
+ *   cost term           h * Q                                             (the trapezoid rule for the integral of phi along j)
+ *   to the start, N[c]  h * (gamma(w[j])[c] * 0.5 + A[c]) - qs * u[c]
+ *   to the end,   E[c]  h * (B[c] + gamma(w[j+1])[c] * 0.5) + qs * u[c]
+ *   A segment with L = 0 contributes nothing to cost or gradient.
+ * Outputs; every pointer of the result is nullable:
+ *   cost       per path: the sum of h * Q over its segments, added in segment order -- approximates the integral of phi(d) ds
+ *   grad (x3)  per WAYPOINT (n_waypoints rows): N of the segment that starts there + E of the segment that ends there (a missing
+ *              one is 0): the exact derivative of `cost` of the waypoint's path at fixed S, wherever the interpolant is
+ *              differentiable.  Every one of the n_waypoints rows is written by every call; rows that belong to no valid path are 0.
+ *   length     per path: the sum of L over its segments, added in segment order
+ *   n_below    per path: samples whose value is < margin (strictly)
+ *   n_samples  per path: as fiesta_hip_path_result.n_samples
+ * Every TERM above is bit-identical on the device, on the host and in fiesta_amd.path_cost_model (numpy); only the order in which
+ * the interior samples' terms are added into P, A, B is left free: it is fixed by the call's arguments and the map (the device
+ * adds by lane groups inside pieces whose size follows n_paths, the small-batch host route in sample order), so the two routes
+ * are NOT promised bit-equal.  With n the number of terms that enter an output and a the sum of their absolute values on the
+ * output's scale, any two orders differ by at most (n + 16) * 2^-52 * a (the bound the tests hold both routes to).
+ * Determinism: no floating-point atomics; the same call on the same map gives the same bits; nothing depends on the launch
+ * shape or on scheduling.
+ * Special paths: empty or one waypoint: cost 0, length 0, gradient row 0, n_below by its samples (0 or 1).  Invalid (the rules of
+ * path clearance, the device variant's offset rules included): cost NaN, length NaN, n_below -1, n_samples -1, its gradient rows
+ * 0; the other paths are unaffected.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): those of path clearance, and a margin that
+ * is not finite.  n_paths = 0 does nothing.
+ * fiesta_hip_path_cost      host pointers; stages, runs, synchronises.  A batch of at most 256 samples is answered on the host from
+ *                           the brick cache.
+ * fiesta_hip_path_cost_dev  every array a device pointer (the struct itself is a host object); only enqueued on the map's stream. */
+typedef struct fiesta_hip_path_cost_result {
+  double *cost;
+  double *grad;
+  double *length;
+  int64_t *n_below;
+  int64_t *n_samples;
+} fiesta_hip_path_cost_result;
+int fiesta_hip_path_cost(fiesta_hip_map *m, const double *waypoints, int64_t n_waypoints, const int64_t *offsets, int64_t n_paths,
+                         double step, double margin, const fiesta_hip_path_cost_result *result);
+int fiesta_hip_path_cost_dev(fiesta_hip_map *m, const double *waypoints_dev, int64_t n_waypoints, const int64_t *offsets_dev,
+                             int64_t n_paths, double step, double margin, const fiesta_hip_path_cost_result *result);
 
 /* ---- whole-field access (tests, visualisation, checkpoints) ----
  * Dense dump in the reference's linear order; each output is nullable.
