@@ -4,7 +4,7 @@ The product is ``libfiesta_hip.so`` (hand-written HIP for gfx950 behind the C AB
 include/fiesta_hip.h); this package is the thin host-side mirror of the reference interface.
 """
 from ._lib import FiestaHipError, LIB_PATH, device_count, load  # noqa: F401
-from .esdf_map import D2_INF, INFINITY, UNDEFINED, ESDFMap, path_cost_model, path_samples, signed_distance  # noqa: F401
+from .esdf_map import D2_INF, INFINITY, UNDEFINED, ESDFMap, frontier_model, path_cost_model, path_samples, signed_distance  # noqa: F401
 
-__all__ = ["ESDFMap", "signed_distance", "path_samples", "path_cost_model", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
+__all__ = ["ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
            "D2_INF"]

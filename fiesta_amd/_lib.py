@@ -174,6 +174,8 @@ def load():
         "fiesta_hip_path_clearance_dev": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
         "fiesta_hip_path_cost": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
         "fiesta_hip_path_cost_dev": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
+        "fiesta_hip_get_frontier_voxels": (C.c_int, [vp, vp, vp, dbl, vp, vp, i64, vp]),
+        "fiesta_hip_get_frontier_voxels_dev": (C.c_int, [vp, vp, vp, dbl, vp, vp, i64, vp]),
         "fiesta_hip_get_occupancy_vox": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_get_occupancy_pos": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_download_field": (C.c_int, [vp, vp, vp, vp, vp]),

@@ -63,6 +63,14 @@ void path_args(fiesta_hip_map *m, const double *w, int64_t n_wp, const int64_t *
   need(off[0] == 0 && off[n_paths] == n_wp, "path query: offsets[0] must be 0 and offsets[n_paths] = n_waypoints");
   for (int64_t p = 0; p < n_paths; ++p) need(off[p] <= off[p + 1], "path query: offsets must be non-decreasing");
 }
+// the whole-call errors of fiesta_hip_get_frontier_voxels[_dev] (include/fiesta_hip.h)
+void frontier_args(fiesta_hip_map *m, const int32_t *lo, const int32_t *hi, double min_clearance, int64_t capacity, const void *n_out) {
+  need(m != nullptr, "null map handle");
+  need(n_out != nullptr, "get_frontier_voxels: n_out is null");
+  need(!std::isnan(min_clearance), "get_frontier_voxels: min_clearance is NaN");
+  need((lo == nullptr) == (hi == nullptr), "get_frontier_voxels: lo and hi must both be given or both be null");
+  need(capacity >= 0, "get_frontier_voxels: negative capacity");
+}
 }  // namespace
 
 extern "C" {
@@ -469,6 +477,24 @@ int fiesta_hip_get_occupied_voxels(fiesta_hip_map *m, int32_t *vox, int64_t capa
   return guarded([&] {
     need(n_out != nullptr && capacity >= 0, "bad argument");
     *n_out = dense(m, "get_occupied_voxels").occupied_voxels(vox, capacity);
+  });
+}
+int fiesta_hip_get_frontier_voxels(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance, int32_t *vox,
+                                   uint8_t *mask, int64_t capacity, int64_t *n_out) {
+  return guarded([&] {
+    frontier_args(m, lo, hi, min_clearance, capacity, n_out);
+    *n_out = m->dense ? m->dense->frontier_voxels(lo, hi, min_clearance, vox, mask, capacity, nullptr, false)
+                      : m->hash->frontier_voxels(lo, hi, min_clearance, vox, mask, capacity, nullptr, false);
+  });
+}
+int fiesta_hip_get_frontier_voxels_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance, int32_t *vox_dev,
+                                       uint8_t *mask_dev, int64_t capacity, unsigned long long *n_out_dev) {
+  return guarded([&] {
+    frontier_args(m, lo, hi, min_clearance, capacity, n_out_dev);
+    if (m->dense)
+      m->dense->frontier_voxels(lo, hi, min_clearance, vox_dev, mask_dev, capacity, n_out_dev, true);
+    else
+      m->hash->frontier_voxels(lo, hi, min_clearance, vox_dev, mask_dev, capacity, n_out_dev, true);
   });
 }
 int fiesta_hip_get_slice(fiesta_hip_map *m, int32_t z_vox, double *out) {

@@ -24,6 +24,7 @@
 // are appended to the next round's tile list (level-synchronous rounds, one launch per round).
 #include "dense_map.hpp"
 #include "checkpoint.hpp"
+#include "frontier_kernels.hpp"
 #include "ft_kernels.hpp"
 #include "nn_kernels.hpp"
 #include "mask_kernels.hpp"
@@ -667,6 +668,15 @@ struct DensePathEval {
   __device__ double operator()(const double *p, double *grad) const {
     FieldWords wd{g, coc};
     return query_trilinear(g, wd, p, grad);
+  }
+};
+// the clearance filter of the frontier kernel (frontier_kernels.hpp): GetDistance(Vector3i) on the field itself, local coordinates
+struct DenseFrontierDist {
+  Geom g;
+  const vox_t *coc;
+  __device__ double operator()(int x, int y, int z) const {
+    FieldWords wd{g, coc};
+    return vox_distance(g, wd, x, y, z);
   }
 };
 // GetOccupancy x2 (src/ESDFMap.cpp:452-465)
@@ -2632,6 +2642,54 @@ int64_t DenseMap::occupied_voxels(int32_t *vox, int64_t cap) {
   FIESTA_HIP_CHECK(hipGetLastError());
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
   if (dout && n) FIESTA_HIP_CHECK(hipMemcpyAsync(vox, dout, (size_t)std::min(n, cap) * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
+  return n;
+}
+
+// fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp); arguments checked by the caller.  dev: vox / mask / n_out_dev are
+// device pointers and the call is only enqueued; else host pointers, and the total is returned.
+int64_t DenseMap::frontier_voxels(const int32_t *lo, const int32_t *hi, double min_clearance, int32_t *vox, uint8_t *mask, int64_t cap,
+                                  unsigned long long *n_out_dev, bool dev) {
+  use_device();
+  unsigned long long *count = dev ? n_out_dev : &counters_[C_SCRATCH];
+  if (dev)
+    hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, stream_, count, 1);
+  else
+    zero_counter(C_SCRATCH);
+  FIESTA_HIP_CHECK(hipGetLastError());
+  // the box in local array coordinates, intersected with the array
+  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0}, dims[3] = {g_.nx, g_.ny, g_.nz};
+  int64_t blo[3], bhi[3], nvox = 1;
+  for (int c = 0; c < 3; ++c) {
+    blo[c] = lo ? std::max<int64_t>((int64_t)lo[c] - g0[c], 0) : 0;
+    bhi[c] = hi ? std::min<int64_t>((int64_t)hi[c] - g0[c], dims[c] - 1) : dims[c] - 1;
+    nvox = blo[c] > bhi[c] ? 0 : nvox * (bhi[c] - blo[c] + 1);
+  }
+  cap = std::min(cap, nvox);
+  int32_t *dvox = dev ? vox : nullptr;
+  uint8_t *dmask = dev ? mask : nullptr;
+  if (!dev && cap > 0) {
+    if (vox) stage_a_.ensure((size_t)cap * 3 * sizeof(int32_t), stream_), dvox = (int32_t *)stage_a_.p;
+    if (mask) stage_b_.ensure((size_t)cap, stream_), dmask = (uint8_t *)stage_b_.p;
+  }
+  if (nvox > 0 && g_.sharded) {
+    // a shard's ghost cells are written by the halo exchange, which does not keep obsbits_: bring the bitmap in line with the field
+    hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
+    FIESTA_HIP_CHECK(hipGetLastError());
+  }
+  if (nvox > 0) {
+    const FrontierBox b{(int)blo[0], (int)blo[1], (int)blo[2], (int)bhi[0], (int)bhi[1], (int)bhi[2]};
+    const int64_t nwords = (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * ((bhi[2] >> 5) - (blo[2] >> 5) + 1);
+    hipLaunchKernelGGL(k_frontier_dense<DenseFrontierDist>, dim3(grid_for(nwords, 256, 8192)), dim3(256), 0, stream_, g_,
+                       (const uint32_t *)obsbits_, (const uint32_t *)occbits_, b, DenseFrontierDist{g_, (const vox_t *)coc_}, min_clearance,
+                       FrontierOut{dvox, dmask, (unsigned long long)cap, count});
+    FIESTA_HIP_CHECK(hipGetLastError());
+  }
+  if (dev) return 0;
+  const int64_t n = (int64_t)read_counter(C_SCRATCH);
+  const size_t k = (size_t)std::min(n, cap);
+  if (dvox && k) FIESTA_HIP_CHECK(hipMemcpyAsync(vox, dvox, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(mask, dmask, k, hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }

@@ -153,6 +153,9 @@ class DenseMap {
   void download_field(int32_t *d2, int32_t *coc, uint8_t *occ, double *logodds);
   void download_counts(int32_t *num_hit, int32_t *num_miss);
   int64_t occupied_voxels(int32_t *vox, int64_t cap);  // returns the total count (may exceed cap)
+  // fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp); returns the total count (host variant; may exceed cap)
+  int64_t frontier_voxels(const int32_t *lo, const int32_t *hi, double min_clearance, int32_t *vox, uint8_t *mask, int64_t cap,
+                          unsigned long long *n_out_dev, bool dev);
   int64_t count_no_obstacle();
   void slice_distances(int z_vox, double *out);        // nx * ny doubles, x-major
   // GetPointCloud / GetSliceMarker as arrays; both return the total count (may exceed cap), order unspecified

@@ -19,6 +19,7 @@
 
 #include "level_kernels.hpp"
 #include "path_cost_kernels.hpp"
+#include "frontier_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
@@ -493,6 +494,15 @@ struct HashPathEval {
     auto corner = [&](int vx, int vy, int vz) { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); };
     return h_trilinear(g, corner, p, grad);
   }
+};
+// the page source of the frontier kernel (frontier_kernels.hpp), MAP voxel coordinates: the queries' lookup and GetDistance(Vector3i)
+struct HashFrontierPages {
+  Geom g;
+  const int32_t *dir;
+  PageTable tab;
+  const vox_t *coc;
+  __device__ int64_t addr(int vx, int vy, int vz) const { return h_lookup(g, dir, tab, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
+  __device__ double operator()(int vx, int vy, int vz) const { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
 };
 // a brick of the host-side cache: the 16^3 distances and occupancy bits of map brick (bx, by, bz), straight into pinned memory
 __global__ __launch_bounds__(256) void k_h_fetch_brick(Geom g, const int32_t *dir, PageTable tab, const vox_t *coc, const uint32_t *occbits, int bx,
@@ -1545,6 +1555,43 @@ int64_t HashMap::point_cloud(int vis_lower_bound, int vis_upper_bound, float *xy
   FIESTA_HIP_CHECK(hipGetLastError());
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
   if (dout && n) FIESTA_HIP_CHECK(hipMemcpyAsync(xyz, dout, (size_t)std::min(n, cap) * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
+  return n;
+}
+
+// fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp); arguments checked by the caller.  Every page, resident or parked; a
+// null box is the whole map.
+int64_t HashMap::frontier_voxels(const int32_t *lo, const int32_t *hi, double min_clearance, int32_t *vox, uint8_t *mask, int64_t cap,
+                                 unsigned long long *n_out_dev, bool dev) {
+  use_device();
+  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
+  unsigned long long *count = dev ? n_out_dev : &counters_[C_SCRATCH];
+  hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, stream_, count, 1);
+  FIESTA_HIP_CHECK(hipGetLastError());
+  // (page coordinates stay within +-2^25: clamping the box there changes nothing and keeps the kernel's differences in range)
+  auto c = [](int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, -(1ll << 30)), 1ll << 30); };
+  FrontierBox b{c(INT32_MIN), c(INT32_MIN), c(INT32_MIN), c(INT32_MAX), c(INT32_MAX), c(INT32_MAX)};
+  if (lo) b = FrontierBox{c(lo[0]), c(lo[1]), c(lo[2]), c(hi[0]), c(hi[1]), c(hi[2])};
+  const bool empty = b.x0 > b.x1 || b.y0 > b.y1 || b.z0 > b.z1 || npages_ == 0;
+  cap = std::min<int64_t>(cap, npages_ * kPageVox);
+  int32_t *dvox = dev ? vox : nullptr;
+  uint8_t *dmask = dev ? mask : nullptr;
+  if (!dev && cap > 0) {
+    if (vox) stage_a_.ensure((size_t)cap * 3 * sizeof(int32_t), stream_), dvox = (int32_t *)stage_a_.p;
+    if (mask) stage_b_.ensure((size_t)cap, stream_), dmask = (uint8_t *)stage_b_.p;
+  }
+  if (!empty) {
+    hipLaunchKernelGGL(k_frontier_hash<HashFrontierPages>, dim3(grid_for(npages_, 1, 8192)), dim3(256), 0, stream_,
+                       (const int32_t *)page_gtile_.p, npages_, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p, b,
+                       HashFrontierPages{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}, min_clearance,
+                       FrontierOut{dvox, dmask, (unsigned long long)cap, count});
+    FIESTA_HIP_CHECK(hipGetLastError());
+  }
+  if (dev) return 0;
+  const int64_t n = (int64_t)read_counter(C_SCRATCH);
+  const size_t k = (size_t)std::min(n, cap);
+  if (dvox && k) FIESTA_HIP_CHECK(hipMemcpyAsync(vox, dvox, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(mask, dmask, k, hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }

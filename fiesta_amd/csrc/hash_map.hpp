@@ -90,6 +90,9 @@ class HashMap {
   void checkpoint(const char *path, bool write);  // raw dump / load of the whole state (checkpoint.hpp)
   int64_t point_cloud(int vis_lower_bound, int vis_upper_bound, float *xyz, int64_t cap);  // GetPointCloud, as arrays
   int64_t slice_marker(int slice, double max_dist, double *xyz, float *rgba, int64_t cap);  // GetSliceMarker
+  // fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp); returns the total count (host variant; may exceed cap)
+  int64_t frontier_voxels(const int32_t *lo, const int32_t *hi, double min_clearance, int32_t *vox, uint8_t *mask, int64_t cap,
+                          unsigned long long *n_out_dev, bool dev);
   void synchronize();
 
  private:

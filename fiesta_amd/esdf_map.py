@@ -171,6 +171,36 @@ def path_cost_model(query, waypoints, offsets, step, margin):
     return out
 
 
+def frontier_model(observed, occupied, dist=None, lo=None, hi=None, min_clearance=0.0, origin_vox=(0, 0, 0), bounded=True):
+    """The definition of fiesta_hip_get_frontier_voxels (include/fiesta_hip.h) in numpy, over 3-D boolean arrays indexed [x, y, z]
+    whose element (0, 0, 0) is map voxel `origin_vox`: the observed, unoccupied voxels with a never-observed 6-neighbour, inside the
+    inclusive map-voxel box [lo, hi] (None: everything), and -- only if min_clearance > 0 -- with dist >= min_clearance (`dist`: the
+    f64 array of GetDistance(Vector3i)).  A neighbour outside the array is not unknown when `bounded` (a dense map's outer face is no
+    frontier) and unknown otherwise (a hash-block map scattered into a padded array).  Returns (vox (n, 3) int32 in map voxel
+    coordinates, mask (n,) uint8: bit 0 -x, 1 +x, 2 -y, 3 +y, 4 -z, 5 +z), sorted lexicographically by (x, y, z)."""
+    obs = np.asarray(observed, dtype=bool)
+    free = obs & ~np.asarray(occupied, dtype=bool)
+    unknown = np.pad(~obs, 1, constant_values=not bounded)   # unknown[i + 1, j + 1, k + 1] belongs to voxel (i, j, k)
+    nx, ny, nz = obs.shape
+    mask = np.zeros(obs.shape, np.uint8)
+    for bit, (dx, dy, dz) in enumerate(((-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1))):
+        nb = unknown[1 + dx:1 + dx + nx, 1 + dy:1 + dy + ny, 1 + dz:1 + dz + nz]
+        mask |= (nb & free).astype(np.uint8) << bit
+    keep = mask != 0
+    org = np.asarray(origin_vox, dtype=np.int64).reshape(3)
+    if lo is not None or hi is not None:
+        if lo is None or hi is None:
+            raise ValueError("lo and hi must both be given or both be None")
+        lo = np.asarray(lo, dtype=np.int64).reshape(3) - org
+        hi = np.asarray(hi, dtype=np.int64).reshape(3) - org
+        ix, iy, iz = np.ogrid[:nx, :ny, :nz]
+        keep &= (ix >= lo[0]) & (ix <= hi[0]) & (iy >= lo[1]) & (iy <= hi[1]) & (iz >= lo[2]) & (iz <= hi[2])
+    if min_clearance > 0:
+        keep &= np.asarray(dist, dtype=np.float64) >= min_clearance
+    idx = np.argwhere(keep)                                   # (row-major: sorted by x, then y, then z)
+    return (idx + org).astype(np.int32).reshape(-1, 3), mask[keep].astype(np.uint8)
+
+
 class ESDFMap:
     """Drop-in for ``fiesta::ESDFMap``; array mode by default, hash-block mode with ``mode="hash"``."""
 
@@ -465,6 +495,32 @@ class ESDFMap:
         if n.value:
             check(self._lib.fiesta_hip_get_occupied_voxels(self._h, _p(out), n.value, C.byref(n)))
         return out
+
+    def GetFrontierVoxels(self, lo=None, hi=None, min_clearance=0.0, want_mask=True):
+        """fiesta_hip_get_frontier_voxels: the observed-free voxels with a never-observed 6-neighbour inside the inclusive map-voxel
+        box [lo, hi] (both None: the whole map), optionally only those with GetDistance >= min_clearance -- (vox (n, 3) int32,
+        mask (n,) uint8: the unknown-neighbour bits, or None without want_mask), unordered; frontier_model is the definition"""
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        blo = None if lo is None else np.ascontiguousarray(lo, np.int32).reshape(3)
+        bhi = None if hi is None else np.ascontiguousarray(hi, np.int32).reshape(3)
+        n = C.c_int64(0)
+        check(self._lib.fiesta_hip_get_frontier_voxels(self._h, _p(blo), _p(bhi), float(min_clearance), None, None, 0, C.byref(n)))
+        vox = np.empty((n.value, 3), np.int32)
+        mask = np.empty(n.value, np.uint8) if want_mask else None
+        if n.value:
+            check(self._lib.fiesta_hip_get_frontier_voxels(self._h, _p(blo), _p(bhi), float(min_clearance), _p(vox), _p(mask), n.value,
+                                                           C.byref(n)))
+        return vox, mask
+
+    def GetFrontierVoxelsDevice(self, lo, hi, min_clearance, vox_dev_ptr: int, mask_dev_ptr: int, capacity: int, n_out_dev_ptr: int):
+        """fiesta_hip_get_frontier_voxels_dev: the outputs and the 64-bit counter resident on the device (0: that array is not
+        written), lo / hi host triples or None; only enqueued on the map's stream, the call zeroes the counter itself"""
+        blo = None if lo is None else np.ascontiguousarray(lo, np.int32).reshape(3)
+        bhi = None if hi is None else np.ascontiguousarray(hi, np.int32).reshape(3)
+        check(self._lib.fiesta_hip_get_frontier_voxels_dev(self._h, _p(blo), _p(bhi), float(min_clearance), C.c_void_p(vox_dev_ptr or None),
+                                                           C.c_void_p(mask_dev_ptr or None), int(capacity),
+                                                           C.c_void_p(n_out_dev_ptr or None)))
 
     def count_no_obstacle(self) -> int:
         """Observed voxels whose distance reads +10000 (on grids beyond 1024 per axis this includes everything farther than

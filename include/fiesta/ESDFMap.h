@@ -246,6 +246,19 @@ class ESDFMap {
       centres->push_back(Eigen::Vector3d((vox[3 * i] + 0.5) * res_ + origin_[0], (vox[3 * i + 1] + 0.5) * res_ + origin_[1],
                                          (vox[3 * i + 2] + 0.5) * res_ + origin_[2]));
   }
+  // Frontier voxels (fiesta_hip_get_frontier_voxels, include/fiesta_hip.h): the observed, unoccupied voxels with a never-observed
+  // 6-neighbour inside the inclusive voxel box [lo, hi], optionally only those with GetDistance >= min_clearance; `mask` receives
+  // the unknown-neighbour bits (bit 0 -x, 1 +x, 2 -y, 3 +y, 4 -z, 5 +z) of out[i].  Order unspecified.  An exploration planner calls
+  // it with the bounding box of the last sensor frame.
+  void GetFrontierVoxels(const Eigen::Vector3i &lo, const Eigen::Vector3i &hi, double min_clearance, std::vector<Eigen::Vector3i> &out,
+                         std::vector<uint8_t> *mask = nullptr) {
+    const int32_t a[3] = {lo(0), lo(1), lo(2)}, b[3] = {hi(0), hi(1), hi(2)};
+    FrontierVoxels(a, b, min_clearance, out, mask);
+  }
+  // ... of the whole map
+  void GetFrontierVoxels(double min_clearance, std::vector<Eigen::Vector3i> &out, std::vector<uint8_t> *mask = nullptr) {
+    FrontierVoxels(nullptr, nullptr, min_clearance, out, mask);
+  }
   // The reference's own getters (include/ESDFMap.h:144-145, src/ESDFMap.cpp:544-699).  The message types are template
   // parameters so that this header builds without ROS; sensor_msgs::PointCloud and visualization_msgs::Marker fit as
   // they are (fields used: header.frame_id, points[i].x/y/z, and for the marker id, type, action, scale, pose.orientation,
@@ -330,6 +343,17 @@ class ESDFMap {
 
  private:
   static constexpr size_t kFlushAt = 1u << 20;
+  void FrontierVoxels(const int32_t *lo, const int32_t *hi, double min_clearance, std::vector<Eigen::Vector3i> &out,
+                      std::vector<uint8_t> *mask) {
+    Flush();
+    int64_t n = 0;
+    ck(fiesta_hip_get_frontier_voxels(h_, lo, hi, min_clearance, nullptr, nullptr, 0, &n));
+    std::vector<int32_t> vox((size_t)3 * n);
+    if (mask) mask->assign((size_t)n, 0);
+    if (n) ck(fiesta_hip_get_frontier_voxels(h_, lo, hi, min_clearance, vox.data(), mask ? mask->data() : nullptr, n, &n));
+    out.clear();
+    for (int64_t i = 0; i < n; ++i) out.push_back(Eigen::Vector3i(vox[3 * i], vox[3 * i + 1], vox[3 * i + 2]));
+  }
   fiesta_hip_map *h_ = nullptr;
   bool hash_ = false;
   double origin_[3], res_ = 0, min_range_[3], max_range_[3];

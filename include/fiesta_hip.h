@@ -130,7 +130,8 @@ typedef struct fiesta_hip_stats {
 
 const char *fiesta_hip_last_error(void);
 /* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev].
- * fiesta_hip_path_cost[_dev] came later without a new number: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_path_cost[_dev] and fiesta_hip_get_frontier_voxels[_dev] came later without a new number: detect them by symbol
+ * lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -402,6 +403,40 @@ int fiesta_hip_path_cost(fiesta_hip_map *m, const double *waypoints, int64_t n_w
                          double step, double margin, const fiesta_hip_path_cost_result *result);
 int fiesta_hip_path_cost_dev(fiesta_hip_map *m, const double *waypoints_dev, int64_t n_waypoints, const int64_t *offsets_dev,
                              int64_t n_paths, double step, double margin, const fiesta_hip_path_cost_result *result);
+
+/* ---- frontier voxels: observed-free voxels that border never-observed space, compacted on the device ----
+ * What an exploration planner asks after every frame: where does known free space end, and which of those places can the robot
+ * reach?  No reference counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.
+ * For a voxel v of the map, in map voxel coordinates (those fiesta_hip_get_occupied_voxels reports):
+ *   observed(v)  v has been observed at least once: exactly the voxels where fiesta_hip_download_field's d2 >= 0; on a hash-block
+ *                map the voxels fiesta_hip_download_hash lists with d2 >= 0 (a voxel of a tile without a page is not observed).
+ *   free(v)      observed(v) and Exist(v) is false (GetOccupancy(v) == 0).
+ *   u(v)         the unknown-neighbour mask, six bits: a bit is set where that 6-neighbour is inside the map and not observed.
+ *                bit 0: -x, bit 1: +x, bit 2: -y, bit 3: +y, bit 4: -z, bit 5: +z.  A neighbour outside a dense map's array is NOT
+ *                unknown (the outer face of the map is no frontier); a hash-block map has no outside.  The query box below does
+ *                not clip the neighbour test.
+ *   frontier(v)  free(v) and u(v) != 0, v inside the inclusive voxel box [lo, hi], and -- only if min_clearance > 0 --
+ *                GetDistance(Vector3i v) >= min_clearance, with the very f64 value the voxel query returns
+ *                (sqrt((double)d2) * resolution; +10000 for "observed, no obstacle", which therefore passes).  With
+ *                min_clearance <= 0 the field is not read at all.  The field is read as it stands, like every query: after
+ *                UpdateOccupancy and before UpdateESDF the filter sees the old distances.
+ * lo / hi are HOST pointers in both variants.  Both NULL: the whole array of a dense map, every page of a hash-block map (parked
+ * pages included: they answer every query).  The box is intersected with the map; an empty intersection, or lo[c] > hi[c], gives
+ * a total of 0 and is no error.
+ * At most `capacity` entries are written: vox holds 3 int32 per entry, mask holds u(v), entry k of both arrays describes the same
+ * voxel; each of the two is nullable.  *n_out is the total whatever the capacity (call with capacity 0 to size the buffers, as
+ * with the visualisation getters).  Order is unspecified; the SET of (v, u(v)) pairs is exact and the same for every launch shape.
+ * A map created as a shard answers for its own array, like fiesta_hip_get_occupied_voxels; there is no shard-group call.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): min_clearance is NaN, exactly one of lo / hi
+ * is NULL, capacity is negative, n_out is NULL.
+ * fiesta_hip_get_frontier_voxels      host arrays; stages, runs, synchronises, copies min(total, capacity) entries back.
+ * fiesta_hip_get_frontier_voxels_dev  vox_dev / mask_dev / n_out_dev are device pointers; only enqueued on the map's stream, no host
+ *                                     round trip: the call zeroes *n_out_dev itself (a hash-block map first rebuilds its page table
+ *                                     if its page set changed, as every query does). */
+int fiesta_hip_get_frontier_voxels(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance, int32_t *vox,
+                                   uint8_t *mask, int64_t capacity, int64_t *n_out);
+int fiesta_hip_get_frontier_voxels_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance,
+                                       int32_t *vox_dev, uint8_t *mask_dev, int64_t capacity, unsigned long long *n_out_dev);
 
 /* ---- whole-field access (tests, visualisation, checkpoints) ----
  * Dense dump in the reference's linear order; each output is nullable.
