@@ -4,7 +4,8 @@ The product is ``libfiesta_hip.so`` (hand-written HIP for gfx950 behind the C AB
 include/fiesta_hip.h); this package is the thin host-side mirror of the reference interface.
 """
 from ._lib import FiestaHipError, LIB_PATH, device_count, load  # noqa: F401
-from .esdf_map import D2_INF, INFINITY, UNDEFINED, ESDFMap, frontier_model, path_cost_model, path_samples, signed_distance  # noqa: F401
+from .esdf_map import (D2_INF, INFINITY, UNDEFINED, ESDFMap, frontier_model, path_cost_model, path_samples, ray_query_model,  # noqa: F401
+                       ray_walk, ray_walks, signed_distance)
 
-__all__ = ["ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
+__all__ = ["ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
            "D2_INF"]

@@ -79,6 +79,12 @@ class PathCostResult(C.Structure):
                 ("n_samples", C.c_void_p)]
 
 
+class RayResult(C.Structure):
+    """fiesta_hip_ray_result: one array per output of fiesta_hip_ray_query, every pointer nullable"""
+    _fields_ = [("n_visited", C.c_void_p), ("hit_index", C.c_void_p), ("hit_class", C.c_void_p), ("hit_vox", C.c_void_p),
+                ("hit_dist", C.c_void_p), ("counts", C.c_void_p)]
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/fiesta_hip.h declares (used by the CPU export test)."""
     text = open(header_path).read()
@@ -176,6 +182,8 @@ def load():
         "fiesta_hip_path_cost_dev": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
         "fiesta_hip_get_frontier_voxels": (C.c_int, [vp, vp, vp, dbl, vp, vp, i64, vp]),
         "fiesta_hip_get_frontier_voxels_dev": (C.c_int, [vp, vp, vp, dbl, vp, vp, i64, vp]),
+        "fiesta_hip_ray_query": (C.c_int, [vp, vp, vp, i64, i32, vp]),
+        "fiesta_hip_ray_query_dev": (C.c_int, [vp, vp, vp, i64, i32, vp]),
         "fiesta_hip_get_occupancy_vox": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_get_occupancy_pos": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_download_field": (C.c_int, [vp, vp, vp, vp, vp]),

@@ -71,6 +71,13 @@ void frontier_args(fiesta_hip_map *m, const int32_t *lo, const int32_t *hi, doub
   need((lo == nullptr) == (hi == nullptr), "get_frontier_voxels: lo and hi must both be given or both be null");
   need(capacity >= 0, "get_frontier_voxels: negative capacity");
 }
+// the whole-call errors of fiesta_hip_ray_query[_dev] (include/fiesta_hip.h)
+void ray_args(fiesta_hip_map *m, const double *start, const double *end, int64_t n, int32_t stop_mask, const void *r) {
+  need(m != nullptr, "null map handle");
+  need(start && end && r, "ray_query: start, end or result is null");
+  need(n >= 0, "ray_query: negative count");
+  need(stop_mask >= 0 && stop_mask <= 7, "ray_query: stop_mask must be a subset of OCCUPIED | UNKNOWN | OUTSIDE (0..7)");
+}
 }  // namespace
 
 extern "C" {
@@ -495,6 +502,26 @@ int fiesta_hip_get_frontier_voxels_dev(fiesta_hip_map *m, const int32_t lo[3], c
       m->dense->frontier_voxels(lo, hi, min_clearance, vox_dev, mask_dev, capacity, n_out_dev, true);
     else
       m->hash->frontier_voxels(lo, hi, min_clearance, vox_dev, mask_dev, capacity, n_out_dev, true);
+  });
+}
+int fiesta_hip_ray_query(fiesta_hip_map *m, const double *start, const double *end, int64_t n, int32_t stop_mask,
+                         const fiesta_hip_ray_result *r) {
+  return guarded([&] {
+    ray_args(m, start, end, n, stop_mask, r);
+    if (m->dense)
+      m->dense->ray_query(start, end, n, stop_mask, *r, false);
+    else
+      m->hash->ray_query(start, end, n, stop_mask, *r, false);
+  });
+}
+int fiesta_hip_ray_query_dev(fiesta_hip_map *m, const double *start_dev, const double *end_dev, int64_t n, int32_t stop_mask,
+                             const fiesta_hip_ray_result *r) {
+  return guarded([&] {
+    ray_args(m, start_dev, end_dev, n, stop_mask, r);
+    if (m->dense)
+      m->dense->ray_query(start_dev, end_dev, n, stop_mask, *r, true);
+    else
+      m->hash->ray_query(start_dev, end_dev, n, stop_mask, *r, true);
   });
 }
 int fiesta_hip_get_slice(fiesta_hip_map *m, int32_t z_vox, double *out) {

@@ -25,6 +25,7 @@
 #include "dense_map.hpp"
 #include "checkpoint.hpp"
 #include "frontier_kernels.hpp"
+#include "ray_query_kernels.hpp"
 #include "ft_kernels.hpp"
 #include "nn_kernels.hpp"
 #include "mask_kernels.hpp"
@@ -2692,6 +2693,18 @@ int64_t DenseMap::frontier_voxels(const int32_t *lo, const int32_t *hi, double m
   if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(mask, dmask, k, hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
+}
+
+// fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller
+void DenseMap::ray_query(const double *start, const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev) {
+  if (n <= 0) return;
+  use_device();
+  if (g_.sharded) {  // (the halo exchange does not keep obsbits_ in ghost cells: see frontier_voxels)
+    hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
+    FIESTA_HIP_CHECK(hipGetLastError());
+  }
+  ray_query_run(stream_, path_in_, path_out_, DenseRaySource(g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_), start, end, n,
+                stop_mask, r, dev);
 }
 
 int64_t DenseMap::point_cloud(int vis_lower_bound, int vis_upper_bound, float *xyz, int64_t cap) {

@@ -156,6 +156,8 @@ class DenseMap {
   // fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp); returns the total count (host variant; may exceed cap)
   int64_t frontier_voxels(const int32_t *lo, const int32_t *hi, double min_clearance, int32_t *vox, uint8_t *mask, int64_t cap,
                           unsigned long long *n_out_dev, bool dev);
+  // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller
+  void ray_query(const double *start, const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev);
   int64_t count_no_obstacle();
   void slice_distances(int z_vox, double *out);        // nx * ny doubles, x-major
   // GetPointCloud / GetSliceMarker as arrays; both return the total count (may exceed cap), order unspecified
@@ -336,7 +338,7 @@ class DenseMap {
 
   // staging
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_;
-  DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path clearance: staged inputs, plan / piece records, staged outputs
+  DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path and ray queries: staged inputs, plan / piece records, staged outputs
   // raycast front-end state (per-frame stamp arrays = Fiesta::set_occ_/set_free_, include/Fiesta.h:107-110;
   // per-ray traversal lists), lazily allocated by raycast.hip
   struct RaycastState;

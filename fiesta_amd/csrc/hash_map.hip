@@ -20,6 +20,7 @@
 #include "level_kernels.hpp"
 #include "path_cost_kernels.hpp"
 #include "frontier_kernels.hpp"
+#include "ray_query_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
@@ -503,6 +504,37 @@ struct HashFrontierPages {
   const vox_t *coc;
   __device__ int64_t addr(int vx, int vy, int vz) const { return h_lookup(g, dir, tab, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
   __device__ double operator()(int vx, int vy, int vz) const { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
+};
+// the voxel source of the ray query (ray_query_kernels.hpp): the queries' lookup once per TILE -- the page address of the tile the
+// ray is in stays in registers (-1: no page, every voxel of it unknown) -- then the voxel's field word and, if it is observed, the
+// occupancy word of its row
+struct HashRaySource {
+  RayGeom g;
+  Geom win;  // the window, for the lookup
+  const int32_t *dir;
+  PageTable tab;
+  const vox_t *coc;
+  const uint32_t *occbits;
+  struct Cache {
+    int tx, ty, tz;
+    int64_t base, ow;
+    uint32_t occ;
+  };
+  __device__ static Cache fresh() { return Cache{INT32_MIN, 0, 0, -1, -1, 0u}; }
+  __device__ int classify(const int *, const int *v, Cache &c) const {
+    constexpr int kFar = 1 << 28;  // (pages lie within +-2^24 voxels of the map origin: tile_key)
+    if (v[0] < -kFar || v[0] > kFar || v[1] < -kFar || v[1] > kFar || v[2] < -kFar || v[2] > kFar) return FIESTA_HIP_RAY_UNKNOWN;
+    const int tx = v[0] >> 4, ty = v[1] >> 4, tz = v[2] >> 5;
+    if (tx != c.tx || ty != c.ty || tz != c.tz) {
+      c.tx = tx, c.ty = ty, c.tz = tz;
+      c.base = h_lookup(win, dir, tab, tx * 16 - win.gx0, ty * 16 - win.gy0, tz * 32 - win.gz0);  // (the tile's first voxel: offset 0 of its page)
+    }
+    if (c.base < 0) return FIESTA_HIP_RAY_UNKNOWN;
+    const int64_t a = c.base + (((v[0] & 15) * 16 + (v[1] & 15)) * 32 + (v[2] & 31));
+    if (coc[a] == kUnobserved) return FIESTA_HIP_RAY_UNKNOWN;
+    if ((a >> 5) != c.ow) c.ow = a >> 5, c.occ = occbits[a >> 5];
+    return ((c.occ >> (a & 31)) & 1u) ? FIESTA_HIP_RAY_OCCUPIED : FIESTA_HIP_RAY_FREE;
+  }
 };
 // a brick of the host-side cache: the 16^3 distances and occupancy bits of map brick (bx, by, bz), straight into pinned memory
 __global__ __launch_bounds__(256) void k_h_fetch_brick(Geom g, const int32_t *dir, PageTable tab, const vox_t *coc, const uint32_t *occbits, int bx,
@@ -1594,6 +1626,15 @@ int64_t HashMap::frontier_voxels(const int32_t *lo, const int32_t *hi, double mi
   if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(mask, dmask, k, hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
+}
+
+// fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller.  Every page answers, resident or parked.
+void HashMap::ray_query(const double *start, const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev) {
+  if (n <= 0) return;
+  use_device();
+  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
+  ray_query_run(stream_, path_in_, path_out_, HashRaySource{ray_geom(g_), g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p},
+                start, end, n, stop_mask, r, dev);
 }
 
 int64_t HashMap::slice_marker(int slice, double max_dist, double *xyz, float *rgba, int64_t cap) {

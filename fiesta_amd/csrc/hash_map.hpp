@@ -93,6 +93,8 @@ class HashMap {
   // fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp); returns the total count (host variant; may exceed cap)
   int64_t frontier_voxels(const int32_t *lo, const int32_t *hi, double min_clearance, int32_t *vox, uint8_t *mask, int64_t cap,
                           unsigned long long *n_out_dev, bool dev);
+  // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller
+  void ray_query(const double *start, const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev);
   void synchronize();
 
  private:
@@ -173,7 +175,7 @@ class HashMap {
   int64_t dropped_host_ = 0;  // voxels of observe_box() requests clipped away by the window (added to C_DROPPED in stats)
   unsigned long long *counters_ = nullptr, *h_counters_ = nullptr;
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_, stage_d_;
-  DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path clearance: staged inputs, plan / piece records, staged outputs
+  DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path and ray queries: staged inputs, plan / piece records, staged outputs
 };
 
 void raycast_single(const double *start, const double *end, const double *minv, const double *maxv, double *out,

@@ -1,7 +1,7 @@
 // fiesta_amd/csrc/raycast.hip -- per-ray HIP kernels that turn one sensor frame into the occupancy delta.
 //
 // Replaces (reference = HKUST-Aerial-Robotics/FIESTA):
-//   Raycast(start,end,min,max,&out)          src/raycast.cpp:56-158   -> dda_walk (device, one CASTING ray per lane)
+//   Raycast(start,end,min,max,&out)          src/raycast.cpp:56-158   -> dda_walk (ray_walk.hpp; one CASTING ray per lane)
 //   Fiesta::RaycastProcess / Multithread     include/Fiesta.h:194-303 -> k_ray_ends / k_ray_cast_list / k_ray_walk /
 //                                                                       k_ray_codes / k_ray_resolve_w / k_ray_apply_w
 //   pinhole part of Fiesta::DepthConversion  include/Fiesta.h:341-351 -> k_depth_points
@@ -27,6 +27,7 @@
 
 #include "dense_map.hpp"
 #include "hash_map.hpp"
+#include "ray_walk.hpp"  // dda_walk, ray_pos_in_map
 
 namespace fiesta {
 
@@ -34,7 +35,6 @@ constexpr uint32_t kCodeSkip = 0xFFFFFFFFu;      // no-op entry: beyond max rang
 constexpr uint32_t kCodeMinBreak = 0xFFFFFFFEu;  // closer than min_ray_length: the walk ends here
 constexpr uint32_t kCodeNoCount = 0x40000000u;   // inside the map but outside the update window
 constexpr uint32_t kCodeIdxMask = 0x3FFFFFFFu;
-constexpr int kMaxRayVoxels = 1500;              // src/raycast.cpp:127-130
 
 struct RayArgs {
   double T[16];
@@ -44,58 +44,6 @@ struct RayArgs {
   int dedup;
   int inverse;  // SIGNED_NEEDED companion map (include/Fiesta.h:216-218,249-251): end points count as free, crossings as occupied
 };
-
-__device__ inline int sgn_i(int v) { return v == 0 ? 0 : (v < 0 ? -1 : 1); }            // signum (:6-8)
-__device__ inline double wrap1(double v) { return fmod(fmod(v, 1.0) + 1.0, 1.0); }      // mod (:10-12)
-__device__ inline double first_crossing(double s, double ds) {                          // intbound (:14-23)
-  if (ds < 0) {
-    s = -s;
-    ds = -ds;
-  }
-  return (1 - wrap1(s)) / ds;
-}
-
-// Amanatides-Woo traversal with the reference's arithmetic (src/raycast.cpp:56-158). `emit(x,y,z,k)` is
-// called for every voxel the reference pushes; returns the count, or -1 if it would exceed 1500 voxels.
-template <typename Emit>
-__device__ inline int dda_walk(const double *a, const double *b, const double *lo, const double *hi, Emit emit) {
-  int c[3] = {(int)floor(a[0]), (int)floor(a[1]), (int)floor(a[2])};
-  const int e[3] = {(int)floor(b[0]), (int)floor(b[1]), (int)floor(b[2])};
-  const double r0 = b[0] - a[0], r1 = b[1] - a[1], r2 = b[2] - a[2];
-  const double reach2 = r0 * r0 + r1 * r1 + r2 * r2;
-  double tmax[3], tstep[3];
-  int step[3];
-  for (int i = 0; i < 3; ++i) {
-    const double delta = e[i] - c[i];  // NB: integer voxel delta, not the true ray direction (:89-91)
-    step[i] = sgn_i((int)delta);
-    tmax[i] = first_crossing(a[i], delta);
-    tstep[i] = ((double)step[i]) / delta;
-  }
-  if (step[0] == 0 && step[1] == 0 && step[2] == 0) return 0;
-  int count = 0;
-  for (int guard = 0; guard < 8192; ++guard) {
-    if (c[0] >= lo[0] && c[0] < hi[0] && c[1] >= lo[1] && c[1] < hi[1] && c[2] >= lo[2] && c[2] < hi[2]) {
-      emit(c[0], c[1], c[2], count);
-      ++count;
-      const double q0 = c[0] - a[0], q1 = c[1] - a[1], q2 = c[2] - a[2];
-      if (q0 * q0 + q1 * q1 + q2 * q2 > reach2) return count;
-      if (count > kMaxRayVoxels) return -1;
-    }
-    if (c[0] == e[0] && c[1] == e[1] && c[2] == e[2]) break;
-    int ax;  // strict '<' tie rules (:139-157)
-    if (tmax[0] < tmax[1])
-      ax = (tmax[0] < tmax[2]) ? 0 : 2;
-    else
-      ax = (tmax[1] < tmax[2]) ? 1 : 2;
-    c[ax] += step[ax];
-    tmax[ax] += tstep[ax];
-  }
-  return count;
-}
-
-__device__ inline bool ray_pos_in_map(const Geom &g, const double *p) {
-  return !(p[0] < g.lo[0] || p[1] < g.lo[1] || p[2] < g.lo[2] || p[0] > g.hi[0] || p[1] > g.hi[1] || p[2] > g.hi[2]);
-}
 
 __device__ inline void count_observation(int64_t idx, int occ, unsigned long long *cnt, uint32_t *touched,
                                          unsigned long long *counters) {

@@ -11,12 +11,13 @@ bench read like the reference's own driver (test/test_ESDF_Map.cpp:42-104).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
 
 from . import _lib
-from ._lib import Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, Stats, check
+from ._lib import Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, Stats, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -201,6 +202,133 @@ def frontier_model(observed, occupied, dist=None, lo=None, hi=None, min_clearanc
     return (idx + org).astype(np.int32).reshape(-1, 3), mask[keep].astype(np.uint8)
 
 
+# fiesta_hip_ray_query (include/fiesta_hip.h): the classes, the result struct in its order (name, dtype, per-ray shape), the limits
+RAY_FREE, RAY_OCCUPIED, RAY_UNKNOWN, RAY_OUTSIDE = 0, 1, 2, 4
+RAY_FIELDS = (("n_visited", np.int32, ()), ("hit_index", np.int32, ()), ("hit_class", np.uint8, ()), ("hit_vox", np.int32, (3,)),
+              ("hit_dist", np.float64, ()), ("counts", np.int32, (4,)))
+RAY_MAX_COORD = 2.0 ** 30     # |start / resolution| and |end / resolution| stay below it
+RAY_MAX_MANHATTAN = 4095      # voxel steps between the two ends
+RAY_MAX_STEPS = 8192          # the traversal's own loop bound
+RAY_NO_VOXEL = -2 ** 31
+
+
+def _ray_first_crossing(s, ds):
+    """intbound (reference src/raycast.cpp:14-23) with mod (:10-12); a zero ds divides a positive number by +0"""
+    if ds < 0:
+        s, ds = -s, -ds
+    w = math.fmod(math.fmod(s, 1.0) + 1.0, 1.0)
+    return (1 - w) / ds if ds != 0 else math.inf
+
+
+def ray_walk(a, b):
+    """The walk W of fiesta_hip_ray_query (include/fiesta_hip.h) for a ray from a to b, both in VOXEL units (position / resolution),
+    in plain Python floats (f64, every operation rounded once): the definition.  The reference's Raycast (src/raycast.cpp:56-158)
+    without clipping box and without its 1500-voxel exception, at most 8192 iterations, then the last voxel replaced by floor(b);
+    [floor(b)] if both ends lie in one voxel.  Returns an (m, 3) int64 array from start to end, or None for an invalid ray (a
+    non-finite component, one at or beyond 2^30, more than 4095 voxel steps between the ends)."""
+    a, b = [float(v) for v in a], [float(v) for v in b]
+    if not all(math.isfinite(v) and abs(v) < RAY_MAX_COORD for v in a + b):
+        return None
+    c, e = [math.floor(v) for v in a], [math.floor(v) for v in b]
+    if sum(abs(e[i] - c[i]) for i in range(3)) > RAY_MAX_MANHATTAN:
+        return None
+    r0, r1, r2 = b[0] - a[0], b[1] - a[1], b[2] - a[2]
+    reach2 = r0 * r0 + r1 * r1 + r2 * r2
+    step, tmax, tstep = [0] * 3, [0.0] * 3, [0.0] * 3
+    for i in range(3):
+        delta = float(e[i] - c[i])      # the integer voxel delta, not the true direction (:89-91)
+        step[i] = (delta > 0) - (delta < 0)
+        tmax[i] = _ray_first_crossing(a[i], delta)
+        tstep[i] = step[i] / delta if delta != 0 else math.nan
+    out = []
+    if step != [0, 0, 0]:
+        for _ in range(RAY_MAX_STEPS):
+            out.append(tuple(c))
+            q0, q1, q2 = c[0] - a[0], c[1] - a[1], c[2] - a[2]
+            if q0 * q0 + q1 * q1 + q2 * q2 > reach2 or c == e:
+                break
+            if tmax[0] < tmax[1]:       # strict '<' tie rules (:139-157)
+                ax = 0 if tmax[0] < tmax[2] else 2
+            else:
+                ax = 1 if tmax[1] < tmax[2] else 2
+            c[ax] += step[ax]
+            tmax[ax] += tstep[ax]
+    if out:
+        out[-1] = tuple(e)
+    else:
+        out = [tuple(e)]
+    return np.array(out, np.int64).reshape(-1, 3)
+
+
+def ray_walks(start, end, resolution):
+    """ray_walk of every ray of an (n, 3) batch in metres: a = start / resolution, b = end / resolution.  A list (None: invalid)."""
+    s = np.ascontiguousarray(start, dtype=np.float64).reshape(-1, 3)
+    t = np.ascontiguousarray(end, dtype=np.float64).reshape(-1, 3)
+    ok = np.isfinite(s).all(1) & np.isfinite(t).all(1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        a, b = s / float(resolution), t / float(resolution)
+    return [ray_walk(a[i], b[i]) if ok[i] else None for i in range(len(s))]
+
+
+def ray_query_model(observed, occupied, origin, resolution, start, end, stop_mask, origin_vox=(0, 0, 0), bounded=True, pos_range=None,
+                    walks=None):
+    """The definition of fiesta_hip_ray_query (include/fiesta_hip.h) in numpy over ray_walk: `observed` / `occupied` are 3-D boolean
+    arrays indexed [x, y, z] whose element (0, 0, 0) is map voxel `origin_vox` (a dense map: download_field's d2 >= 0 and occ; a
+    hash-block map: download_hash scattered into an array), `origin` / `resolution` the map's.  bounded: a voxel outside the array,
+    or whose centre lies outside pos_range = (lo, hi) in metres (PosInMap; a dense map's (origin, origin + map_size), which is also
+    the default with map_size = (origin_vox + shape) * resolution), is OUTSIDE; not bounded: it is UNKNOWN and there is no OUTSIDE.  `walks`: the
+    result of ray_walks for these rays, to share it among calls.  Returns a dict of the six outputs, bit for bit the library's."""
+    obs = np.asarray(observed, dtype=bool)
+    occ = np.asarray(occupied, dtype=bool)
+    res = float(resolution)
+    org = np.asarray(origin, dtype=np.float64).reshape(3)
+    ov = np.asarray(origin_vox, dtype=np.int64).reshape(3)
+    s = np.ascontiguousarray(start, dtype=np.float64).reshape(-1, 3)
+    t = np.ascontiguousarray(end, dtype=np.float64).reshape(-1, 3)
+    stop_mask = int(stop_mask)
+    if len(s) != len(t) or not 0 <= stop_mask <= 7:
+        raise ValueError("start and end need the same length, stop_mask a subset of OCCUPIED | UNKNOWN | OUTSIDE")
+    n = len(s)
+    if walks is None:
+        walks = ray_walks(s, t, res)
+    out = {"n_visited": np.full(n, -1, np.int32), "hit_index": np.full(n, -1, np.int32), "hit_class": np.zeros(n, np.uint8),
+           "hit_vox": np.full((n, 3), RAY_NO_VOXEL, np.int32), "hit_dist": np.full(n, np.nan), "counts": np.zeros((n, 4), np.int32)}
+    valid = np.array([w is not None for w in walks], bool)
+    if not valid.any():
+        return out
+    rays = np.flatnonzero(valid)
+    lens = np.array([len(walks[i]) for i in rays], np.int64)
+    first = np.concatenate([[0], np.cumsum(lens)])               # walk of rays[j]: rows first[j] .. first[j + 1] - 1
+    W = np.concatenate([walks[i] for i in rays])
+    p = (W.astype(np.float64) + 0.5) * res                       # the centres
+    v = np.clip(np.floor((p - org) / res), -(2.0 ** 31 - 1), 2.0 ** 31 - 1).astype(np.int64)   # Pos2Vox, saturated
+    idx = v - ov
+    inside = np.all((idx >= 0) & (idx < np.array(obs.shape)), axis=1)
+    ic = np.where(inside[:, None], idx, 0)
+    o = obs[ic[:, 0], ic[:, 1], ic[:, 2]] & inside
+    cls = np.where(o, np.where(occ[ic[:, 0], ic[:, 1], ic[:, 2]], RAY_OCCUPIED, RAY_FREE), RAY_UNKNOWN)
+    if bounded:
+        lo, hi = (org, org + (ov + np.array(obs.shape)) * res) if pos_range is None else [np.asarray(q, np.float64).reshape(3) for q in pos_range]
+        in_map = ~(np.any(p < lo, axis=1) | np.any(p > hi, axis=1))
+        cls = np.where(in_map & inside, cls, RAY_OUTSIDE)
+    N = len(W)
+    at = np.where((cls & stop_mask) != 0, np.arange(N), N)
+    hit = np.minimum.reduceat(at, first[:-1])                    # row of the first blocking voxel of each walk; >= its end: none
+    has = hit < first[1:]
+    stop = np.where(has, hit, first[1:])                         # the rows before it are counted
+    out["hit_index"][rays] = np.where(has, hit - first[:-1], -1)
+    out["n_visited"][rays] = np.where(has, hit - first[:-1] + 1, lens)
+    h = hit[has]
+    out["hit_class"][rays[has]] = cls[h]
+    out["hit_vox"][rays[has]] = v[h]
+    q = p[h] - s[rays[has]]
+    out["hit_dist"][rays[has]] = np.sqrt(q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2])
+    for k, c in enumerate((RAY_FREE, RAY_OCCUPIED, RAY_UNKNOWN, RAY_OUTSIDE)):
+        cs = np.concatenate([[0], np.cumsum(cls == c)])
+        out["counts"][rays, k] = cs[stop] - cs[first[:-1]]
+    return out
+
+
 class ESDFMap:
     """Drop-in for ``fiesta::ESDFMap``; array mode by default, hash-block mode with ``mode="hash"``."""
 
@@ -223,6 +351,9 @@ class ESDFMap:
         self.mode = mode
         self.resolution = float(resolution)
         self.origin = _d3(origin)
+        # PosInMap's range of an array-mode map as the library adds it up (ray_query_model's pos_range); a shard: the global map's
+        self.pos_range = (self.origin, self.origin + (np.array(global_grid, np.float64) * float(resolution) if shard_lo is not None
+                                                      else _d3(cfg.map_size[:])))
         self._h = C.c_void_p()
         check(self._lib.fiesta_hip_create(C.byref(cfg), C.byref(self._h)))
         gs = np.zeros(3, np.int32)
@@ -521,6 +652,29 @@ class ESDFMap:
         check(self._lib.fiesta_hip_get_frontier_voxels_dev(self._h, _p(blo), _p(bhi), float(min_clearance), C.c_void_p(vox_dev_ptr or None),
                                                            C.c_void_p(mask_dev_ptr or None), int(capacity),
                                                            C.c_void_p(n_out_dev_ptr or None)))
+
+    def RayQuery(self, start, end, stop_mask=7) -> dict:
+        """fiesta_hip_ray_query: per segment start -> end (metres, (n, 3) or one triple) the first voxel of its walk whose class is in
+        `stop_mask` (RAY_OCCUPIED | RAY_UNKNOWN | RAY_OUTSIDE), its index, class, map voxel and distance, the number of voxels visited
+        and the counts of free / occupied / unknown / outside voxels before it -- a dict of numpy arrays named as the fields of
+        fiesta_hip_ray_result; ray_query_model is the definition.  One launch per call: batch the rays."""
+        s = np.ascontiguousarray(start, dtype=np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(end, dtype=np.float64).reshape(-1, 3)
+        if len(s) != len(t):
+            raise ValueError("start and end need the same number of rows")
+        n = len(s)
+        out = {name: np.empty((n,) + shape, dtype) for name, dtype, shape in RAY_FIELDS}
+        res = RayResult(*[out[name].ctypes.data for name, _, _ in RAY_FIELDS])
+        check(self._lib.fiesta_hip_ray_query(self._h, _p(s), _p(t), n, int(stop_mask), C.byref(res)))
+        return out
+
+    def RayQueryDevice(self, start_dev_ptr: int, end_dev_ptr: int, n: int, stop_mask=7, out=None):
+        """fiesta_hip_ray_query_dev: inputs and outputs resident on the device (n x 3 f64 each; `out` maps field names of
+        fiesta_hip_ray_result to device pointers, missing fields are not written); only enqueued on the map's stream"""
+        out = out or {}
+        res = RayResult(*[int(out.get(name, 0)) or None for name, _, _ in RAY_FIELDS])
+        check(self._lib.fiesta_hip_ray_query_dev(self._h, C.c_void_p(start_dev_ptr), C.c_void_p(end_dev_ptr), int(n), int(stop_mask),
+                                                 C.byref(res)))
 
     def count_no_obstacle(self) -> int:
         """Observed voxels whose distance reads +10000 (on grids beyond 1024 per axis this includes everything farther than

@@ -259,6 +259,38 @@ class ESDFMap {
   void GetFrontierVoxels(double min_clearance, std::vector<Eigen::Vector3i> &out, std::vector<uint8_t> *mask = nullptr) {
     FrontierVoxels(nullptr, nullptr, min_clearance, out, mask);
   }
+  // Ray queries (fiesta_hip_ray_query, include/fiesta_hip.h): what a sensor ray from `start` to `end` would cross, read-only.  The
+  // walk is the ray cast's; a voxel is FREE, OCCUPIED, UNKNOWN (never observed) or OUTSIDE (dense maps), and the query stops at
+  // the first voxel whose class is in stop_mask (FIESTA_HIP_RAY_OCCUPIED | _UNKNOWN | _OUTSIDE).  Line of sight through known free
+  // space: stop_mask 7 and no hit; the gain of a view: stop_mask 1, counts[2]; expected depth: stop_mask 1 or 3, hit_dist.
+  // Every call is one kernel launch and one synchronisation, whatever the number of rays: batch them.
+  struct RayHit {
+    int32_t n_visited = -1, hit_index = -1;  // n_visited -1: an invalid ray (non-finite, too far out, more than 4095 voxel steps)
+    uint8_t hit_class = 0;
+    Eigen::Vector3i hit_vox = Eigen::Vector3i(INT32_MIN, INT32_MIN, INT32_MIN);
+    double hit_dist = std::nan("");
+    int32_t counts[4] = {0, 0, 0, 0};        // free, occupied, unknown, outside voxels before the hit
+    bool valid() const { return n_visited >= 0; }
+    bool hit() const { return hit_index >= 0; }
+  };
+  // n rays, start / end n x 3 doubles (metres); `result` (fiesta_hip_ray_result) holds one entry per ray, every pointer nullable
+  void RayQueryBatch(const double *start, const double *end, int64_t n, int32_t stop_mask, const fiesta_hip_ray_result &result) {
+    ck(fiesta_hip_ray_query(h_, start, end, n, stop_mask, &result));
+  }
+  RayHit RayQuery(const Eigen::Vector3d &start, const Eigen::Vector3d &end, int32_t stop_mask) {
+    const double a[3] = {start(0), start(1), start(2)}, b[3] = {end(0), end(1), end(2)};
+    RayHit h;
+    int32_t v[3];
+    const fiesta_hip_ray_result r{&h.n_visited, &h.hit_index, &h.hit_class, v, &h.hit_dist, h.counts};
+    ck(fiesta_hip_ray_query(h_, a, b, 1, stop_mask, &r));
+    h.hit_vox = Eigen::Vector3i(v[0], v[1], v[2]);
+    return h;
+  }
+  // true iff the segment is a valid ray and crosses nothing but voxels observed free (no occupied, unknown or outside voxel)
+  bool IsSegmentFree(const Eigen::Vector3d &a, const Eigen::Vector3d &b) {
+    const RayHit h = RayQuery(a, b, FIESTA_HIP_RAY_OCCUPIED | FIESTA_HIP_RAY_UNKNOWN | FIESTA_HIP_RAY_OUTSIDE);
+    return h.valid() && !h.hit();
+  }
   // The reference's own getters (include/ESDFMap.h:144-145, src/ESDFMap.cpp:544-699).  The message types are template
   // parameters so that this header builds without ROS; sensor_msgs::PointCloud and visualization_msgs::Marker fit as
   // they are (fields used: header.frame_id, points[i].x/y/z, and for the marker id, type, action, scale, pose.orientation,

@@ -130,8 +130,8 @@ typedef struct fiesta_hip_stats {
 
 const char *fiesta_hip_last_error(void);
 /* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev].
- * fiesta_hip_path_cost[_dev] and fiesta_hip_get_frontier_voxels[_dev] came later without a new number: detect them by symbol
- * lookup (dlsym). */
+ * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev] and fiesta_hip_ray_query[_dev] came later without a new number:
+ * detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -437,6 +437,74 @@ int fiesta_hip_get_frontier_voxels(fiesta_hip_map *m, const int32_t lo[3], const
                                    uint8_t *mask, int64_t capacity, int64_t *n_out);
 int fiesta_hip_get_frontier_voxels_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance,
                                        int32_t *vox_dev, uint8_t *mask_dev, int64_t capacity, unsigned long long *n_out_dev);
+
+/* ---- ray queries: what a sensor ray from start to end would cross, read-only and batched ----
+ * Line of sight for path shortcutting and any-angle search (occupied AND unknown must block, which the distance field cannot tell
+ * apart), the information gain of a candidate view (unknown voxels along its rays up to the first obstacle -- the question after
+ * fiesta_hip_get_frontier_voxels), an expected depth image.  Nothing is written to the map.  No reference counterpart as a call;
+ * the traversal is the reference's.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.
+ *
+ * start / end: n x 3 f64, metres.  All arithmetic is f64, in the order written here, every operation rounded once.
+ * The walk W of a ray:
+ *   1. a[c] = start[c] / resolution, b[c] = end[c] / resolution (the operands the ray cast hands to its traversal).
+ *   2. R = the voxel sequence of the reference's Raycast(a, b, min, max) (src/raycast.cpp:56-158; in voxel units, like the output
+ *      of fiesta_hip_raycast_single) with min = -2^31 and max = 2^31 on every axis -- nothing is clipped -- and without its
+ *      1500-voxel exception; its loop runs at most 8192 iterations.
+ *   3. W = R with its LAST element replaced by e = floor(b); R empty (start and end in one voxel): W = [e].
+ *      (The per-frame loop of the ray cast never marks Raycast's last output -- include/Fiesta.h:239 starts one before it -- and
+ *      marks the end point's voxel on its own; that last output is not always e, the traversal can stop one voxel to the side
+ *      through its squared-reach test.  So W is what a ray cast alone in a frame observes: after it, and UpdateOccupancy, no voxel
+ *      of W is unknown, given min_ray_length 0 and a map origin that is a multiple of the resolution.)
+ *   Indices k = 0 .. |W| - 1 run from start to end.
+ * The class of W[k] = r:
+ *   1. centre p[c] = (r[c] + 0.5) * resolution;  2. map voxel v[c] = floor((p[c] - origin[c]) / resolution) (Pos2Vox; saturated
+ *      at +-(2^31 - 1)) -- the arithmetic of the ray cast's visits;
+ *   3. dense map: OUTSIDE if PosInMap(p) is false (p outside [origin, origin + map_size]; a shard: the global map's range) or v is
+ *      not in the map's array (a shard answers for its own array, ghost layers included, like fiesta_hip_get_frontier_voxels);
+ *   4. UNKNOWN if v is not observed: fiesta_hip_download_field's d2 < 0; on a hash-block map a voxel fiesta_hip_download_hash
+ *      lists with d2 < 0 or a voxel of a tile without a page (parked pages answer, as for every query; a hash-block map has no
+ *      OUTSIDE);
+ *   5. else OCCUPIED if Exist(v) (GetOccupancy(v) == 1), else FREE.  UNKNOWN takes precedence over a stale occupancy bit.
+ *   Classes are read from the occupancy state as it stands: UpdateOccupancy changes them, UpdateESDF does not (the distance field
+ *   is never read).
+ * stop_mask: a subset of OCCUPIED | UNKNOWN | OUTSIDE (0..7).  Per ray (every pointer of the result struct is nullable):
+ *   hit_index  the smallest k with class(W[k]) & stop_mask != 0; -1: none
+ *   hit_class  that voxel's class; 0: none
+ *   hit_vox    that voxel's map voxel v; INT32_MIN x 3: none
+ *   hit_dist   q[c] = p[c] - start[c] for that voxel's centre p, sqrt(q0*q0 + q1*q1 + q2*q2) summed left to right; NaN: none
+ *   n_visited  hit_index + 1 with a hit, else |W|
+ *   counts     the numbers of FREE, OCCUPIED, UNKNOWN, OUTSIDE voxels among W[k], k < n_visited, the hit voxel itself not counted
+ *   Every output is an integer or an f64 in a fixed operation order: the same bits for every launch shape, and the bits of
+ *   fiesta_amd.ray_query_model (the definition in numpy) and of the C++ facade.
+ *   Uses: line of sight through known free space -- stop_mask 7, the segment is clear iff hit_index == -1 (and n_visited >= 0);
+ *   the gain of a view -- stop_mask 1 (OCCUPIED), read counts[2]; expected depth -- stop_mask 1 or 3, read hit_dist.
+ * An INVALID ray -- a non-finite component, |a[c]| or |b[c]| >= 2^30, or M = |floor(b)[0] - floor(a)[0]| + |..[1]| + |..[2]| > 4095
+ * -- reads n_visited -1, hit_index -1, hit_class 0, hit_vox INT32_MIN x 3, hit_dist NaN, counts 0; the other rays are unaffected.
+ * (A valid ray's walk has at most M + 1 voxels.)
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): start, end or result NULL, stop_mask outside
+ * 0..7, n negative.  n = 0 does nothing.
+ * fiesta_hip_ray_query      host arrays; stages, runs, synchronises, copies back.
+ * fiesta_hip_ray_query_dev  start_dev / end_dev and the arrays the result struct names are device pointers (the struct itself is a
+ *                           host object); only enqueued on the map's stream (a hash-block map first rebuilds its page table if its
+ *                           page set changed, as every query does).
+ * Both launch one kernel whatever n is: there is no host-cache route, a call with one ray costs a launch (and the host variant a
+ * synchronisation) -- batch the rays of a view or of a search front. */
+#define FIESTA_HIP_RAY_FREE 0
+#define FIESTA_HIP_RAY_OCCUPIED 1
+#define FIESTA_HIP_RAY_UNKNOWN 2
+#define FIESTA_HIP_RAY_OUTSIDE 4
+typedef struct fiesta_hip_ray_result { /* every pointer nullable */
+  int32_t *n_visited;                  /* per ray */
+  int32_t *hit_index;                  /* per ray */
+  uint8_t *hit_class;                  /* per ray */
+  int32_t *hit_vox;                    /* per ray x 3, map voxel coordinates */
+  double *hit_dist;                    /* per ray, metres */
+  int32_t *counts;                     /* per ray x 4: free, occupied, unknown, outside */
+} fiesta_hip_ray_result;
+int fiesta_hip_ray_query(fiesta_hip_map *m, const double *start, const double *end, int64_t n, int32_t stop_mask,
+                         const fiesta_hip_ray_result *result);
+int fiesta_hip_ray_query_dev(fiesta_hip_map *m, const double *start_dev, const double *end_dev, int64_t n, int32_t stop_mask,
+                             const fiesta_hip_ray_result *result);
 
 /* ---- whole-field access (tests, visualisation, checkpoints) ----
  * Dense dump in the reference's linear order; each output is nullable.
