@@ -6,6 +6,7 @@ include/fiesta_hip.h); this package is the thin host-side mirror of the referenc
 from ._lib import FiestaHipError, LIB_PATH, device_count, load  # noqa: F401
 from .esdf_map import (D2_INF, INFINITY, UNDEFINED, ESDFMap, frontier_model, path_cost_model, path_samples, ray_query_model,  # noqa: F401
                        ray_walk, ray_walks, signed_distance)
+from .reach_model import REACH_THROUGH_UNKNOWN, reach_model  # noqa: F401
 
-__all__ = ["ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
+__all__ = ["ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "reach_model", "REACH_THROUGH_UNKNOWN", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
            "D2_INF"]

@@ -85,6 +85,17 @@ class RayResult(C.Structure):
                 ("hit_dist", C.c_void_p), ("counts", C.c_void_p)]
 
 
+class ReachResult(C.Structure):
+    """fiesta_hip_reach_result: one array per output of fiesta_hip_reach_field, every pointer nullable"""
+    _fields_ = [("cost", C.c_void_p), ("target_cost", C.c_void_p)]
+
+
+class ReachInfo(C.Structure):
+    """fiesta_hip_reach_info: the clipped box and the counters of one fiesta_hip_reach_field call"""
+    _fields_ = [("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3), ("n_traversable", C.c_int64), ("n_seeds_used", C.c_int64),
+                ("n_reached", C.c_int64), ("max_cost", C.c_int64), ("rounds", C.c_int64), ("tile_visits", C.c_int64)]
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/fiesta_hip.h declares (used by the CPU export test)."""
     text = open(header_path).read()
@@ -184,6 +195,8 @@ def load():
         "fiesta_hip_get_frontier_voxels_dev": (C.c_int, [vp, vp, vp, dbl, vp, vp, i64, vp]),
         "fiesta_hip_ray_query": (C.c_int, [vp, vp, vp, i64, i32, vp]),
         "fiesta_hip_ray_query_dev": (C.c_int, [vp, vp, vp, i64, i32, vp]),
+        "fiesta_hip_reach_field": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, vp, vp]),
+        "fiesta_hip_reach_field_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, vp, vp]),
         "fiesta_hip_get_occupancy_vox": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_get_occupancy_pos": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_download_field": (C.c_int, [vp, vp, vp, vp, vp]),

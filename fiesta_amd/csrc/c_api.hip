@@ -78,6 +78,22 @@ void ray_args(fiesta_hip_map *m, const double *start, const double *end, int64_t
   need(n >= 0, "ray_query: negative count");
   need(stop_mask >= 0 && stop_mask <= 7, "ray_query: stop_mask must be a subset of OCCUPIED | UNKNOWN | OUTSIDE (0..7)");
 }
+// the whole-call errors of fiesta_hip_reach_field[_dev] (include/fiesta_hip.h) that need no device -- checked before the handle is
+// touched; the clipped box's volume is checked by the map, before anything is launched
+void reach_args(fiesta_hip_map *m, const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets,
+                int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags, const fiesta_hip_reach_result *r) {
+  need(r != nullptr, "reach_field: result is null");
+  need(!std::isnan(min_clearance), "reach_field: min_clearance is NaN");
+  need((lo == nullptr) == (hi == nullptr), "reach_field: lo and hi must both be given or both be null");
+  need(connectivity == 6 || connectivity == 26, "reach_field: connectivity must be 6 or 26");
+  need((flags & ~FIESTA_HIP_REACH_THROUGH_UNKNOWN) == 0, "reach_field: unknown flag bits");
+  need(n_seeds >= 0 && n_targets >= 0, "reach_field: negative count");
+  need(seeds != nullptr || n_seeds == 0, "reach_field: seeds is null");
+  need(targets != nullptr || n_targets == 0, "reach_field: targets is null");
+  need(targets != nullptr || r->target_cost == nullptr, "reach_field: target_cost given without targets");
+  need(m != nullptr, "null map handle");
+  need(m->dense != nullptr || lo != nullptr, "reach_field: a hash-block map has no outside, the box is mandatory");
+}
 }  // namespace
 
 extern "C" {
@@ -522,6 +538,28 @@ int fiesta_hip_ray_query_dev(fiesta_hip_map *m, const double *start_dev, const d
       m->dense->ray_query(start_dev, end_dev, n, stop_mask, *r, true);
     else
       m->hash->ray_query(start_dev, end_dev, n, stop_mask, *r, true);
+  });
+}
+int fiesta_hip_reach_field(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds, int64_t n_seeds,
+                           const int32_t *targets, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
+                           const fiesta_hip_reach_result *result, fiesta_hip_reach_info *info) {
+  return guarded([&] {
+    reach_args(m, lo, hi, seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, result);
+    if (m->dense)
+      m->dense->reach_field(lo, hi, seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, *result, info, false);
+    else
+      m->hash->reach_field(lo, hi, seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, *result, info, false);
+  });
+}
+int fiesta_hip_reach_field_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds_dev, int64_t n_seeds,
+                               const int32_t *targets_dev, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
+                               const fiesta_hip_reach_result *result, fiesta_hip_reach_info *info) {
+  return guarded([&] {
+    reach_args(m, lo, hi, seeds_dev, n_seeds, targets_dev, n_targets, min_clearance, connectivity, flags, result);
+    if (m->dense)
+      m->dense->reach_field(lo, hi, seeds_dev, n_seeds, targets_dev, n_targets, min_clearance, connectivity, flags, *result, info, true);
+    else
+      m->hash->reach_field(lo, hi, seeds_dev, n_seeds, targets_dev, n_targets, min_clearance, connectivity, flags, *result, info, true);
   });
 }
 int fiesta_hip_get_slice(fiesta_hip_map *m, int32_t z_vox, double *out) {

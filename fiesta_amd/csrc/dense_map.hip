@@ -26,6 +26,7 @@
 #include "checkpoint.hpp"
 #include "frontier_kernels.hpp"
 #include "ray_query_kernels.hpp"
+#include "reach_kernels.hpp"
 #include "ft_kernels.hpp"
 #include "nn_kernels.hpp"
 #include "mask_kernels.hpp"
@@ -675,6 +676,25 @@ struct DensePathEval {
 struct DenseFrontierDist {
   Geom g;
   const vox_t *coc;
+  __device__ double operator()(int x, int y, int z) const {
+    FieldWords wd{g, coc};
+    return vox_distance(g, wd, x, y, z);
+  }
+};
+// the map side of the reachability flood (reach_kernels.hpp: k_reach_mask), local array coordinates: 32 voxels of the two bitmaps
+// from any z (two words and a funnel shift when z0 is no multiple of 32; past the array: zero) and the frontier filter's distance
+struct DenseReachSource {
+  Geom g;
+  const uint32_t *obs, *occ;
+  const vox_t *coc;
+  __device__ void row(int x, int y, int z0, uint32_t &o, uint32_t &c) const {
+    const int64_t wi = g.bitword(x, y, z0);
+    const int s = z0 & 31;
+    const uint32_t o0 = obs[wi], c0 = occ[wi];
+    uint32_t o1 = 0, c1 = 0;
+    if (s && (z0 >> 5) + 1 < g.nzw) o1 = obs[wi + 1], c1 = occ[wi + 1];
+    o = reach_funnel(o0, o1, s), c = reach_funnel(c0, c1, s);
+  }
   __device__ double operator()(int x, int y, int z) const {
     FieldWords wd{g, coc};
     return vox_distance(g, wd, x, y, z);
@@ -2693,6 +2713,31 @@ int64_t DenseMap::frontier_voxels(const int32_t *lo, const int32_t *hi, double m
   if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(mask, dmask, k, hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
+}
+
+// fiesta_hip_reach_field[_dev] (reach_kernels.hpp); arguments checked by the caller.  The box in local array coordinates,
+// intersected with the array; the padding bits of a row's last bitmap word lie past the clipped box and are masked there.
+void DenseMap::reach_field(const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets, int64_t n_targets,
+                           double min_clearance, int connectivity, int flags, const fiesta_hip_reach_result &r, fiesta_hip_reach_info *info,
+                           bool dev) {
+  use_device();
+  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0}, dims[3] = {g_.nx, g_.ny, g_.nz};
+  int64_t blo[3], bhi[3];
+  bool empty = false;
+  for (int c = 0; c < 3; ++c) {
+    blo[c] = lo ? std::max<int64_t>((int64_t)lo[c] - g0[c], 0) : 0;
+    bhi[c] = hi ? std::min<int64_t>((int64_t)hi[c] - g0[c], dims[c] - 1) : dims[c] - 1;
+    empty = empty || blo[c] > bhi[c];
+  }
+  if (empty) blo[0] = 1, bhi[0] = 0;
+  if (!empty && (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * (bhi[2] - blo[2] + 1) > kReachMaxVoxels)  // (before anything is launched)
+    throw Error(FIESTA_HIP_ERR_INVALID, "reach_field: the clipped box holds more than 2^28 voxels");
+  if (!empty && g_.sharded) {  // (the halo exchange does not keep obsbits_ in ghost cells: see frontier_voxels)
+    hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
+    FIESTA_HIP_CHECK(hipGetLastError());
+  }
+  reach_run(stream_, reach_, path_in_, path_out_, DenseReachSource{g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, (const vox_t *)coc_}, blo,
+            bhi, g0, ReachArgs{seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, &r, info, dev});
 }
 
 // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller

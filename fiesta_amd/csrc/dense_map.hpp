@@ -47,6 +47,14 @@ struct DevBuf {
   }
 };
 
+// scratch of fiesta_hip_reach_field (reach_kernels.hpp), owned by a map: the box's traversability bitmap, tile flags and lists of
+// both round parities, the counters, and a cost field for calls that pass none; allocated on first use, freed with the map
+struct ReachScratch {
+  DevBuf<uint32_t> bits, flags, lists;
+  DevBuf<int32_t> cost;
+  DevBuf<unsigned long long> ctr;
+};
+
 // Device-side counters, one 64-bit word each.
 enum Counter {
   C_TOUCHED = 0,   // length of the touched-voxel list (the reference's occupancy_queue_)
@@ -158,6 +166,9 @@ class DenseMap {
                           unsigned long long *n_out_dev, bool dev);
   // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller
   void ray_query(const double *start, const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev);
+  // fiesta_hip_reach_field[_dev] (reach_kernels.hpp); arguments checked by the caller
+  void reach_field(const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets, int64_t n_targets,
+                   double min_clearance, int connectivity, int flags, const fiesta_hip_reach_result &r, fiesta_hip_reach_info *info, bool dev);
   int64_t count_no_obstacle();
   void slice_distances(int z_vox, double *out);        // nx * ny doubles, x-major
   // GetPointCloud / GetSliceMarker as arrays; both return the total count (may exceed cap), order unspecified
@@ -339,6 +350,7 @@ class DenseMap {
   // staging
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_;
   DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path and ray queries: staged inputs, plan / piece records, staged outputs
+  ReachScratch reach_;
   // raycast front-end state (per-frame stamp arrays = Fiesta::set_occ_/set_free_, include/Fiesta.h:107-110;
   // per-ray traversal lists), lazily allocated by raycast.hip
   struct RaycastState;

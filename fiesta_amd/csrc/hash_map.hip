@@ -21,6 +21,7 @@
 #include "path_cost_kernels.hpp"
 #include "frontier_kernels.hpp"
 #include "ray_query_kernels.hpp"
+#include "reach_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
@@ -503,6 +504,33 @@ struct HashFrontierPages {
   PageTable tab;
   const vox_t *coc;
   __device__ int64_t addr(int vx, int vy, int vz) const { return h_lookup(g, dir, tab, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
+  __device__ double operator()(int vx, int vy, int vz) const { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
+};
+// the map side of the reachability flood (reach_kernels.hpp: k_reach_mask), MAP voxel coordinates: 32 voxels from any z are the
+// rows of one or two tiles, each found by the queries' map-wide lookup (parked pages answer; no page: all unknown), its observed
+// bits gathered from the page's field words; the frontier filter's distance is GetDistance(Vector3i)
+struct HashReachSource {
+  Geom g;
+  const int32_t *dir;
+  PageTable tab;
+  const vox_t *coc;
+  const uint32_t *occbits;
+  __device__ void tile_row(int vx, int vy, int vz, uint32_t &o, uint32_t &c) const {  // vz: a multiple of 32
+    constexpr int kFar = 1 << 24;  // (pages lie within +-2^24 voxels of the map origin: tile_key)
+    o = c = 0u;
+    if (vx < -kFar || vx >= kFar || vy < -kFar || vy >= kFar || vz < -kFar || vz >= kFar) return;
+    const int64_t a = h_lookup(g, dir, tab, vx - g.gx0, vy - g.gy0, vz - g.gz0);
+    if (a < 0) return;
+    for (int k = 0; k < 32; ++k) o |= (uint32_t)(coc[a + k] != kUnobserved) << k;
+    c = occbits[a >> 5];
+  }
+  __device__ void row(int vx, int vy, int vz0, uint32_t &o, uint32_t &c) const {
+    const int s = vz0 & 31;
+    uint32_t o0, c0, o1 = 0, c1 = 0;
+    tile_row(vx, vy, vz0 - s, o0, c0);
+    if (s) tile_row(vx, vy, vz0 - s + 32, o1, c1);
+    o = reach_funnel(o0, o1, s), c = reach_funnel(c0, c1, s);
+  }
   __device__ double operator()(int vx, int vy, int vz) const { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
 };
 // the voxel source of the ray query (ray_query_kernels.hpp): the queries' lookup once per TILE -- the page address of the tile the
@@ -1626,6 +1654,29 @@ int64_t HashMap::frontier_voxels(const int32_t *lo, const int32_t *hi, double mi
   if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(mask, dmask, k, hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
+}
+
+// fiesta_hip_reach_field[_dev] (reach_kernels.hpp); arguments checked by the caller.  The map has no outside: the box is taken as
+// given (clamped like the frontier call's); every page answers, resident or parked, and a tile without a page is unknown.
+void HashMap::reach_field(const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets, int64_t n_targets,
+                          double min_clearance, int connectivity, int flags, const fiesta_hip_reach_result &r, fiesta_hip_reach_info *info,
+                          bool dev) {
+  use_device();
+  auto c = [](int64_t v) { return std::min<int64_t>(std::max<int64_t>(v, -(1ll << 30)), 1ll << 30); };
+  int64_t blo[3], bhi[3];
+  bool empty = false;
+  for (int k = 0; k < 3; ++k) blo[k] = c(lo[k]), bhi[k] = c(hi[k]), empty = empty || blo[k] > bhi[k];
+  if (empty) blo[0] = 1, bhi[0] = 0;
+  if (!empty) {  // (before anything is launched; each extent is below 2^32)
+    const int64_t ex = bhi[0] - blo[0] + 1, ey = bhi[1] - blo[1] + 1, ez = bhi[2] - blo[2] + 1;
+    if (ex > kReachMaxVoxels || ey > kReachMaxVoxels || ex * ey > kReachMaxVoxels || ex * ey * ez > kReachMaxVoxels)
+      throw Error(FIESTA_HIP_ERR_INVALID, "reach_field: the box holds more than 2^28 voxels");
+  }
+  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
+  const int off[3] = {0, 0, 0};
+  reach_run(stream_, reach_, path_in_, path_out_,
+            HashReachSource{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p}, blo, bhi, off,
+            ReachArgs{seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, &r, info, dev});
 }
 
 // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller.  Every page answers, resident or parked.

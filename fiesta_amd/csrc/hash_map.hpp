@@ -95,6 +95,9 @@ class HashMap {
                           unsigned long long *n_out_dev, bool dev);
   // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller
   void ray_query(const double *start, const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev);
+  // fiesta_hip_reach_field[_dev] (reach_kernels.hpp); arguments checked by the caller (lo / hi are not null here)
+  void reach_field(const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets, int64_t n_targets,
+                   double min_clearance, int connectivity, int flags, const fiesta_hip_reach_result &r, fiesta_hip_reach_info *info, bool dev);
   void synchronize();
 
  private:
@@ -176,6 +179,7 @@ class HashMap {
   unsigned long long *counters_ = nullptr, *h_counters_ = nullptr;
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_, stage_d_;
   DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path and ray queries: staged inputs, plan / piece records, staged outputs
+  ReachScratch reach_;
 };
 
 void raycast_single(const double *start, const double *end, const double *minv, const double *maxv, double *out,

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, Stats, check
+from ._lib import Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachResult, Stats, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -675,6 +675,76 @@ class ESDFMap:
         res = RayResult(*[int(out.get(name, 0)) or None for name, _, _ in RAY_FIELDS])
         check(self._lib.fiesta_hip_ray_query_dev(self._h, C.c_void_p(start_dev_ptr), C.c_void_p(end_dev_ptr), int(n), int(stop_mask),
                                                  C.byref(res)))
+
+    @staticmethod
+    def _reach_info(info) -> dict:
+        d = {k: getattr(info, k) for k, _ in ReachInfo._fields_}
+        d["box_lo"], d["box_hi"] = list(info.box_lo), list(info.box_hi)
+        return d
+
+    def ReachField(self, seeds, lo=None, hi=None, targets=None, min_clearance=0.0, connectivity=26, flags=0, want_cost=True) -> dict:
+        """fiesta_hip_reach_field: the cost-to-go field of the inclusive map-voxel box [lo, hi] (both None: a dense map's whole array)
+        flooded from `seeds` ((n, 3) map voxels) through the traversable voxels -- observed free, with GetDistance >= min_clearance if
+        that is > 0, and with flags = REACH_THROUGH_UNKNOWN the never-observed ones too -- by moves of weight 3 / 4 / 5 (connectivity 6:
+        only 3).  Returns the fields of fiesta_hip_reach_info plus cost ((ex, ey, ez) int32 over the clipped box: -1 not traversable,
+        2^31 - 1 not reached; None without want_cost) and, with `targets`, target_cost ((n,) int32; -1 outside the box);
+        fiesta_amd.reach_model is the definition"""
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        blo = None if lo is None else np.ascontiguousarray(lo, np.int32).reshape(3)
+        bhi = None if hi is None else np.ascontiguousarray(hi, np.int32).reshape(3)
+        s = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
+        t = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32).reshape(-1, 3)
+        nt = 0 if t is None else len(t)
+        tc = None if t is None else np.empty(nt, np.int32)
+        info = ReachInfo()
+        args = (_p(blo), _p(bhi), _p(s) if len(s) else None, len(s), _p(t) if nt else None, nt, float(min_clearance), int(connectivity),
+                int(flags))
+        cost = None
+        if want_cost:
+            cost = np.empty(self._reach_extents(blo, bhi), np.int32)   # (the clipped box decides the size of the field)
+        res = ReachResult(cost.ctypes.data if cost is not None and cost.size else None, tc.ctypes.data if nt else None)
+        check(self._lib.fiesta_hip_reach_field(self._h, *args, C.byref(res), C.byref(info)))
+        out = self._reach_info(info)
+        out["cost"] = cost
+        if t is not None:
+            out["target_cost"] = tc
+        return out
+
+    def _reach_extents(self, blo, bhi):
+        """extents of the box a reach call clips [blo, bhi] to (host arithmetic, the library's rule)"""
+        if self.mode != "array":
+            if blo is None:
+                raise ValueError("a hash-block map has no outside: the box is mandatory")
+            a, b = np.clip(blo.astype(np.int64), -2 ** 30, 2 ** 30), np.clip(bhi.astype(np.int64), -2 ** 30, 2 ** 30)
+        else:
+            org = self._array_origin()
+            dims = np.array(self.grid_size, np.int64)
+            a = np.zeros(3, np.int64) if blo is None else np.maximum(blo.astype(np.int64) - org, 0)
+            b = dims - 1 if bhi is None else np.minimum(bhi.astype(np.int64) - org, dims - 1)
+        if np.any(a > b):
+            return (0, 0, 0)
+        return tuple(int(v) for v in b - a + 1)
+
+    def _array_origin(self):
+        """map voxel of element (0, 0, 0) of an array-mode map's array (non-zero on a shard)"""
+        info = _lib.ShardInfo()
+        check(self._lib.fiesta_hip_shard_info_get(self._h, C.byref(info)))
+        return np.array(list(info.local_origin), np.int64)
+
+    def ReachFieldDevice(self, seeds_dev_ptr: int, n_seeds: int, lo=None, hi=None, targets_dev_ptr: int = 0, n_targets: int = 0,
+                         min_clearance=0.0, connectivity=26, flags=0, cost_dev_ptr: int = 0, target_cost_dev_ptr: int = 0) -> dict:
+        """fiesta_hip_reach_field_dev: seeds, targets, cost and target_cost resident on the device (0: not given / not written; the
+        cost field needs ex * ey * ez int32 of the clipped box); returns the fields of fiesta_hip_reach_info.  Synchronises with the
+        map's stream, unlike the other device calls"""
+        blo = None if lo is None else np.ascontiguousarray(lo, np.int32).reshape(3)
+        bhi = None if hi is None else np.ascontiguousarray(hi, np.int32).reshape(3)
+        info = ReachInfo()
+        res = ReachResult(int(cost_dev_ptr) or None, int(target_cost_dev_ptr) or None)
+        check(self._lib.fiesta_hip_reach_field_dev(self._h, _p(blo), _p(bhi), C.c_void_p(seeds_dev_ptr or None), int(n_seeds),
+                                                   C.c_void_p(targets_dev_ptr or None), int(n_targets), float(min_clearance),
+                                                   int(connectivity), int(flags), C.byref(res), C.byref(info)))
+        return self._reach_info(info)
 
     def count_no_obstacle(self) -> int:
         """Observed voxels whose distance reads +10000 (on grids beyond 1024 per axis this includes everything farther than

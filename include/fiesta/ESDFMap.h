@@ -291,6 +291,37 @@ class ESDFMap {
     const RayHit h = RayQuery(a, b, FIESTA_HIP_RAY_OCCUPIED | FIESTA_HIP_RAY_UNKNOWN | FIESTA_HIP_RAY_OUTSIDE);
     return h.valid() && !h.hit();
   }
+  // Reachability (fiesta_hip_reach_field, include/fiesta_hip.h): the travel cost from `seeds` through the traversable voxels of the
+  // inclusive voxel box [lo, hi] (both null: a dense map's whole array) -- observed free, with GetDistance >= min_clearance if that
+  // is > 0, with flags = FIESTA_HIP_REACH_THROUGH_UNKNOWN the never-observed ones too -- by moves of weight 3 / 4 / 5 (connectivity
+  // 26; 6: only 3), so metres ~ cost * resolution / 3.  target_cost (nullable) receives one cost per target: -1 not traversable or
+  // outside the box, INT32_MAX traversable and out of reach.  cost (nullable) receives the whole field of the clipped box, x-major,
+  // z fastest, from info.box_lo.  The frontier call's voxels are the usual targets: which of them can the robot reach, and how far?
+  fiesta_hip_reach_info ReachField(const Eigen::Vector3i *lo, const Eigen::Vector3i *hi, const std::vector<Eigen::Vector3i> &seeds,
+                                   const std::vector<Eigen::Vector3i> &targets, double min_clearance, int32_t connectivity, int32_t flags,
+                                   std::vector<int32_t> *target_cost, std::vector<int32_t> *cost = nullptr) {
+    Flush();
+    if ((lo == nullptr) != (hi == nullptr)) throw std::invalid_argument("ReachField: lo and hi must both be given or both be null");
+    int32_t a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
+    int64_t nvox = 1;  // of the box as the library clips it (a dense map: its array; a hash-block map: +-2^30)
+    for (int c = 0; c < 3; ++c) {
+      if (lo) a[c] = (*lo)(c), b[c] = (*hi)(c);
+      const int64_t l = hash_ ? std::max<int64_t>(a[c], -(1ll << 30)) : (lo ? std::max<int64_t>(a[c], 0) : 0);
+      const int64_t h = hash_ ? std::min<int64_t>(b[c], 1ll << 30) : (lo ? std::min<int64_t>(b[c], gs_[c] - 1) : gs_[c] - 1);
+      nvox = (l > h || nvox == 0) ? 0 : std::min<int64_t>(nvox * (h - l + 1), (1ll << 28) + 1);
+    }
+    std::vector<int32_t> sv, tv;
+    for (const auto &v : seeds) sv.insert(sv.end(), {v(0), v(1), v(2)});
+    for (const auto &v : targets) tv.insert(tv.end(), {v(0), v(1), v(2)});
+    if (target_cost) target_cost->assign(targets.size(), -1);
+    if (cost) cost->assign(nvox <= (1ll << 28) ? (size_t)nvox : 0, -1);
+    const fiesta_hip_reach_result r{cost && !cost->empty() ? cost->data() : nullptr,
+                                    target_cost && !targets.empty() ? target_cost->data() : nullptr};
+    fiesta_hip_reach_info info{};
+    ck(fiesta_hip_reach_field(h_, lo ? a : nullptr, lo ? b : nullptr, sv.empty() ? nullptr : sv.data(), (int64_t)seeds.size(),
+                              tv.empty() ? nullptr : tv.data(), (int64_t)targets.size(), min_clearance, connectivity, flags, &r, &info));
+    return info;
+  }
   // The reference's own getters (include/ESDFMap.h:144-145, src/ESDFMap.cpp:544-699).  The message types are template
   // parameters so that this header builds without ROS; sensor_msgs::PointCloud and visualization_msgs::Marker fit as
   // they are (fields used: header.frame_id, points[i].x/y/z, and for the marker id, type, action, scale, pose.orientation,

@@ -130,8 +130,8 @@ typedef struct fiesta_hip_stats {
 
 const char *fiesta_hip_last_error(void);
 /* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev].
- * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev] and fiesta_hip_ray_query[_dev] came later without a new number:
- * detect them by symbol lookup (dlsym). */
+ * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev], fiesta_hip_ray_query[_dev] and fiesta_hip_reach_field[_dev] came
+ * later without a new number: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -505,6 +505,74 @@ int fiesta_hip_ray_query(fiesta_hip_map *m, const double *start, const double *e
                          const fiesta_hip_ray_result *result);
 int fiesta_hip_ray_query_dev(fiesta_hip_map *m, const double *start_dev, const double *end_dev, int64_t n, int32_t stop_mask,
                              const fiesta_hip_ray_result *result);
+
+/* ---- reachability: the cost-to-go field through traversable space, flooded on the device ----
+ * The second half of the frontier question: WHICH of those places can the robot reach, and how far is it?  A clearance per voxel is
+ * a local test -- a frontier voxel behind a wall, in a pocket seen through a window or behind a door narrower than the robot passes
+ * it.  This call floods the traversable voxels of a box from seed voxels and reports the travel cost of every voxel and of a list
+ * of targets (e.g. the frontier call's output).  Read-only; no reference counterpart.  fiesta_hip_version() is still 101: detect
+ * these two calls by symbol lookup.
+ * The box: lo / hi are HOST pointers in both variants, an inclusive voxel box in map voxel coordinates (those
+ *   fiesta_hip_get_frontier_voxels reports).  It is intersected with a dense map's array (a map created as a shard answers for its
+ *   own array, like the frontier call; there is no shard-group call); both NULL: the whole array.  A hash-block map has no outside:
+ *   there the box is mandatory (both NULL is an error) and only clamped to +-2^30 per coordinate.  With extents ex, ey, ez the
+ *   clipped box must satisfy ex * ey * ez <= 2^28.  An empty intersection, or lo[c] > hi[c], is no error: *info reads all zero and
+ *   the target costs read -1.
+ * traversable(v), for v inside the clipped box: either
+ *   - free(v) exactly as the frontier call defines it (observed and not Exist) and -- only if min_clearance > 0 --
+ *     GetDistance(Vector3i v) >= min_clearance with the voxel query's own f64 value (+10000 passes); or
+ *   - flags & FIESTA_HIP_REACH_THROUGH_UNKNOWN and v is not observed (optimistic planning; no clearance test on such a voxel; a
+ *     tile without a page on a hash-block map is unknown).
+ *   A voxel outside the clipped box is not traversable.  With min_clearance <= 0 the distance field is not read at all.  The map is
+ *   read as it stands: after UpdateOccupancy and before UpdateESDF the clearance filter sees the old distances.
+ * Moves: between two traversable voxels that differ by at most 1 per axis; a move that changes 1, 2 or 3 axes weighs 3, 4 or 5 (the
+ *   3-4-5 chamfer), so costs are integers in units of a third of a voxel: metres ~ cost * resolution / 3.  connectivity 6 allows
+ *   only the weight-3 moves, 26 all of them.  A diagonal move needs only its two ends traversable (ask with 6, or with a clearance,
+ *   for no corner cutting).
+ * Seeds: n_seeds x 3 int32 map voxels; a seed outside the clipped box or not traversable is ignored.  n_seeds = 0 or no usable
+ *   seed is no error: nothing is reached.
+ * cost(v), per voxel of the clipped box: the minimum total weight over all move sequences from any usable seed to v; INT32_MAX if
+ *   v is traversable and there is none; -1 if v is not traversable.  This is the fixed point of a shortest-path relaxation on
+ *   integer weights: it is unique, so every output is exact and the same bits for any launch shape and scheduling, and the bits of
+ *   fiesta_amd.reach_model (the definition in numpy).
+ * Outputs; every pointer of the result struct is nullable (the struct itself is not):
+ *   cost         int32, ex * ey * ez entries in box-local linear order ((x - lo'x) * ey + (y - lo'y)) * ez + (z - lo'z), lo' the
+ *                clipped corner (info->box_lo)
+ *   target_cost  int32 per target (targets: n_targets x 3 map voxels): cost(v), or -1 for a target outside the clipped box
+ * info (a HOST struct in both variants, nullable): the clipped box, the number of traversable voxels, of usable seed entries (a
+ *   voxel listed twice counts twice), of traversable voxels with a finite cost, the largest finite cost (0: nothing reached), and
+ *   how the flood ran: rounds (launches that found work) and tile visits (16 x 16 x 32-voxel tiles of the box relaxed, over all rounds).
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): min_clearance is NaN, exactly one of lo / hi
+ *   is NULL, both NULL on a hash-block map, a clipped box above 2^28 voxels, connectivity other than 6 or 26, unknown flag bits, a
+ *   negative count, seeds NULL with n_seeds > 0, targets NULL with n_targets > 0, target_cost given without targets, result NULL.
+ *   The flood's scratch memory (the box's bitmap, tile flags and lists, a cost field when the caller passes none) belongs to the
+ *   map: allocated on first use, grown as needed, freed by fiesta_hip_destroy; a failed allocation is FIESTA_HIP_ERR_NOMEM and leaves
+ *   the map usable.  FIESTA_HIP_ERR_STATE: the flood ran more rounds than there are traversable voxels (a defect, never expected).
+ * fiesta_hip_reach_field      host arrays; stages, runs, synchronises, copies back.
+ * fiesta_hip_reach_field_dev  seeds / targets and the arrays the result struct names are device pointers.  UNLIKE the other _dev
+ *                             calls this one synchronises with the map's stream: the number of rounds depends on the data, so
+ *                             the call reads a small counter block after every batch of eight rounds (a hash-block map first
+ *                             rebuilds its page table if its page set changed, as every query does). */
+#define FIESTA_HIP_REACH_THROUGH_UNKNOWN 1
+typedef struct fiesta_hip_reach_result { /* every pointer nullable */
+  int32_t *cost;                         /* ex * ey * ez, box-local order */
+  int32_t *target_cost;                  /* per target */
+} fiesta_hip_reach_result;
+typedef struct fiesta_hip_reach_info {
+  int32_t box_lo[3], box_hi[3]; /* the clipped box, map voxel coordinates, inclusive */
+  int64_t n_traversable;
+  int64_t n_seeds_used;
+  int64_t n_reached;
+  int64_t max_cost;
+  int64_t rounds;
+  int64_t tile_visits;
+} fiesta_hip_reach_info;
+int fiesta_hip_reach_field(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds, int64_t n_seeds,
+                           const int32_t *targets, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
+                           const fiesta_hip_reach_result *result, fiesta_hip_reach_info *info);
+int fiesta_hip_reach_field_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds_dev, int64_t n_seeds,
+                               const int32_t *targets_dev, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
+                               const fiesta_hip_reach_result *result, fiesta_hip_reach_info *info);
 
 /* ---- whole-field access (tests, visualisation, checkpoints) ----
  * Dense dump in the reference's linear order; each output is nullable.
