@@ -96,6 +96,12 @@ class ReachInfo(C.Structure):
                 ("n_reached", C.c_int64), ("max_cost", C.c_int64), ("rounds", C.c_int64), ("tile_visits", C.c_int64)]
 
 
+class ReachPathsResult(C.Structure):
+    """fiesta_hip_reach_paths_result: offsets is required, every other pointer nullable"""
+    _fields_ = [("offsets", C.c_void_p), ("waypoints_vox", C.c_void_p), ("waypoints_pos", C.c_void_p), ("status", C.c_void_p),
+                ("n_moves", C.c_void_p)]
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/fiesta_hip.h declares (used by the CPU export test)."""
     text = open(header_path).read()
@@ -197,6 +203,8 @@ def load():
         "fiesta_hip_ray_query_dev": (C.c_int, [vp, vp, vp, i64, i32, vp]),
         "fiesta_hip_reach_field": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, vp, vp]),
         "fiesta_hip_reach_field_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, vp, vp]),
+        "fiesta_hip_reach_paths": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
+        "fiesta_hip_reach_paths_dev": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
         "fiesta_hip_get_occupancy_vox": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_get_occupancy_pos": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_download_field": (C.c_int, [vp, vp, vp, vp, vp]),

@@ -1,6 +1,7 @@
 // fiesta_amd/csrc/c_api.hip -- the extern "C" boundary declared in include/fiesta_hip.h.
 // Every entry point converts C++ exceptions into a status code + thread-local message; nothing throws
 // across the ABI and no HIP / C++ type appears in a signature.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -93,6 +94,30 @@ void reach_args(fiesta_hip_map *m, const int32_t *lo, const int32_t *hi, const i
   need(targets != nullptr || r->target_cost == nullptr, "reach_field: target_cost given without targets");
   need(m != nullptr, "null map handle");
   need(m->dense != nullptr || lo != nullptr, "reach_field: a hash-block map has no outside, the box is mandatory");
+}
+// the whole-call errors of fiesta_hip_reach_paths[_dev] (include/fiesta_hip.h); none of them needs a device, and all but the last
+// are checked before the handle is touched
+void reach_paths_args(fiesta_hip_map *m, const int32_t *cost, const int32_t *lo, const int32_t *hi, const int32_t *targets, int64_t n_targets,
+                      int32_t connectivity, int32_t flags, int32_t max_span, int64_t capacity, const fiesta_hip_reach_paths_result *r) {
+  need(r != nullptr, "reach_paths: result is null");
+  need(r->offsets != nullptr, "reach_paths: result->offsets is null");
+  need(connectivity == 6 || connectivity == 26, "reach_paths: connectivity must be 6 or 26");
+  need((flags & ~FIESTA_HIP_REACH_PATHS_SHORTCUT) == 0, "reach_paths: unknown flag bits");
+  need(!(flags & FIESTA_HIP_REACH_PATHS_SHORTCUT) || max_span >= 1, "reach_paths: max_span must be >= 1 with SHORTCUT");
+  need(n_targets >= 0, "reach_paths: negative count");
+  need(capacity >= 0, "reach_paths: negative capacity");
+  need(targets != nullptr || n_targets == 0, "reach_paths: targets is null");
+  need((cost == nullptr) == (lo == nullptr) && (lo == nullptr) == (hi == nullptr),
+       "reach_paths: cost, box_lo and box_hi must all be given or all be null");
+  if (cost) {
+    int64_t nvox = 1;
+    for (int c = 0; c < 3; ++c) {
+      need(lo[c] <= hi[c], "reach_paths: the box is empty (box_lo > box_hi)");
+      nvox *= std::min<int64_t>((int64_t)hi[c] - lo[c] + 1, (1ll << 28) + 1);  // (three factors of at most 2^28 + 1 would overflow:
+      need(nvox <= (1ll << 28), "reach_paths: the box holds more than 2^28 voxels");  //  checked after every factor)
+    }
+  }
+  need(m != nullptr, "null map handle");
 }
 }  // namespace
 
@@ -560,6 +585,28 @@ int fiesta_hip_reach_field_dev(fiesta_hip_map *m, const int32_t lo[3], const int
       m->dense->reach_field(lo, hi, seeds_dev, n_seeds, targets_dev, n_targets, min_clearance, connectivity, flags, *result, info, true);
     else
       m->hash->reach_field(lo, hi, seeds_dev, n_seeds, targets_dev, n_targets, min_clearance, connectivity, flags, *result, info, true);
+  });
+}
+int fiesta_hip_reach_paths(fiesta_hip_map *m, const int32_t *cost, const int32_t box_lo[3], const int32_t box_hi[3], const int32_t *targets,
+                           int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span, int64_t capacity,
+                           const fiesta_hip_reach_paths_result *result) {
+  return guarded([&] {
+    reach_paths_args(m, cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, result);
+    if (m->dense)
+      m->dense->reach_paths(cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, *result, false);
+    else
+      m->hash->reach_paths(cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, *result, false);
+  });
+}
+int fiesta_hip_reach_paths_dev(fiesta_hip_map *m, const int32_t *cost_dev, const int32_t box_lo[3], const int32_t box_hi[3],
+                               const int32_t *targets_dev, int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span,
+                               int64_t capacity, const fiesta_hip_reach_paths_result *result) {
+  return guarded([&] {
+    reach_paths_args(m, cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, result);
+    if (m->dense)
+      m->dense->reach_paths(cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, *result, true);
+    else
+      m->hash->reach_paths(cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, *result, true);
   });
 }
 int fiesta_hip_get_slice(fiesta_hip_map *m, int32_t z_vox, double *out) {

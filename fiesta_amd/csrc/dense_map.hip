@@ -27,6 +27,7 @@
 #include "frontier_kernels.hpp"
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
+#include "reach_path_kernels.hpp"
 #include "ft_kernels.hpp"
 #include "nn_kernels.hpp"
 #include "mask_kernels.hpp"
@@ -2738,6 +2739,15 @@ void DenseMap::reach_field(const int32_t *lo, const int32_t *hi, const int32_t *
   }
   reach_run(stream_, reach_, path_in_, path_out_, DenseReachSource{g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, (const vox_t *)coc_}, blo,
             bhi, g0, ReachArgs{seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, &r, info, dev});
+}
+
+// fiesta_hip_reach_paths[_dev] (reach_path_kernels.hpp); arguments checked by the caller.  Nothing of the map is read but its
+// resolution and origin, and the cost field the reachability scratch retains (or the caller's).
+void DenseMap::reach_paths(const int32_t *cost, const int32_t *box_lo, const int32_t *box_hi, const int32_t *targets, int64_t n_targets,
+                      int connectivity, int flags, int max_span, int64_t capacity, const fiesta_hip_reach_paths_result &r, bool dev) {
+  use_device();
+  reach_paths_run(stream_, reach_, path_in_, path_out_, g_.res, g_.org,
+                  ReachPathArgs{cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, &r, dev});
 }
 
 // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller

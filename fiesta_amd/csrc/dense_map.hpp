@@ -48,11 +48,17 @@ struct DevBuf {
 };
 
 // scratch of fiesta_hip_reach_field (reach_kernels.hpp), owned by a map: the box's traversability bitmap, tile flags and lists of
-// both round parities, the counters, and a cost field for calls that pass none; allocated on first use, freed with the map
+// both round parities, the counters, and a cost field for calls that pass none; allocated on first use, freed with the map.
+// field_*: what `cost` holds for fiesta_hip_reach_paths (reach_path_kernels.hpp) -- the RETAINED field: valid after a reach_field
+// call that finished with its cost field in this scratch, or after a reach_paths host call uploaded one; its inclusive box in map
+// voxel coordinates and the connectivity it was flooded with
 struct ReachScratch {
   DevBuf<uint32_t> bits, flags, lists;
   DevBuf<int32_t> cost;
   DevBuf<unsigned long long> ctr;
+  bool field_valid = false;
+  int32_t field_lo[3] = {0, 0, 0}, field_hi[3] = {0, 0, 0};
+  int field_connectivity = 0;
 };
 
 // Device-side counters, one 64-bit word each.
@@ -169,6 +175,9 @@ class DenseMap {
   // fiesta_hip_reach_field[_dev] (reach_kernels.hpp); arguments checked by the caller
   void reach_field(const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets, int64_t n_targets,
                    double min_clearance, int connectivity, int flags, const fiesta_hip_reach_result &r, fiesta_hip_reach_info *info, bool dev);
+  // fiesta_hip_reach_paths[_dev] (reach_path_kernels.hpp); arguments checked by the caller
+  void reach_paths(const int32_t *cost, const int32_t *box_lo, const int32_t *box_hi, const int32_t *targets, int64_t n_targets, int connectivity,
+                   int flags, int max_span, int64_t capacity, const fiesta_hip_reach_paths_result &r, bool dev);
   int64_t count_no_obstacle();
   void slice_distances(int z_vox, double *out);        // nx * ny doubles, x-major
   // GetPointCloud / GetSliceMarker as arrays; both return the total count (may exceed cap), order unspecified

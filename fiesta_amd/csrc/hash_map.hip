@@ -22,6 +22,7 @@
 #include "frontier_kernels.hpp"
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
+#include "reach_path_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
@@ -1677,6 +1678,15 @@ void HashMap::reach_field(const int32_t *lo, const int32_t *hi, const int32_t *s
   reach_run(stream_, reach_, path_in_, path_out_,
             HashReachSource{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p}, blo, bhi, off,
             ReachArgs{seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, &r, info, dev});
+}
+
+// fiesta_hip_reach_paths[_dev] (reach_path_kernels.hpp); arguments checked by the caller.  Nothing of the map is read but its
+// resolution and origin, and the cost field the reachability scratch retains (or the caller's).
+void HashMap::reach_paths(const int32_t *cost, const int32_t *box_lo, const int32_t *box_hi, const int32_t *targets, int64_t n_targets,
+                     int connectivity, int flags, int max_span, int64_t capacity, const fiesta_hip_reach_paths_result &r, bool dev) {
+  use_device();
+  reach_paths_run(stream_, reach_, path_in_, path_out_, g_.res, g_.org,
+                  ReachPathArgs{cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, &r, dev});
 }
 
 // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller.  Every page answers, resident or parked.

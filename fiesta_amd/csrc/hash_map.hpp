@@ -98,6 +98,9 @@ class HashMap {
   // fiesta_hip_reach_field[_dev] (reach_kernels.hpp); arguments checked by the caller (lo / hi are not null here)
   void reach_field(const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets, int64_t n_targets,
                    double min_clearance, int connectivity, int flags, const fiesta_hip_reach_result &r, fiesta_hip_reach_info *info, bool dev);
+  // fiesta_hip_reach_paths[_dev] (reach_path_kernels.hpp); arguments checked by the caller
+  void reach_paths(const int32_t *cost, const int32_t *box_lo, const int32_t *box_hi, const int32_t *targets, int64_t n_targets, int connectivity,
+                   int flags, int max_span, int64_t capacity, const fiesta_hip_reach_paths_result &r, bool dev);
   void synchronize();
 
  private:

@@ -240,6 +240,7 @@ template <class SRC>
 void reach_run(hipStream_t st, ReachScratch &S, DevBuf<unsigned char> &in, DevBuf<unsigned char> &out, const SRC &src, const int64_t lo[3],
                const int64_t hi[3], const int off[3], const ReachArgs &a) {
   const fiesta_hip_reach_result &res = *a.res;
+  S.field_valid = false;  // (fiesta_hip_reach_paths' retained field: only a call that finishes with its costs in S.cost leaves one)
   if (a.info) *a.info = fiesta_hip_reach_info{};
   const bool want_targets = res.target_cost && a.n_targets > 0;
   int32_t *dtc = nullptr;
@@ -339,6 +340,12 @@ void reach_run(hipStream_t st, ReachScratch &S, DevBuf<unsigned char> &in, DevBu
     I.max_cost = (int64_t)h[R_MAXCOST], I.rounds = (int64_t)h[R_ROUNDS], I.tile_visits = (int64_t)h[R_VISITS];
   } else {
     FIESTA_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  if (dcost == S.cost.p) {
+    S.field_lo[0] = ox, S.field_lo[1] = oy, S.field_lo[2] = oz;
+    for (int c = 0; c < 3; ++c) S.field_hi[c] = (int32_t)(hi[c] + off[c]);
+    S.field_connectivity = a.connectivity;
+    S.field_valid = true;
   }
 }
 

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachResult, Stats, check
+from ._lib import Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachPathsResult, ReachResult, Stats, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -745,6 +745,54 @@ class ESDFMap:
                                                    C.c_void_p(targets_dev_ptr or None), int(n_targets), float(min_clearance),
                                                    int(connectivity), int(flags), C.byref(res), C.byref(info)))
         return self._reach_info(info)
+
+    def ReachPaths(self, targets, cost=None, box=None, connectivity=26, shortcut=False, max_span=4096, want_pos=True) -> dict:
+        """fiesta_hip_reach_paths: per target ((n, 3) map voxels) the path down a cost-to-go field from the seed it was reached from to
+        the target.  The field: the one the map retained from its last ReachField call (cost and box None), or `cost` ((ex, ey, ez)
+        int32) with box = (box_lo, box_hi), the inclusive map-voxel box ReachField reported, and the connectivity it was flooded with.
+        shortcut: pull the staircase tight by line of sight through the field's traversable voxels, at most max_span moves per
+        segment.  Returns offsets ((n + 1,) int64 CSR), waypoints_vox ((N, 3) int32), waypoints_pos ((N, 3) f64 metres, the input of
+        PathClearance / PathCost; None without want_pos), status ((n,) int32, REACH_PATH_*) and n_moves ((n,) int32);
+        fiesta_amd.reach_paths_model is the definition"""
+        if (cost is None) != (box is None):
+            raise ValueError("cost and box must both be given or both be None")
+        t = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1, 3)
+        n = len(t)
+        c = blo = bhi = None
+        if cost is not None:
+            blo = np.ascontiguousarray(box[0], np.int32).reshape(3)
+            bhi = np.ascontiguousarray(box[1], np.int32).reshape(3)
+            c = np.ascontiguousarray(cost, dtype=np.int32)
+            if c.size != int(np.prod(np.maximum(bhi.astype(np.int64) - blo + 1, 0))):
+                raise ValueError("cost does not have the box's number of voxels")
+        flags = 1 if shortcut else 0
+        out = {"offsets": np.zeros(n + 1, np.int64), "status": np.empty(n, np.int32), "n_moves": np.empty(n, np.int32)}
+        res = ReachPathsResult(out["offsets"].ctypes.data, None, None, out["status"].ctypes.data, out["n_moves"].ctypes.data)
+        tp = _p(t) if n else None
+        check(self._lib.fiesta_hip_reach_paths(self._h, _p(c), _p(blo), _p(bhi), tp, n, int(connectivity), flags, int(max_span), 0, C.byref(res)))
+        total = int(out["offsets"][n])
+        out["waypoints_vox"] = np.empty((total, 3), np.int32)
+        out["waypoints_pos"] = np.empty((total, 3), np.float64) if want_pos else None
+        if total:
+            # (an explicit field was uploaded by the sizing call: the map retains it)
+            res = ReachPathsResult(out["offsets"].ctypes.data, out["waypoints_vox"].ctypes.data,
+                                   out["waypoints_pos"].ctypes.data if want_pos else None, None, None)
+            check(self._lib.fiesta_hip_reach_paths(self._h, None, None, None, tp, n, int(connectivity), flags, int(max_span), total, C.byref(res)))
+        return out
+
+    def ReachPathsDevice(self, targets_dev_ptr: int, n_targets: int, offsets_dev_ptr: int, cost_dev_ptr: int = 0, box=None, connectivity=26,
+                         shortcut=False, max_span=4096, capacity: int = 0, waypoints_vox_dev_ptr: int = 0, waypoints_pos_dev_ptr: int = 0,
+                         status_dev_ptr: int = 0, n_moves_dev_ptr: int = 0):
+        """fiesta_hip_reach_paths_dev: targets, the cost field (0: the retained one; else with box = (box_lo, box_hi), host triples) and
+        the outputs resident on the device (offsets: n_targets + 1 int64, required; 0: that array is not written); only enqueued on
+        the map's stream.  offsets holds the true totals whatever `capacity` is: enqueue with capacity 0 to size the buffers"""
+        blo = None if box is None else np.ascontiguousarray(box[0], np.int32).reshape(3)
+        bhi = None if box is None else np.ascontiguousarray(box[1], np.int32).reshape(3)
+        res = ReachPathsResult(int(offsets_dev_ptr) or None, int(waypoints_vox_dev_ptr) or None, int(waypoints_pos_dev_ptr) or None,
+                               int(status_dev_ptr) or None, int(n_moves_dev_ptr) or None)
+        check(self._lib.fiesta_hip_reach_paths_dev(self._h, C.c_void_p(cost_dev_ptr or None), _p(blo), _p(bhi), C.c_void_p(targets_dev_ptr or None),
+                                                   int(n_targets), int(connectivity), 1 if shortcut else 0, int(max_span), int(capacity),
+                                                   C.byref(res)))
 
     def count_no_obstacle(self) -> int:
         """Observed voxels whose distance reads +10000 (on grids beyond 1024 per axis this includes everything farther than

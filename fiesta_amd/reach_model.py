@@ -111,3 +111,167 @@ def reach_model(observed, occupied, seeds, dist=None, lo=None, hi=None, min_clea
         tc[tin] = field[t[tin, 0], t[tin, 1], t[tin, 2]]
         out["target_cost"] = tc
     return out
+
+
+# ---- fiesta_hip_reach_paths: paths out of a cost field -------------------------------------------------------------------------
+REACH_PATHS_SHORTCUT = 1       # FIESTA_HIP_REACH_PATHS_SHORTCUT
+REACH_PATH_OK = 0              # FIESTA_HIP_REACH_PATH_*: the per-target status
+REACH_PATH_OUTSIDE = 1         # the target lies outside the field's box
+REACH_PATH_BLOCKED = 2         # cost -1
+REACH_PATH_UNREACHED = 3       # cost INT32_MAX
+REACH_PATH_BROKEN = 4          # the field is no fixed point here: a voxel without predecessor, or a cost below -1
+REACH_PATH_MAX_MANHATTAN = 4095  # voxel steps between the two ends of a visibility test
+
+
+def reach_walk(p, q):
+    """The voxels the reference traversal (src/raycast.cpp:56-158; fiesta_amd.ray_walk's loop) emits from the centre of map voxel
+    p to the centre of map voxel q, a = p + 0.5 and b = q + 0.5 in voxel units, without clipping box, without the 1500-voxel
+    exception and WITHOUT the ray query's substitution of the last voxel: the traversal may stop one voxel beside q.  A list of
+    (x, y, z) tuples; empty for p == q."""
+    c = [int(p[0]), int(p[1]), int(p[2])]
+    e = [int(q[0]), int(q[1]), int(q[2])]
+    a = [c[0] + 0.5, c[1] + 0.5, c[2] + 0.5]
+    b = [e[0] + 0.5, e[1] + 0.5, e[2] + 0.5]
+    r0, r1, r2 = b[0] - a[0], b[1] - a[1], b[2] - a[2]
+    reach2 = r0 * r0 + r1 * r1 + r2 * r2
+    step, tmax, tstep = [0] * 3, [0.0] * 3, [0.0] * 3
+    for i in range(3):
+        delta = float(e[i] - c[i])
+        step[i] = (delta > 0) - (delta < 0)
+        # intbound of a centre: mod(+-(x + 0.5), 1) is 0.5 for either sign; a zero delta divides by +0
+        tmax[i] = (1 - 0.5) / abs(delta) if delta != 0 else float("inf")
+        tstep[i] = step[i] / delta if delta != 0 else float("nan")
+    out = []
+    if step == [0, 0, 0]:
+        return out
+    for _ in range(8192):
+        out.append((c[0], c[1], c[2]))
+        q0, q1, q2 = c[0] - a[0], c[1] - a[1], c[2] - a[2]
+        if q0 * q0 + q1 * q1 + q2 * q2 > reach2 or c == e:
+            break
+        if tmax[0] < tmax[1]:
+            ax = 0 if tmax[0] < tmax[2] else 2
+        else:
+            ax = 1 if tmax[1] < tmax[2] else 2
+        c[ax] += step[ax]
+        tmax[ax] += tstep[ax]
+    return out
+
+
+def reach_visible(cost3d, box_lo, p, q):
+    """visible(p, q) of fiesta_hip_reach_paths for map voxels p and q: at most 4095 voxel steps apart, and every voxel of
+    reach_walk(p, q) lies inside the field's box (element (0, 0, 0) of `cost3d` is map voxel `box_lo`) and has a cost >= 0"""
+    cost = np.asarray(cost3d)
+    if sum(abs(int(p[c]) - int(q[c])) for c in range(3)) > REACH_PATH_MAX_MANHATTAN:
+        return False
+    for v in reach_walk(p, q):
+        l = [v[c] - int(box_lo[c]) for c in range(3)]
+        if not all(0 <= l[c] < cost.shape[c] for c in range(3)) or cost[l[0], l[1], l[2]] < 0:
+            return False
+    return True
+
+
+def reach_paths_model(cost3d, box_lo, targets, connectivity=26, flags=0, max_span=4096, origin=(0.0, 0.0, 0.0), resolution=1.0, stats=None):
+    """The definition of fiesta_hip_reach_paths (include/fiesta_hip.h) in plain Python: `cost3d` is a cost field indexed
+    [x, y, z] whose element (0, 0, 0) is map voxel `box_lo` (reach_model's "cost" and "box_lo"), `targets` (n, 3) map voxels.
+    Per target the descent D[0] = target, D[k + 1] = the first move of reach_moves(connectivity) whose voxel lies in the box, has a
+    cost >= 0 and cost + weight == cost(D[k]), down to cost 0; with REACH_PATHS_SHORTCUT the anchors of the greedy line-of-sight
+    rule (reach_visible, at most max_span moves per segment), else every voxel; the waypoints are the anchors from the seed to the
+    target.  Returns a dict: offsets ((n + 1,) int64, CSR), waypoints_vox ((N, 3) int32), waypoints_pos ((N, 3) f64: Vox2Pos with
+    `origin` and `resolution`), status and n_moves ((n,) int32).  `stats`: a dict that receives visibility_tests and voxel_tests, the
+    work of the rule target by target with nothing shared: visible() calls, and the voxels they read up to the first that fails."""
+    moves = reach_moves(connectivity)
+    if flags & ~REACH_PATHS_SHORTCUT:
+        raise ValueError("unknown flag bits")
+    shortcut = bool(flags & REACH_PATHS_SHORTCUT)
+    if shortcut and max_span < 1:
+        raise ValueError("max_span must be >= 1 with REACH_PATHS_SHORTCUT")
+    cost = np.asarray(cost3d)
+    if cost.ndim != 3:
+        raise ValueError("cost3d must be a 3-D array")
+    ex, ey, ez = cost.shape
+    flat = cost.reshape(-1).tolist()
+    lo = [int(v) for v in np.asarray(box_lo).reshape(3)]
+    tg = np.asarray(targets, dtype=np.int64).reshape(-1, 3)
+    step_memo, span_memo, seen = {}, {}, {}
+
+    def descend(v):
+        """the voxel after v (cost > 0) on the way down; None: broken"""
+        if v in step_memo:
+            return step_memo[v]
+        x, y, z = v
+        c = flat[(x * ey + y) * ez + z]
+        found, bad = None, False
+        for dx, dy, dz, w in moves:
+            a, b, d = x + dx, y + dy, z + dz
+            if 0 <= a < ex and 0 <= b < ey and 0 <= d < ez:
+                cn = flat[(a * ey + b) * ez + d]
+                bad = bad or cn < -1                       # every neighbour of the step is read: one below -1 breaks the path
+                if found is None and cn >= 0 and cn + w == c:
+                    found = (a, b, d)
+        step_memo[v] = None if bad else found
+        return step_memo[v]
+
+    def visible(p, q):
+        """(visible, voxels read)"""
+        if abs(p[0] - q[0]) + abs(p[1] - q[1]) + abs(p[2] - q[2]) > REACH_PATH_MAX_MANHATTAN:
+            return False, 0
+        if (p, q) not in seen:
+            ok, read = True, 0
+            for x, y, z in reach_walk(p, q):               # (box-local voxels: a translation by integers changes no bit of the walk)
+                read += 1
+                if not (0 <= x < ex and 0 <= y < ey and 0 <= z < ez) or flat[(x * ey + y) * ez + z] < 0:
+                    ok = False
+                    break
+            seen[(p, q)] = (ok, read)
+        return seen[(p, q)]
+
+    n = len(tg)
+    work = [0, 0]                                          # visibility tests, voxels read
+    status = np.zeros(n, np.int32)
+    n_moves = np.full(n, -1, np.int32)
+    paths = []
+    for t in range(n):
+        v = tuple(int(tg[t, c]) - lo[c] for c in range(3))
+        paths.append([])
+        if not (0 <= v[0] < ex and 0 <= v[1] < ey and 0 <= v[2] < ez):
+            status[t] = REACH_PATH_OUTSIDE
+            continue
+        c = flat[(v[0] * ey + v[1]) * ez + v[2]]
+        if c == REACH_BLOCKED or c == REACH_UNREACHED or c < -1:
+            status[t] = REACH_PATH_BLOCKED if c == REACH_BLOCKED else (REACH_PATH_UNREACHED if c == REACH_UNREACHED else REACH_PATH_BROKEN)
+            continue
+        D = [v]
+        while D[-1] is not None and flat[(D[-1][0] * ey + D[-1][1]) * ez + D[-1][2]] > 0:
+            D.append(descend(D[-1]))
+        if D[-1] is None:
+            status[t] = REACH_PATH_BROKEN
+            continue
+        L = len(D) - 1
+        K = list(range(L + 1))
+        if shortcut:
+            K, i = [0], 0
+            while i < L:
+                # (the anchor after D[i] depends on D[i] alone: the rest of the descent follows from it)
+                if D[i] not in span_memo:
+                    j, tests, read = i + 1, 0, 0
+                    while j < L and j + 1 - i <= max_span:
+                        ok, r = visible(D[i], D[j + 1])
+                        tests, read = tests + 1, read + r
+                        if not ok:
+                            break
+                        j += 1
+                    span_memo[D[i]] = (j - i, tests, read)
+                span, tests, read = span_memo[D[i]]
+                work[0], work[1] = work[0] + tests, work[1] + read
+                i += span
+                K.append(i)
+        n_moves[t] = L
+        paths[-1] = [D[k] for k in reversed(K)]
+    if stats is not None:
+        stats["visibility_tests"], stats["voxel_tests"] = work
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum([len(p) for p in paths])
+    vox = np.array([w for p in paths for w in p], np.int64).reshape(-1, 3) + np.array(lo, np.int64)
+    pos = (vox.astype(np.float64) + 0.5) * float(resolution) + np.asarray(origin, np.float64).reshape(3)
+    return {"offsets": offsets, "waypoints_vox": vox.astype(np.int32), "waypoints_pos": pos, "status": status, "n_moves": n_moves}

@@ -322,6 +322,57 @@ class ESDFMap {
                               tv.empty() ? nullptr : tv.data(), (int64_t)targets.size(), min_clearance, connectivity, flags, &r, &info));
     return info;
   }
+  // Reach paths (fiesta_hip_reach_paths, include/fiesta_hip.h): per target voxel the path down a cost-to-go field, from the seed it was
+  // reached from to the target.  The field is the one the map retained from the last ReachField call (cost null), or *cost with its
+  // inclusive voxel box [box_lo, box_hi] (ReachField's info.box_lo / box_hi) and the connectivity it was flooded with.  shortcut: the
+  // staircase pulled tight by line of sight through the field's traversable voxels, at most max_span moves per segment.  offsets is
+  // CSR over the waypoints; pos (metres, 3 doubles per waypoint) and offsets are exactly what PathCostBatch and PathClearanceBatch
+  // take.  status: FIESTA_HIP_REACH_PATH_*; a target that is not OK has no waypoints and n_moves -1.
+  struct ReachPathSet {
+    std::vector<int64_t> offsets;  // n_targets + 1
+    std::vector<int32_t> vox;      // 3 per waypoint, map voxel coordinates
+    std::vector<double> pos;       // 3 per waypoint, metres
+    std::vector<int32_t> status, n_moves;
+    std::vector<Eigen::Vector3d> Path(size_t p) const {  // the waypoints of target p, seed first
+      std::vector<Eigen::Vector3d> out;
+      for (int64_t i = offsets[p]; i < offsets[p + 1]; ++i) out.push_back(Eigen::Vector3d(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]));
+      return out;
+    }
+  };
+  ReachPathSet ReachPaths(const std::vector<Eigen::Vector3i> &targets, int32_t connectivity = 26, bool shortcut = false, int32_t max_span = 4096,
+                          const std::vector<int32_t> *cost = nullptr, const Eigen::Vector3i *box_lo = nullptr,
+                          const Eigen::Vector3i *box_hi = nullptr) {
+    Flush();
+    if ((cost == nullptr) != (box_lo == nullptr) || (cost == nullptr) != (box_hi == nullptr))
+      throw std::invalid_argument("ReachPaths: cost, box_lo and box_hi must all be given or all be null");
+    int32_t a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
+    if (cost) {
+      int64_t nvox = 1;
+      for (int c = 0; c < 3; ++c) {
+        a[c] = (*box_lo)(c), b[c] = (*box_hi)(c);
+        nvox = a[c] > b[c] ? 0 : std::min<int64_t>(nvox * ((int64_t)b[c] - a[c] + 1), (1ll << 28) + 1);
+      }
+      if (nvox != (int64_t)cost->size()) throw std::invalid_argument("ReachPaths: cost does not have the box's number of voxels");
+    }
+    std::vector<int32_t> tv;
+    for (const auto &v : targets) tv.insert(tv.end(), {v(0), v(1), v(2)});
+    const int64_t n = (int64_t)targets.size();
+    const int32_t flags = shortcut ? FIESTA_HIP_REACH_PATHS_SHORTCUT : 0;
+    ReachPathSet out;
+    out.offsets.assign((size_t)n + 1, 0);
+    out.status.assign((size_t)n + 1, 0), out.n_moves.assign((size_t)n + 1, -1);  // (one spare entry: never a null pointer)
+    fiesta_hip_reach_paths_result r{out.offsets.data(), nullptr, nullptr, out.status.data(), out.n_moves.data()};
+    ck(fiesta_hip_reach_paths(h_, cost ? cost->data() : nullptr, cost ? a : nullptr, cost ? b : nullptr, tv.empty() ? nullptr : tv.data(), n,
+                              connectivity, flags, max_span, 0, &r));  // sizes the buffers (and uploads an explicit field: it is retained)
+    out.status.resize((size_t)n), out.n_moves.resize((size_t)n);
+    const int64_t total = out.offsets[(size_t)n];
+    out.vox.assign((size_t)total * 3, 0), out.pos.assign((size_t)total * 3, 0.0);
+    if (total > 0) {
+      r = fiesta_hip_reach_paths_result{out.offsets.data(), out.vox.data(), out.pos.data(), nullptr, nullptr};
+      ck(fiesta_hip_reach_paths(h_, nullptr, nullptr, nullptr, tv.data(), n, connectivity, flags, max_span, total, &r));
+    }
+    return out;
+  }
   // The reference's own getters (include/ESDFMap.h:144-145, src/ESDFMap.cpp:544-699).  The message types are template
   // parameters so that this header builds without ROS; sensor_msgs::PointCloud and visualization_msgs::Marker fit as
   // they are (fields used: header.frame_id, points[i].x/y/z, and for the marker id, type, action, scale, pose.orientation,

@@ -130,8 +130,8 @@ typedef struct fiesta_hip_stats {
 
 const char *fiesta_hip_last_error(void);
 /* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev].
- * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev], fiesta_hip_ray_query[_dev] and fiesta_hip_reach_field[_dev] came
- * later without a new number: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev], fiesta_hip_ray_query[_dev], fiesta_hip_reach_field[_dev] and
+ * fiesta_hip_reach_paths[_dev] came later without a new number: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -573,6 +573,80 @@ int fiesta_hip_reach_field(fiesta_hip_map *m, const int32_t lo[3], const int32_t
 int fiesta_hip_reach_field_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds_dev, int64_t n_seeds,
                                const int32_t *targets_dev, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
                                const fiesta_hip_reach_result *result, fiesta_hip_reach_info *info);
+
+/* ---- reach paths: the paths themselves, extracted from the cost-to-go field on the device ----
+ * The last step of the chain frontier voxels -> reachability -> paths -> path cost: fiesta_hip_reach_field says which targets the
+ * robot can reach and at what cost, this call descends the cost field from every target to the seed it was reached from and
+ * returns the paths in exactly the input form of fiesta_hip_path_clearance[_dev] and fiesta_hip_path_cost[_dev] -- CSR offsets
+ * (int64) over n x 3 f64 waypoints in metres -- so the whole chain stays on the device.  A raw path is a staircase of one-voxel
+ * moves; FIESTA_HIP_REACH_PATHS_SHORTCUT pulls it tight by line of sight through the flood's own traversable set.  Read-only; no
+ * reference counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.
+ * The field: either explicit -- `cost` holds ex * ey * ez int32 in fiesta_hip_reach_field's box-local order, box_lo / box_hi (HOST
+ *   pointers in both variants) are the inclusive box it covers in map voxel coordinates (fiesta_hip_reach_info.box_lo / box_hi of
+ *   the flood that made it; lo[c] <= hi[c], at most 2^28 voxels), connectivity the one it was flooded with -- or RETAINED: cost,
+ *   box_lo and box_hi all NULL.  A map retains the field of its last fiesta_hip_reach_field[_dev] call if that call succeeded, its
+ *   clipped box was not empty and its cost field lived in the map's own scratch memory (every host-variant call; a _dev call with
+ *   result->cost == NULL); any other reach_field call leaves nothing retained.  The host variant of THIS call with an explicit cost
+ *   uploads it into that scratch memory: it becomes the retained field, with the box and connectivity as given.  The _dev variant
+ *   reads an explicit cost in place and leaves what is retained alone.  With NULLs and nothing retained: FIESTA_HIP_ERR_STATE; with
+ *   NULLs and a connectivity other than the retained field's: FIESTA_HIP_ERR_INVALID.
+ *   The retained field is a SNAPSHOT: later fiesta_hip_update_occupancy / _update_esdf calls do not invalidate it, and paths run
+ *   through space as it was when it was flooded.  Nothing else of the map is read but its resolution and origin, so the call is
+ *   the same for dense maps, shards (whose info reports global voxel coordinates: use them) and hash-block maps.
+ * Descent: the moves are (dx, dy, dz) over -1, 0, 1 in lexicographic order, those that change one axis (connectivity 6) or any
+ *   (26), with weights 3 / 4 / 5 (fiesta_amd.reach_moves).  D[0] is the target.  From D[k] = v with c = cost(v) > 0, D[k + 1] is
+ *   v + move for the FIRST move, in that order, whose voxel n lies inside the box and has cost(n) >= 0 and cost(n) + weight == c.
+ *   The descent ends at cost 0 after L moves.  Every step lowers the cost by at least 3, so it ends after at most c / 3 steps
+ *   whatever the array holds.  A step reads every neighbour its moves name that lies inside the box; if none qualifies, or one of
+ *   them (or the target itself) has a cost below -1, the path is BROKEN -- the field is no fixed point for this connectivity.  No
+ *   read ever leaves the box.
+ * visible(p, q), for map voxels p and q: |p - q| summed over the axes is at most 4095, and every voxel that the reference traversal
+ *   (Raycast, src/raycast.cpp:56-158: the ray cast's and the ray query's, without clipping box and without the 1500-voxel
+ *   exception) emits from a = p + 0.5 to b = q + 0.5 -- f64, exact, in map voxel units, nothing is divided by the resolution --
+ *   its last one included, lies inside the box and has cost >= 0.  This is NOT the ray query's walk W: W replaces the traversal's
+ *   last voxel by floor(b), while between two centres the unsubstituted sequence followed by q is a 6-connected chain, so a
+ *   visible segment cuts no corner of a voxel that is not traversable.
+ * Anchors: without SHORTCUT every index 0 .. L (max_span is ignored).  With SHORTCUT (max_span >= 1):
+ *     K = [0]; i = 0
+ *     while i < L:  j = i + 1;  while j < L and j + 1 - i <= max_span and visible(D[i], D[j + 1]): j += 1;  K.append(j); i = j
+ *   (the first move from an anchor is never tested: it is a legal move of the flood; max_span = 1 reproduces the raw path).
+ * Outputs, per target p (targets: n_targets x 3 int32 map voxels):
+ *   offsets        int64, n_targets + 1: CSR over the waypoints, the TRUE totals whatever capacity is; REQUIRED
+ *   waypoints_vox  int32 x 3 per waypoint, map voxel coordinates; a path's waypoints are D[k] for k in K IN REVERSE: from the seed it
+ *                  reached to the target
+ *   waypoints_pos  f64 x 3 per waypoint, metres: ((double)v[c] + 0.5) * resolution + origin[c] (Vox2Pos)
+ *   status         FIESTA_HIP_REACH_PATH_*; n_moves: L.  A target of cost 0 yields one waypoint and 0 moves; every status other
+ *                  than OK yields no waypoint and n_moves -1.
+ *   Waypoints with a global index below `capacity` are written, nothing beyond it is touched: call with capacity 0 (the waypoint
+ *   arrays may then be NULL) and read offsets[n_targets] to size the buffers.  n_targets = 0 writes offsets[0] = 0.
+ *   All arithmetic is integer, the traversal and the positions apart: every output has the same bits for any launch shape, and the
+ *   bits of fiesta_amd.reach_paths_model (the definition in plain Python).
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): result or result->offsets NULL,
+ *   connectivity other than 6 or 26, unknown flag bits, SHORTCUT with max_span < 1, a negative count or capacity, targets NULL
+ *   with n_targets > 0, not all or none of cost / box_lo / box_hi given, an explicit box with lo[c] > hi[c] or more than 2^28 voxels.
+ * fiesta_hip_reach_paths      host arrays; stages through the path queries' buffers, runs, copies back min(total, capacity)
+ *                             waypoints, synchronises.
+ * fiesta_hip_reach_paths_dev  cost, targets and the result's arrays are device pointers; only enqueued on the map's stream (count,
+ *                             scan, write: no data-dependent allocation), unlike fiesta_hip_reach_field_dev. */
+#define FIESTA_HIP_REACH_PATHS_SHORTCUT 1
+#define FIESTA_HIP_REACH_PATH_OK 0        /* status values */
+#define FIESTA_HIP_REACH_PATH_OUTSIDE 1   /* target outside the field's box */
+#define FIESTA_HIP_REACH_PATH_BLOCKED 2   /* cost -1: not traversable */
+#define FIESTA_HIP_REACH_PATH_UNREACHED 3 /* cost INT32_MAX */
+#define FIESTA_HIP_REACH_PATH_BROKEN 4    /* the descent met a voxel with no predecessor, or a cost below -1 */
+typedef struct fiesta_hip_reach_paths_result {
+  int64_t *offsets;       /* n_targets + 1; REQUIRED */
+  int32_t *waypoints_vox; /* capacity x 3, map voxel coordinates; nullable */
+  double *waypoints_pos;  /* capacity x 3, metres; nullable */
+  int32_t *status;        /* per target; nullable */
+  int32_t *n_moves;       /* per target; nullable */
+} fiesta_hip_reach_paths_result;
+int fiesta_hip_reach_paths(fiesta_hip_map *m, const int32_t *cost, const int32_t box_lo[3], const int32_t box_hi[3], const int32_t *targets,
+                           int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span, int64_t capacity,
+                           const fiesta_hip_reach_paths_result *result);
+int fiesta_hip_reach_paths_dev(fiesta_hip_map *m, const int32_t *cost_dev, const int32_t box_lo[3], const int32_t box_hi[3],
+                               const int32_t *targets_dev, int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span,
+                               int64_t capacity, const fiesta_hip_reach_paths_result *result);
 
 /* ---- whole-field access (tests, visualisation, checkpoints) ----
  * Dense dump in the reference's linear order; each output is nullable.
