@@ -127,6 +127,14 @@ __device__ inline void wave_append(bool pred, uint32_t value, uint32_t *list, un
   if (pred) list[base + __popcll(m & ((1ull << lane) - 1ull))] = value;
 }
 
+// one thread per element unless the caller names a cap (= the kernel strides over the grid): the default must cover the
+// largest arrays (a 1024^3 shard touches 10^9 voxels at once -- a cap of 2^20 blocks silently dropped three quarters
+// of them, found by tools/c5_smoke.py)
+inline int grid_for(int64_t n, int block = 256, int cap = 0x7FFFFFFF) {
+  const int64_t b = (n + block - 1) / block;
+  return (int)(b < 1 ? 1 : b > cap ? cap : b);
+}
+
 // ---- geometry of one (shard of a) dense grid -------------------------------------------------------
 struct Geom {
   int nx, ny, nz;     // local array extent (owned box + ghost layers when sharded)
@@ -157,6 +165,8 @@ struct Geom {
   __host__ __device__ inline int64_t gbitword(int gx, int gy, int gz) const {
     return ((int64_t)gx * GY + gy) * GZW + (gz >> 5);
   }
+  // the update window covers the whole array (host side; the delete scans carry their own copy of the test)
+  inline bool full_window() const { return wx0 <= 0 && wy0 <= 0 && wz0 <= 0 && wx1 >= nx - 1 && wy1 >= ny - 1 && wz1 >= nz - 1; }
   __host__ __device__ inline bool owned(int x, int y, int z) const {
     return x >= ox0 && x <= ox1 && y >= oy0 && y <= oy1 && z >= oz0 && z <= oz1;
   }

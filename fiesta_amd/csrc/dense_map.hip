@@ -923,16 +923,6 @@ __global__ void k_count_stale(Geom g, const vox_t *coc, unsigned long long *out)
 // =====================================================================================================
 // host side
 // =====================================================================================================
-// one thread per element unless the caller names a cap (= the kernel strides over the grid): the default must cover the
-// largest arrays (a 1024^3 shard touches 10^9 voxels at once -- a cap of 2^20 blocks silently dropped three quarters
-// of them, found by tools/c5_smoke.py)
-static inline int grid_for(int64_t n, int block = 256, int cap = 0x7FFFFFFF) {
-  int64_t b = (n + block - 1) / block;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (int)b;
-}
-
 void DenseMap::use_device() const { FIESTA_HIP_CHECK(hipSetDevice(device_)); }
 
 DenseMap::DenseMap(const fiesta_hip_config &cfg) {
@@ -1072,7 +1062,6 @@ DenseMap::~DenseMap() {
   if (h_mask_ctr_) (void)hipHostFree(h_mask_ctr_);
   delete bricks_;
   delete lv_;
-  if (lv_done_) (void)hipEventDestroy(lv_done_);
   for (hipEvent_t e : evpool_) (void)hipEventDestroy(e);
   for (hipEvent_t e : ft_ev_)
     if (e) (void)hipEventDestroy(e);
@@ -1737,21 +1726,15 @@ bool DenseMap::run_cells(fiesta_hip_stats *st, int margin, bool publish, bool in
 // The map-local half of the engine choice: may this update be served by the bulk transform at all?
 bool DenseMap::bulk_eligible(unsigned long long ni, unsigned long long nd) {
   const Geom &g = g_;
-  // (a map that held no obstacle before this update has no history left: update_esdf clears the flag ahead of recording
-  //  this update's own window; here only when the window is the whole array -- the sharded driver's probe comes this way)
-  const bool full_win = g.wx0 <= 0 && g.wy0 <= 0 && g.wz0 <= 0 && g.wx1 >= g.nx - 1 && g.wy1 >= g.ny - 1 && g.wz1 >= g.nz - 1;
-  if (win_dirty_ && full_win && !g.sharded && (long long)h_counters_[C_NOCC] - (long long)ni + (long long)nd <= 0) win_dirty_ = false;
   if (update_engine_ == 1 || update_engine_ == 3) return false;
-  if (!(g.wx0 <= 0 && g.wy0 <= 0 && g.wz0 <= 0 && g.wx1 >= g.nx - 1 && g.wy1 >= g.ny - 1 && g.wz1 >= g.nz - 1)) return false;
+  if (!g.full_window()) return false;
   const long long owned = (long long)(g.ox1 - g.ox0 + 1) * (g.oy1 - g.oy0 + 1) * (g.oz1 - g.oz0 + 1);
   if ((long long)h_counters_[C_OBSERVED] != owned) return false;
   // An update that ran under a partial window left the voxels outside it as they were (inserts never reach them, the
   // orphans of a delete keep what one pull gave them, src/ESDFMap.cpp:351,378): from then on the reference's field is a
-  // function of its history, not the transform of the occupied set -- until the map holds no obstacle again.
-  if (win_dirty_) {
-    const long long before = (long long)h_counters_[C_NOCC] - (long long)ni + (long long)nd;
-    if (!g.sharded && before <= 0) win_dirty_ = false;
-  }
+  // function of its history, not the transform of the occupied set -- until the map holds no obstacle again: update_esdf
+  // clears the flag of an unsharded map that held no obstacle before the update (a shard cannot tell, see below; the sharded
+  // driver's probe, bulk_probe, only ever meets shards: ShardGroup::precheck).
   if (win_dirty_) return false;
   if (stale_inf_) {  // re-validate: does any observed voxel still wait for its first wave?
     zero_counter(C_SCRATCH);
@@ -1778,7 +1761,7 @@ bool DenseMap::masked_eligible(unsigned long long ni, unsigned long long nd) {
   const Geom &g = g_;
   if (g.sharded || g.wrap || update_engine_ == 1 || update_engine_ == 3) return false;
   if (g.nx > nn::kRegionMax || g.ny > nn::kRegionMax || g.nz > nn::kRegionMax) return false;
-  if (!(g.wx0 <= 0 && g.wy0 <= 0 && g.wz0 <= 0 && g.wx1 >= g.nx - 1 && g.wy1 >= g.ny - 1 && g.wz1 >= g.nz - 1)) return false;
+  if (!g.full_window()) return false;
   if (win_dirty_) return false;  // (update_esdf has cleared it if the map held no obstacle before this update)
   const long long before = (long long)h_counters_[C_NOCC] - (long long)ni + (long long)nd;
   unsigned long long late = h_counters_[C_LATE];
@@ -2135,22 +2118,11 @@ void DenseMap::bulk_probe(unsigned long long *ni, unsigned long long *nd, long l
   *eligible = bulk_eligible(*ni, *nd);
 }
 
-void DenseMap::level_tuning(int grid_groups, long long spin_limit) {
-  if (!lv_) lv_ = new LevelEngine;
-  if (grid_groups >= 0) lv_->grid_groups = grid_groups;
-  if (spin_limit >= 0) lv_->spin_limit = (uint32_t)spin_limit;
-}
+void DenseMap::level_tuning(int grid_groups, long long spin_limit) { LevelEngine::tuning(lv_, grid_groups, spin_limit); }
+int DenseMap::level_trace(uint32_t *out48) const { return LevelEngine::trace(lv_, out48); }
 
-int DenseMap::level_trace(uint32_t *out48) const {
-  memset(out48, 0, 48 * sizeof(uint32_t));
-  if (!lv_ || !lv_->h_ctl) return 0;
-  memcpy(out48, lv_->h_ctl->trace, 48 * sizeof(uint32_t));
-  return (int)lv_->h_ctl->level;
-}
-
-// UpdateESDF by the level engine (level_kernels.hpp).  Seeds: the insert queue, and the orphans the delete scan finds.
-// Returns false if the update did not fit the engine's lists: the field then carries frontier tags and the list of active
-// tiles is set up for the frontier rounds, which the caller runs.
+// UpdateESDF by the level engine (LevelEngine::update).  false: the update did not fit the engine's lists, the list of
+// active tiles is set up and the caller runs the frontier rounds.
 bool DenseMap::run_levels(fiesta_hip_stats *st, unsigned long long ni, unsigned long long nd) {
   if (!lv_) {
     lv_ = new LevelEngine;
@@ -2159,91 +2131,31 @@ bool DenseMap::run_levels(fiesta_hip_stats *st, unsigned long long ni, unsigned 
     if (const char *e = getenv("FIESTA_HIP_GRID_MIN")) lv_->grid_min = (uint32_t)atoi(e);
 #endif
   }
-  if (!lv_done_) FIESTA_HIP_CHECK(hipEventCreate(&lv_done_));
   // list capacity: what a frame needs is a few thousand entries; a forced level engine gets room for a large update
   const uint32_t want = update_engine_ == 3 ? (uint32_t)std::min<int64_t>(std::max<int64_t>(g_.n / 4, 1 << 20), 1 << 26) : (1u << 20);
   lv_->ensure(want, stream_);
-  lv_->begin();
-  LevelArgs a = lv_->args(coc_, counters_, track_);
-  DenseSpace sp{g_, occbits_, lv_box(g_)};
-  TileGrid tg{tx_, ty_, ntx_, nty_, ntz_};
-  const bool win_all = g_.wx0 <= 0 && g_.wy0 <= 0 && g_.wz0 <= 0 && g_.wx1 >= g_.nx - 1 && g_.wy1 >= g_.ny - 1 && g_.wz1 >= g_.nz - 1;
-  if (ni) {
-    hipLaunchKernelGGL((k_level_seed_insert<DenseSpace>), dim3(grid_for((int64_t)ni)), dim3(256), 0, stream_, sp, a,
-                       (const uint32_t *)ins_.p, (int64_t)ni);
-    FIESTA_HIP_CHECK(hipGetLastError());
-  }
+  LevelUpdate u{};
+  u.stream = stream_, u.t0 = ev0_;
+  u.coc = coc_, u.counters = counters_, u.track = track_;
+  u.ins = (const uint32_t *)ins_.p, u.ni = ni;
+  u.scan = nd != 0, u.full_window = g_.full_window();
+  u.pinned = update_engine_ == 3, u.tiny = ni + nd <= (unsigned long long)LevelEngine::kTiny;
+  u.nwords = g_.n;
+  u.tg = TileGrid{tx_, ty_, ntx_, nty_, ntz_}, u.tile_flag = tile_flag_[0], u.tile_list = tile_list_[0], u.list_count = &counters_[C_LIST0];
+  // the scan is bounded by (delete queue's box) + (largest stored distance) where that bound is tracked
   const int bounded = (track_ && nd) ? 1 : 0;
-  if (nd) {
-    if (bounded) {
-      hipLaunchKernelGGL(k_del_bbox, dim3(1), dim3(1024), 0, stream_, g_, (const uint32_t *)del_.p, (int64_t)nd, counters_);
-      FIESTA_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_invalidate<true>, dim3((grid_for(g_.n / 16 + 1, 256, 4096) + 7) / 8 * 8), dim3(256), 0, stream_, g_, tg, coc_,
-                       (const uint32_t *)occbits_, (const uint32_t *)gocc_, tile_flag_[0], tile_list_[0], &counters_[C_LIST0],
-                       counters_, bounded, a);
+  const auto scan = [&](bool levels, const LevelArgs &a) {
+    if (levels && bounded) hipLaunchKernelGGL(k_del_bbox, dim3(1), dim3(1024), 0, stream_, g_, (const uint32_t *)del_.p, (int64_t)nd, counters_);
+    hipLaunchKernelGGL(levels ? k_invalidate<true> : k_invalidate<false>, dim3((grid_for(g_.n / 16 + 1, 256, 4096) + 7) / 8 * 8), dim3(256), 0,
+                       stream_, g_, u.tg, coc_, (const uint32_t *)occbits_, (const uint32_t *)gocc_, tile_flag_[0], tile_list_[0],
+                       &counters_[C_LIST0], counters_, bounded, a);
     FIESTA_HIP_CHECK(hipGetLastError());
-    if (!win_all) {
-      hipLaunchKernelGGL((k_level_outside<DenseSpace>), dim3(64), dim3(256), 0, stream_, sp, a);
-      FIESTA_HIP_CHECK(hipGetLastError());
-    }
-    // the delete drain's list walk: the dead cells fill from their rims inwards before level 0 (level_kernels.hpp).  Whole-map
-    // updates only: under a partial window the orphans outside it keep asking their in-window neighbours (k_level_outside), and
-    // that proxy was fitted to neighbours that wait for their first pull (test_local_sliding_window_mode).
-    if (win_all) {
-      hipLaunchKernelGGL((k_level_fill<DenseSpace, 1024>), dim3(1), dim3(1024), 0, stream_, sp, a);
-      FIESTA_HIP_CHECK(hipGetLastError());
-    }
-  }
+  };
   host_counts_[0] = host_counts_[1] = 0;  // (k_level_run clears the device's queue counters)
-  int64_t launches = 0;
-  const LevelEngine::Outcome how = lv_->run(sp, a, stream_, lv_done_, update_engine_ == 3, ni + nd <= (unsigned long long)LevelEngine::kTiny, &launches);
-  const LevelCtl &c = *lv_->h_ctl;
-  if (how == LevelEngine::kDone) {
-    h_counters_fresh_ = false;
-    if (st) {
-      float ms = 0;
-      FIESTA_HIP_CHECK(hipEventElapsedTime(&ms, ev0_, lv_done_));
-      st->device_ms = ms;
-      st->relax_ms = ms;
-      st->rounds = (int64_t)c.work;
-      st->relax_launches = launches;
-      st->voxel_writes = (int64_t)c.writes;
-      st->invalidated = (int64_t)c.invalidated;
-      st->levels = 1;
-      st->grid_levels = (int64_t)c.grid_levels;
-      st->prof[0] = (int64_t)c.ticks * 10, st->prof[1] = (int64_t)c.level;  // ns inside k_level_run, levels
-      for (int k = 0; k < 4; ++k) st->prof[2 + k] = (int64_t)c.phase[k] * 10;
-      st->prof[6] = (int64_t)c.items, st->prof[7] = (int64_t)c.peak;
-    }
-    return true;
-  }
-  if (st) st->prof[1] = (int64_t)c.level, st->prof[6] = (int64_t)c.items, st->prof[7] = (int64_t)c.peak;  // (how far the levels got)
-  if (how == LevelEngine::kAbort)  // k_level_grid gave up between two phases: both repairs below, the list's first
-    FIESTA_HIP_CHECK(hipMemsetAsync(&lv_->ctl->overflow, 0, sizeof(uint32_t), stream_));  // (k_level_pull skips a given-up update)
-  if (how == LevelEngine::kHandOver || how == LevelEngine::kAbort) {  // the frontier grew beyond the level engine's reach: its entries become active tiles
-    a.level = c.level;  // (phase A of the level the engine stopped in front of: see k_level_list_to_tiles)
-    // (work-groups in proportion to the frontier: a delete on a surface orphans 10^5 voxels and level 0 is handed over whole)
-    const uint32_t n_over = std::min(c.n[c.level % 3u], lv_->cap);
-    hipLaunchKernelGGL((k_level_pull<DenseSpace>), dim3(std::min(std::max(n_over / 64u, 64u), 8192u)), dim3(256), 0, stream_, sp, a);
-    hipLaunchKernelGGL((k_level_list_to_tiles<DenseSpace>), dim3(std::min(std::max(n_over / 256u, 16u), 4096u)), dim3(256), 0, stream_, sp, a, tg,
-                       tile_flag_[0], tile_list_[0], &counters_[C_LIST0]);
-    FIESTA_HIP_CHECK(hipGetLastError());
-    if (how == LevelEngine::kHandOver) return false;
-  }
-  // Overflow.  What the level engine left behind: frontier tags on queued voxels, reset orphans that still carry their
-  // dead id, and -- if the scan's own lists overflowed -- orphans outside the window that nobody touched.  The ordinary scan
-  // finds the latter (their links are still dead), k_level_to_tiles turns the tags into active tiles.
-  if (nd) {
-    hipLaunchKernelGGL(k_invalidate<false>, dim3((grid_for(g_.n / 16 + 1, 256, 4096) + 7) / 8 * 8), dim3(256), 0, stream_, g_, tg, coc_,
-                       (const uint32_t *)occbits_, (const uint32_t *)gocc_, tile_flag_[0], tile_list_[0], &counters_[C_LIST0],
-                       counters_, bounded, LevelArgs{});
-    FIESTA_HIP_CHECK(hipGetLastError());
-  }
-  hipLaunchKernelGGL((k_level_to_tiles<DenseSpace>), dim3(grid_for(g_.n, 256, 8192)), dim3(256), 0, stream_, sp, a, g_.n, tg,
-                     tile_flag_[0], tile_list_[0], &counters_[C_LIST0]);
-  FIESTA_HIP_CHECK(hipGetLastError());
-  return false;
+  if (!lv_->update(DenseSpace{g_, occbits_, lv_box(g_)}, u, scan, st)) return false;
+  h_counters_fresh_ = false;
+  if (st) st->device_ms = st->relax_ms;
+  return true;
 }
 
 void DenseMap::update_esdf(fiesta_hip_stats *st, bool seed_only) {  // UpdateESDF (src/ESDFMap.cpp:273-398)
@@ -2286,7 +2198,7 @@ void DenseMap::update_esdf(fiesta_hip_stats *st, bool seed_only) {  // UpdateESD
     if (g_.wrap) notes_ |= FIESTA_HIP_NOTE_ID_WRAP;
     if (update_engine_ != 0) notes_ |= FIESTA_HIP_NOTE_ENGINE_PINNED;
   }
-  const bool full_window = g_.wx0 <= 0 && g_.wy0 <= 0 && g_.wz0 <= 0 && g_.wx1 >= g_.nx - 1 && g_.wy1 >= g_.ny - 1 && g_.wz1 >= g_.nz - 1;
+  const bool full_window = g_.full_window();
   // (a map that held no obstacle before this update has no history: cleared BEFORE this update's own window is recorded --
   //  the first obstacles inserted under a partial window on an empty map must leave the flag set)
   if (win_dirty_ && !g_.sharded && (long long)h_counters_[C_NOCC] - (long long)ni + (long long)nd <= 0) win_dirty_ = false;
@@ -2437,9 +2349,7 @@ void DenseMap::update_esdf(fiesta_hip_stats *st, bool seed_only) {  // UpdateESD
   run_rounds(st, n0, 0);
   bool reseeded = false;
   {  // orphans outside the update window (local / sliding-window maps): their pull, after the rounds
-    const Geom &g = g_;
-    const bool win_all = g.wx0 <= 0 && g.wy0 <= 0 && g.wz0 <= 0 && g.wx1 >= g.nx - 1 && g.wy1 >= g.ny - 1 && g.wz1 >= g.nz - 1;
-    if (!win_all && (nd || remote_del)) {
+    if (!full_window && (nd || remote_del)) {
       reseeded = true;
       hipLaunchKernelGGL(k_reseed_outside, dim3(grid_for(g_.n, 256, 8192)), dim3(256), 0, stream_, g_, coc_, (const uint32_t *)occbits_,
                          (const uint32_t *)gocc_, (const unsigned long long *)counters_, (track_ && nd) ? 1 : 0);

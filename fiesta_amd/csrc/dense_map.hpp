@@ -283,7 +283,6 @@ class DenseMap {
   // observed maps the masked transform for every update the map's history allows
   int update_engine_ = 0;
   LevelEngine *lv_ = nullptr;   // the level engine's lists and control block (level_kernels.hpp), created on first use
-  hipEvent_t lv_done_ = nullptr;
   double bulk_ratio_ = -1;  // >= 0 (a tuning build's FIESTA_HIP_BULK_RATIO): bulk when inserts + deletes exceed this fraction of the occupied voxels
   // Late observations: a voxel first observed while obstacles exist stays at "no obstacle" until a wave reaches it
   // (the reference never queues it), so the field is no longer the transform of the occupied set and the bulk path is

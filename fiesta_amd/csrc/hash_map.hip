@@ -71,14 +71,6 @@ __device__ inline bool h_alive(const Geom &g, const int32_t *dir, const uint32_t
   return ca >= 0 && hbit(occbits, ca);
 }
 
-// one thread per element unless the caller names a cap (= the kernel strides over the grid): the default must cover the
-// largest arrays (a 1024^3 shard touches 10^9 voxels at once -- a cap of 2^20 blocks silently dropped three quarters
-// of them, found by tools/c5_smoke.py)
-static inline int grid_for(int64_t n, int block = 256, int cap = 0x7FFFFFFF) {
-  int64_t b = (n + block - 1) / block;
-  return (int)std::min<int64_t>(std::max<int64_t>(b, 1), cap);
-}
-
 template <typename T>
 __global__ void k_h_fill(T *p, T v, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
@@ -720,7 +712,6 @@ HashMap::~HashMap() {
   if (h_counters_) (void)hipHostFree(h_counters_);
   delete lv_;
   delete bricks_;
-  if (lv_done_) (void)hipEventDestroy(lv_done_);
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
   if (stream_) (void)hipStreamDestroy(stream_);
@@ -1227,97 +1218,36 @@ void HashMap::run_rounds(fiesta_hip_stats *st, uint32_t first_count) {
   }
 }
 
-void HashMap::level_tuning(int grid_groups, long long spin_limit) {
-  if (!lv_) lv_ = new LevelEngine;
-  if (grid_groups >= 0) lv_->grid_groups = grid_groups;
-  if (spin_limit >= 0) lv_->spin_limit = (uint32_t)spin_limit;
-}
+void HashMap::level_tuning(int grid_groups, long long spin_limit) { LevelEngine::tuning(lv_, grid_groups, spin_limit); }
+int HashMap::level_trace(uint32_t *out48) const { return LevelEngine::trace(lv_, out48); }
 
-int HashMap::level_trace(uint32_t *out48) const {
-  memset(out48, 0, 48 * sizeof(uint32_t));
-  if (!lv_ || !lv_->h_ctl) return 0;
-  memcpy(out48, lv_->h_ctl->trace, 48 * sizeof(uint32_t));
-  return (int)lv_->h_ctl->level;
-}
-
-// UpdateESDF by the level engine (level_kernels.hpp; as DenseMap::run_levels).  false: the update did not fit its lists,
-// the field carries frontier tags and the tile list is set up for the frontier rounds.
-bool HashMap::run_levels(fiesta_hip_stats *st, unsigned long long ni, unsigned long long nd, bool scan) {
+// UpdateESDF by the level engine (LevelEngine::update).  false: the update did not fit its lists, the field carries
+// frontier tags and the tile list is set up for the frontier rounds.
+bool HashMap::run_levels(fiesta_hip_stats *st, unsigned long long ni, unsigned long long nd) {
   if (!lv_) lv_ = new LevelEngine;
-  if (!lv_done_) FIESTA_HIP_CHECK(hipEventCreate(&lv_done_));
   lv_->ensure(update_engine_ == 3 ? (1u << 24) : (1u << 20), stream_);
-  lv_->begin();
-  LevelArgs a = lv_->args(coc_.p, counters_, false);
-  PagedSpace sp{g_, occbits_.p, dir_, page_tile_.p, lv_box(g_)};
-  TileGrid tg{kTX, kTY, kNTX, kNTY, kNTZ};
-  const bool win_all = g_.wx0 <= 0 && g_.wy0 <= 0 && g_.wz0 <= 0 && g_.wx1 >= kWin - 1 && g_.wy1 >= kWin - 1 && g_.wz1 >= kWin - 1;
   const int64_t nvox = npages_ * kPageVox;
   if (nvox >= (1ll << 32)) throw Error(FIESTA_HIP_ERR_STATE, "page pool too large for the level engine's 32-bit addresses");
   FIESTA_HIP_CHECK(hipEventRecord(ev0_, stream_));
-  if (ni) {
-    hipLaunchKernelGGL((k_level_seed_insert<PagedSpace>), dim3(grid_for((int64_t)ni)), dim3(256), 0, stream_, sp, a,
-                       (const uint32_t *)ins_.p, (int64_t)ni);
+  LevelUpdate u{};
+  u.stream = stream_, u.t0 = ev0_;
+  u.coc = coc_.p, u.counters = counters_, u.track = false;
+  u.ins = (const uint32_t *)ins_.p, u.ni = ni;
+  u.scan = nd || force_scan_, u.full_window = g_.full_window();  // (a window move: obstacles left the window, parked pages came back)
+  u.pinned = update_engine_ == 3, u.tiny = ni + nd <= (unsigned long long)LevelEngine::kTiny;
+  u.nwords = nvox;
+  u.tg = TileGrid{kTX, kTY, kNTX, kNTY, kNTZ}, u.tile_flag = tile_flag_[0], u.tile_list = tile_list_[0], u.list_count = &counters_[C_LIST0];
+  const auto scan = [&](bool levels, const LevelArgs &a) {
+    hipLaunchKernelGGL(levels ? k_h_invalidate<true> : k_h_invalidate<false>, dim3(grid_for(nvox / 16 + 1, 256, 16384)), dim3(256), 0, stream_, g_,
+                       (const int32_t *)dir_, (const int32_t *)page_tile_.p, (const uint32_t *)page_fresh_.p, nvox, coc_.p,
+                       (const uint32_t *)occbits_.p, tile_flag_[0], tile_list_[0], &counters_[C_LIST0], counters_, a);
     FIESTA_HIP_CHECK(hipGetLastError());
-  }
-  if (scan) {
-    hipLaunchKernelGGL(k_h_invalidate<true>, dim3(grid_for(nvox / 16 + 1, 256, 16384)), dim3(256), 0, stream_, g_, (const int32_t *)dir_,
-                       (const int32_t *)page_tile_.p, (const uint32_t *)page_fresh_.p, nvox, coc_.p, (const uint32_t *)occbits_.p,
-                       tile_flag_[0], tile_list_[0], &counters_[C_LIST0], counters_, a);
-    FIESTA_HIP_CHECK(hipGetLastError());
+    if (!levels) return;  // (the fall-back's rescan: the pages' first-scan marks are cleared by now)
     if (force_scan_) FIESTA_HIP_CHECK(hipMemsetAsync(page_fresh_.p, 0, (size_t)npages_ * sizeof(uint32_t), stream_));
     force_scan_ = false;
-    if (!win_all) {
-      hipLaunchKernelGGL((k_level_outside<PagedSpace>), dim3(64), dim3(256), 0, stream_, sp, a);
-      FIESTA_HIP_CHECK(hipGetLastError());
-    }
-    if (win_all) {  // (see DenseMap::run_levels)
-      hipLaunchKernelGGL((k_level_fill<PagedSpace, 1024>), dim3(1), dim3(1024), 0, stream_, sp, a);
-      FIESTA_HIP_CHECK(hipGetLastError());
-    }
-  }
+  };
   host_ni_ = host_nd_ = 0;  // (k_level_run clears the device's queue counters)
-  int64_t launches = 0;
-  const LevelEngine::Outcome how = lv_->run(sp, a, stream_, lv_done_, update_engine_ == 3, ni + nd <= (unsigned long long)LevelEngine::kTiny, &launches);
-  const LevelCtl &c = *lv_->h_ctl;
-  if (how == LevelEngine::kDone) {
-    if (st) {
-      float ms = 0;
-      FIESTA_HIP_CHECK(hipEventElapsedTime(&ms, ev0_, lv_done_));
-      st->relax_ms = ms;
-      st->rounds = (int64_t)c.work;
-      st->relax_launches = launches;
-      st->voxel_writes = (int64_t)c.writes;
-      st->invalidated = (int64_t)c.invalidated;
-      st->levels = 1;
-      st->grid_levels = (int64_t)c.grid_levels;
-      st->prof[0] = (int64_t)c.ticks * 10, st->prof[1] = (int64_t)c.level;  // ns inside k_level_run, levels
-      for (int k = 0; k < 4; ++k) st->prof[2 + k] = (int64_t)c.phase[k] * 10;
-      st->prof[6] = (int64_t)c.items, st->prof[7] = (int64_t)c.peak;
-    }
-    return true;
-  }
-  if (how == LevelEngine::kAbort)  // (see DenseMap::run_levels)
-    FIESTA_HIP_CHECK(hipMemsetAsync(&lv_->ctl->overflow, 0, sizeof(uint32_t), stream_));
-  if (how == LevelEngine::kHandOver || how == LevelEngine::kAbort) {
-    a.level = c.level;  // (phase A of the level the engine stopped in front of: see k_level_list_to_tiles)
-    // (work-groups in proportion to the frontier: a delete on a surface orphans 10^5 voxels and level 0 is handed over whole)
-    const uint32_t n_over = std::min(c.n[c.level % 3u], lv_->cap);
-    hipLaunchKernelGGL((k_level_pull<PagedSpace>), dim3(std::min(std::max(n_over / 64u, 64u), 8192u)), dim3(256), 0, stream_, sp, a);
-    hipLaunchKernelGGL((k_level_list_to_tiles<PagedSpace>), dim3(std::min(std::max(n_over / 256u, 16u), 4096u)), dim3(256), 0, stream_, sp, a, tg,
-                       tile_flag_[0], tile_list_[0], &counters_[C_LIST0]);
-    FIESTA_HIP_CHECK(hipGetLastError());
-    if (how == LevelEngine::kHandOver) return false;
-  }
-  if (scan) {  // (see DenseMap::run_levels; `scan`, not nd: the first scan also ran for a window move)
-    hipLaunchKernelGGL(k_h_invalidate<false>, dim3(grid_for(nvox / 16 + 1, 256, 16384)), dim3(256), 0, stream_, g_, (const int32_t *)dir_,
-                       (const int32_t *)page_tile_.p, (const uint32_t *)page_fresh_.p, nvox, coc_.p, (const uint32_t *)occbits_.p,
-                       tile_flag_[0], tile_list_[0], &counters_[C_LIST0], counters_, LevelArgs{});
-    FIESTA_HIP_CHECK(hipGetLastError());
-  }
-  hipLaunchKernelGGL((k_level_to_tiles<PagedSpace>), dim3(grid_for(nvox, 256, 8192)), dim3(256), 0, stream_, sp, a, nvox, tg,
-                     tile_flag_[0], tile_list_[0], &counters_[C_LIST0]);
-  FIESTA_HIP_CHECK(hipGetLastError());
-  return false;
+  return lv_->update(PagedSpace{g_, occbits_.p, dir_, page_tile_.p, lv_box(g_)}, u, scan, st);
 }
 
 void HashMap::update_esdf(fiesta_hip_stats *st) {  // UpdateESDF (src/ESDFMap.cpp:273-398)
@@ -1346,7 +1276,7 @@ void HashMap::update_esdf(fiesta_hip_stats *st) {  // UpdateESDF (src/ESDFMap.cp
     if (update_engine_ != 1 && (update_engine_ == 3 || (ni + nd <= (unsigned long long)small_update_ && ni <= (unsigned long long)LevelEngine::kInsertCap))) {
       // (the level engine keeps its statistics in its own control block: no counter reset, no read-back of counters --
       //  dropped observations are reported from the last value the host saw plus what it clipped itself)
-      if (run_levels(st, ni, nd, nd || force_scan_)) {
+      if (run_levels(st, ni, nd)) {
         if (st) {
           st->device_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - d00).count();
           st->dropped_observations = (int64_t)h_counters_[C_DROPPED] + dropped_host_;

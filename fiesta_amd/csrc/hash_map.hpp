@@ -116,7 +116,7 @@ class HashMap {
   void zero_counter(int which);
   void zero_counters(int first, int n);
   void run_rounds(fiesta_hip_stats *st, uint32_t first_count);
-  bool run_levels(fiesta_hip_stats *st, unsigned long long ni, unsigned long long nd, bool scan);  // false: the rounds finish
+  bool run_levels(fiesta_hip_stats *st, unsigned long long ni, unsigned long long nd);  // false: the rounds finish
   PageTable page_table();  // the map-wide page table of the query kernels (hash_map.hip)
   // scalar queries (n <= kHostQueries positions per call, host pointers): a host-side cache of 16^3-voxel bricks of DISTANCES (f64,
   // as the query kernels compute them) and occupancy bits, keyed by map brick coordinates, fetched on first touch (r06: the dense
@@ -177,7 +177,6 @@ class HashMap {
   int update_engine_ = 0;
   int small_update_ = 4096;
   LevelEngine *lv_ = nullptr;  // level_kernels.hpp
-  hipEvent_t lv_done_ = nullptr;
   int64_t dropped_host_ = 0;  // voxels of observe_box() requests clipped away by the window (added to C_DROPPED in stats)
   unsigned long long *counters_ = nullptr, *h_counters_ = nullptr;
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_, stage_d_;

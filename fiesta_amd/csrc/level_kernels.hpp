@@ -1165,12 +1165,32 @@ __global__ void k_level_list_to_tiles(S sp, LevelArgs a, TileGrid tg, uint32_t *
 }
 
 // ---- host side: buffers and the launch sequence, shared by both map classes ------------------------------------------
+// What a store hands to LevelEngine::update: everything the two stores differ in on that path (besides their delete scan).
+struct LevelUpdate {
+  hipStream_t stream;
+  hipEvent_t t0;                // recorded by the store ahead of the update: relax_ms is measured from it
+  vox_t *coc;                   // LevelEngine::args
+  unsigned long long *counters;
+  bool track;
+  const uint32_t *ins;          // the insert queue and its length
+  unsigned long long ni;
+  bool scan;                    // there is a delete scan (dense: deletes; hash: deletes, or a window move)
+  bool full_window;             // Geom::full_window
+  bool pinned;                  // update_engine 3: every update the lists can hold
+  bool tiny;                    // inserts + deletes <= kTiny
+  int64_t nwords;               // voxel words k_level_to_tiles walks
+  TileGrid tg;                  // the frontier rounds' state that a fall-back fills: tile flags, tile list and its counter
+  uint32_t *tile_flag, *tile_list;
+  unsigned long long *list_count;
+};
+
 struct LevelEngine {
   DevBuf<uint32_t> list[2], res, outside, flags;
   uint32_t grid_launches = 0;
   LevelCtl *ctl2 = nullptr;   // device: two blocks, alternating between updates (the idle one is cleared by k_level_run)
   LevelCtl *ctl = nullptr;    // the current update's
   LevelCtl *h_ctl = nullptr;  // pinned
+  hipEvent_t done = nullptr;  // behind the last kernel of every chain of run()
   uint32_t serial = 0;
   uint32_t cap = 0;
   static constexpr uint32_t kSingleCap = 512;  // frontier one work-group keeps to itself: two entries per quad of lanes
@@ -1192,12 +1212,26 @@ struct LevelEngine {
   ~LevelEngine() {
     if (ctl2) (void)hipFree(ctl2);
     if (h_ctl) (void)hipHostFree(h_ctl);
+    if (done) (void)hipEventDestroy(done);
+  }
+  // fiesta_hip_level_tuning (creates the engine if there is none yet) / fiesta_hip_level_trace
+  static void tuning(LevelEngine *&lv, int grid_groups, long long spin_limit) {
+    if (!lv) lv = new LevelEngine;
+    if (grid_groups >= 0) lv->grid_groups = grid_groups;
+    if (spin_limit >= 0) lv->spin_limit = (uint32_t)spin_limit;
+  }
+  static int trace(const LevelEngine *lv, uint32_t *out48) {
+    memset(out48, 0, 48 * sizeof(uint32_t));
+    if (!lv || !lv->h_ctl) return 0;
+    memcpy(out48, lv->h_ctl->trace, 48 * sizeof(uint32_t));
+    return (int)lv->h_ctl->level;
   }
   void ensure(uint32_t want, hipStream_t s) {
     if (!ctl2) {
       FIESTA_HIP_CHECK(hipMalloc((void **)&ctl2, 2 * sizeof(LevelCtl)));
       FIESTA_HIP_CHECK(hipMemsetAsync(ctl2, 0, 2 * sizeof(LevelCtl), s));
       FIESTA_HIP_CHECK(hipHostMalloc((void **)&h_ctl, sizeof(LevelCtl)));
+      FIESTA_HIP_CHECK(hipEventCreate(&done));
       ctl = ctl2;
       flags.ensure_exact(64, s);
       FIESTA_HIP_CHECK(hipMemsetAsync(flags.p, 0, 64 * sizeof(uint32_t), s));
@@ -1241,7 +1275,7 @@ struct LevelEngine {
   // caller passes it to the rounds (k_level_list_to_tiles).  wide, without the grid: such levels go on as pairs of launches.
   // `done` is recorded behind the last kernel of every chain: when run() returns it marks the end of the levels' device work.
   template <class S>
-  Outcome run(const S &sp, LevelArgs a, hipStream_t s, hipEvent_t done, bool wide, bool tiny, int64_t *launches) {
+  Outcome run(const S &sp, LevelArgs a, hipStream_t s, bool wide, bool tiny, int64_t *launches) {
     uint32_t slot = 0;
     bool first = true;
     a.items_max = wide ? 0xFFFFFFFFu : kItemsMax;
@@ -1289,6 +1323,74 @@ struct LevelEngine {
         FIESTA_HIP_CHECK(hipStreamSynchronize(s));
       }
     }
+  }
+
+  // UpdateESDF by this engine, for either store (S: DenseSpace / PagedSpace).  Seeds: the insert queue, and the orphans the
+  // store's delete scan finds -- `scan(levels, args)`: levels = true, the scan that feeds level 0; false, the ordinary scan of
+  // the frontier rounds (the overflow repair below).  true: the update is finished and `st` holds the engine's statistics.
+  // false: the update did not fit the engine's lists -- the field then carries frontier tags and the list of active tiles
+  // (u.tile_*) is set up for the frontier rounds, which the caller runs.
+  template <class S, class Scan>
+  bool update(const S &sp, const LevelUpdate &u, Scan &&scan, fiesta_hip_stats *st) {
+    const hipStream_t s = u.stream;
+    begin();
+    LevelArgs a = args(u.coc, u.counters, u.track);
+    if (u.ni) {
+      hipLaunchKernelGGL((k_level_seed_insert<S>), dim3(grid_for((int64_t)u.ni)), dim3(256), 0, s, sp, a, u.ins, (int64_t)u.ni);
+      FIESTA_HIP_CHECK(hipGetLastError());
+    }
+    if (u.scan) {
+      scan(true, a);
+      // the delete drain's list walk: the dead cells fill from their rims inwards before level 0 (k_level_fill).  Whole-map
+      // updates only: under a partial window the orphans outside it keep asking their in-window neighbours (k_level_outside), and
+      // that proxy was fitted to neighbours that wait for their first pull (test_local_sliding_window_mode).
+      if (u.full_window)
+        hipLaunchKernelGGL((k_level_fill<S, 1024>), dim3(1), dim3(1024), 0, s, sp, a);
+      else
+        hipLaunchKernelGGL((k_level_outside<S>), dim3(64), dim3(256), 0, s, sp, a);
+      FIESTA_HIP_CHECK(hipGetLastError());
+    }
+    int64_t launches = 0;
+    const Outcome how = run(sp, a, s, u.pinned, u.tiny, &launches);
+    const LevelCtl &c = *h_ctl;
+    if (how == kDone) {
+      if (st) {
+        float ms = 0;
+        FIESTA_HIP_CHECK(hipEventElapsedTime(&ms, u.t0, done));
+        st->relax_ms = ms;
+        st->rounds = (int64_t)c.work;
+        st->relax_launches = launches;
+        st->voxel_writes = (int64_t)c.writes;
+        st->invalidated = (int64_t)c.invalidated;
+        st->levels = 1;
+        st->grid_levels = (int64_t)c.grid_levels;
+        st->prof[0] = (int64_t)c.ticks * 10, st->prof[1] = (int64_t)c.level;  // ns inside k_level_run, levels
+        for (int k = 0; k < 4; ++k) st->prof[2 + k] = (int64_t)c.phase[k] * 10;
+        st->prof[6] = (int64_t)c.items, st->prof[7] = (int64_t)c.peak;
+      }
+      return true;
+    }
+    if (how == kAbort)  // k_level_grid gave up between two phases: both repairs below, the list's first
+      FIESTA_HIP_CHECK(hipMemsetAsync(&ctl->overflow, 0, sizeof(uint32_t), s));  // (k_level_pull skips a given-up update)
+    if (how == kHandOver || how == kAbort) {  // the frontier grew beyond the level engine's reach: its entries become active tiles
+      a.level = c.level;  // (phase A of the level the engine stopped in front of: see k_level_list_to_tiles)
+      // (work-groups in proportion to the frontier: a delete on a surface orphans 10^5 voxels and level 0 is handed over whole)
+      const uint32_t n_over = std::min(c.n[c.level % 3u], cap);
+      hipLaunchKernelGGL((k_level_pull<S>), dim3(std::min(std::max(n_over / 64u, 64u), 8192u)), dim3(256), 0, s, sp, a);
+      hipLaunchKernelGGL((k_level_list_to_tiles<S>), dim3(std::min(std::max(n_over / 256u, 16u), 4096u)), dim3(256), 0, s, sp, a, u.tg,
+                         u.tile_flag, u.tile_list, u.list_count);
+      FIESTA_HIP_CHECK(hipGetLastError());
+      if (how == kHandOver) return false;
+    }
+    // Overflow.  What the level engine left behind: frontier tags on queued voxels, reset orphans that still carry their
+    // dead id, and -- if the scan's own lists overflowed -- orphans outside the window that nobody touched.  The ordinary scan
+    // finds the latter (their links are still dead), k_level_to_tiles turns the tags into active tiles.
+    // (`u.scan`, not the delete count: on the hash store the first scan also ran for a window move)
+    if (u.scan) scan(false, LevelArgs{});
+    hipLaunchKernelGGL((k_level_to_tiles<S>), dim3(grid_for(u.nwords, 256, 8192)), dim3(256), 0, s, sp, a, u.nwords, u.tg, u.tile_flag,
+                       u.tile_list, u.list_count);
+    FIESTA_HIP_CHECK(hipGetLastError());
+    return false;
   }
 };
 

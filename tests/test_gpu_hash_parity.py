@@ -107,6 +107,48 @@ def test_hash_insert_delete_fully_observed_region(hip_lib, oracle_libs, best_ora
     assert rep["d2_mismatch"] == 0 and rep["finite"] == 0, rep
 
 
+# (leg, update_engine, level_tuning(grid_groups, spin_limit) or None)
+LEVEL_LEGS = (("hand-over", "auto", None), ("grid", "levels", None), ("launch pairs", "levels", (0, -1)), ("grid gives up", "levels", (-1, 0)))
+
+
+@pytest.mark.parametrize("leg,engine,tuning", LEVEL_LEGS, ids=[l[0].replace(" ", "-") for l in LEVEL_LEGS])
+def test_hash_level_engine_routes_and_fall_backs(hip_lib, oracle_libs, best_oracle_kind, leg, engine, tuning):
+    """Every way an update leaves the level engine (level_kernels.hpp: LevelEngine::update) on the block store, on the scene of
+    test_hash_insert_delete_fully_observed_region: a fully observed region, where the contract is exact whatever engine serves
+    the update.  250 inserts stay under kInsertCap, the 64 000 voxels they rewrite exceed kItemsMax on a frontier far above
+    kGridMin: `auto` hands the update over to the rounds (k_level_pull, k_level_list_to_tiles); the pinned engine finishes it on
+    k_level_grid, or without it as pairs of launches; a grid that gives up at its first barrier (spin_limit 0) is repaired by
+    both routes (the list's, then the rescan and k_level_to_tiles) and the rounds finish."""
+    gpu, cpu = make(oracle_libs, best_oracle_kind, (0.0, 0.0, 0.0), 0.1, 1000)
+    gpu.set_update_engine(engine)
+    if tuning:
+        gpu.level_tuning(*tuning)
+    n = 40
+    g = np.stack(np.meshgrid(np.arange(n), np.arange(n), np.arange(n), indexing="ij"), -1).reshape(-1, 3).astype(np.int32) - 7
+    cycles(gpu, cpu, [], g, 1)
+    assert compare(gpu, cpu)["d2_mismatch"] == 0
+    rng = np.random.RandomState(9)
+    S = (rng.randint(0, n, (250, 3)) - 7).astype(np.int32)
+    st = cycles(gpu, cpu, S, [], 3)
+    print(leg, "250 inserts:", {k: st[k] for k in ("inserted", "levels", "grid_levels", "rounds", "relax_launches")})
+    rep = compare(gpu, cpu)
+    assert rep["d2_mismatch"] == 0 and rep["finite"] == n ** 3, rep
+    if leg in ("hand-over", "grid gives up"):
+        assert st["levels"] == 0 and st["rounds"] > 0, st
+    else:
+        assert st["levels"] == 1, st
+    if leg == "launch pairs":
+        assert st["grid_levels"] == 0, st
+    if leg == "grid gives up":      # ... and the engine goes on as before once the waits are long enough again
+        gpu.level_tuning(-1, 1 << 18)
+    st = cycles(gpu, cpu, (rng.randint(0, n, (80, 3)) - 7).astype(np.int32), S[:120], 6)
+    print(leg, "80 inserts, 120 deletes:", {k: st[k] for k in ("inserted", "deleted", "levels", "grid_levels", "rounds", "relax_launches")})
+    assert st["levels"] == 1 or st["rounds"] > 0, st
+    if leg == "grid gives up":
+        assert st["levels"] == 1, st
+    assert compare(gpu, cpu)["d2_mismatch"] == 0
+
+
 def test_hash_streaming_window_positions(hip_lib, oracle_libs, best_oracle_kind):
     """Config-4 shape: a moving observation window streams in new space (pages appear), obstacles come and go."""
     res = 0.05
