@@ -102,6 +102,19 @@ class ReachPathsResult(C.Structure):
                 ("n_moves", C.c_void_p)]
 
 
+class ClusterResult(C.Structure):
+    """fiesta_hip_cluster_result: one array per output of fiesta_hip_cluster_voxels, every pointer nullable"""
+    _fields_ = [("label", C.c_void_p), ("size", C.c_void_p), ("root", C.c_void_p), ("box_lo", C.c_void_p), ("box_hi", C.c_void_p),
+                ("centroid", C.c_void_p), ("mask_or", C.c_void_p), ("key_min", C.c_void_p), ("key_argmin", C.c_void_p),
+                ("offsets", C.c_void_p), ("members", C.c_void_p)]
+
+
+class ClusterInfo(C.Structure):
+    """fiesta_hip_cluster_info: the totals of one fiesta_hip_cluster_voxels call, whatever the capacities"""
+    _fields_ = [("n_clusters", C.c_int64), ("n_members", C.c_int64), ("n_invalid", C.c_int64), ("n_duplicates", C.c_int64),
+                ("n_dropped_clusters", C.c_int64), ("largest", C.c_int64)]
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/fiesta_hip.h declares (used by the CPU export test)."""
     text = open(header_path).read()
@@ -205,6 +218,8 @@ def load():
         "fiesta_hip_reach_field_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, vp, vp]),
         "fiesta_hip_reach_paths": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
         "fiesta_hip_reach_paths_dev": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
+        "fiesta_hip_cluster_voxels": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, i64, vp, vp]),
+        "fiesta_hip_cluster_voxels_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, i32, i64, i64, vp, vp]),
         "fiesta_hip_get_occupancy_vox": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_get_occupancy_pos": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_download_field": (C.c_int, [vp, vp, vp, vp, vp]),

@@ -119,6 +119,17 @@ void reach_paths_args(fiesta_hip_map *m, const int32_t *cost, const int32_t *lo,
   }
   need(m != nullptr, "null map handle");
 }
+// the whole-call errors of fiesta_hip_cluster_voxels[_dev] (include/fiesta_hip.h); none of them needs a device
+void cluster_args(fiesta_hip_map *m, const int32_t *vox, int64_t n, int32_t connectivity, int32_t min_size, int64_t cluster_capacity,
+                  int64_t member_capacity, const void *info) {
+  need(info != nullptr, "cluster_voxels: info is null");
+  need(n >= 0 && n <= (1ll << 24), "cluster_voxels: the entry count must lie in 0 .. 2^24");
+  need(connectivity == 6 || connectivity == 18 || connectivity == 26, "cluster_voxels: connectivity must be 6, 18 or 26");
+  need(min_size >= 1, "cluster_voxels: min_size must be >= 1");
+  need(cluster_capacity >= 0 && member_capacity >= 0, "cluster_voxels: negative capacity");
+  need(vox != nullptr || n == 0, "cluster_voxels: vox is null");
+  need(m != nullptr, "null map handle");
+}
 }  // namespace
 
 extern "C" {
@@ -607,6 +618,28 @@ int fiesta_hip_reach_paths_dev(fiesta_hip_map *m, const int32_t *cost_dev, const
       m->dense->reach_paths(cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, *result, true);
     else
       m->hash->reach_paths(cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, *result, true);
+  });
+}
+int fiesta_hip_cluster_voxels(fiesta_hip_map *m, const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, int32_t connectivity,
+                              int32_t min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *result,
+                              fiesta_hip_cluster_info *info) {
+  return guarded([&] {
+    cluster_args(m, vox, n, connectivity, min_size, cluster_capacity, member_capacity, info);
+    if (m->dense)
+      m->dense->cluster_voxels(vox, mask, key, n, nullptr, connectivity, min_size, cluster_capacity, member_capacity, result, info, false);
+    else
+      m->hash->cluster_voxels(vox, mask, key, n, nullptr, connectivity, min_size, cluster_capacity, member_capacity, result, info, false);
+  });
+}
+int fiesta_hip_cluster_voxels_dev(fiesta_hip_map *m, const int32_t *vox_dev, const uint8_t *mask_dev, const int32_t *key_dev, int64_t n,
+                                  const unsigned long long *n_dev, int32_t connectivity, int32_t min_size, int64_t cluster_capacity,
+                                  int64_t member_capacity, const fiesta_hip_cluster_result *result, fiesta_hip_cluster_info *info_dev) {
+  return guarded([&] {
+    cluster_args(m, vox_dev, n, connectivity, min_size, cluster_capacity, member_capacity, info_dev);
+    if (m->dense)
+      m->dense->cluster_voxels(vox_dev, mask_dev, key_dev, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, result, info_dev, true);
+    else
+      m->hash->cluster_voxels(vox_dev, mask_dev, key_dev, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, result, info_dev, true);
   });
 }
 int fiesta_hip_get_slice(fiesta_hip_map *m, int32_t z_vox, double *out) {

@@ -61,6 +61,14 @@ struct ReachScratch {
   int field_connectivity = 0;
 };
 
+// scratch of fiesta_hip_cluster_voxels (cluster_kernels.hpp), owned by a map: the voxel hash table, the per-entry union-find arrays,
+// the per-cluster accumulators and two counters; allocated on first use, grown on demand, freed with the map
+struct ClusterScratch {
+  DevBuf<unsigned long long> keys, sum, kmin, ctr;
+  DevBuf<int32_t> tidx, lab, parent, cnt, box, csize;
+  DevBuf<uint32_t> mor;
+};
+
 // Device-side counters, one 64-bit word each.
 enum Counter {
   C_TOUCHED = 0,   // length of the touched-voxel list (the reference's occupancy_queue_)
@@ -178,6 +186,10 @@ class DenseMap {
   // fiesta_hip_reach_paths[_dev] (reach_path_kernels.hpp); arguments checked by the caller
   void reach_paths(const int32_t *cost, const int32_t *box_lo, const int32_t *box_hi, const int32_t *targets, int64_t n_targets, int connectivity,
                    int flags, int max_span, int64_t capacity, const fiesta_hip_reach_paths_result &r, bool dev);
+  // fiesta_hip_cluster_voxels[_dev] (cluster_kernels.hpp); arguments checked by the caller
+  void cluster_voxels(const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const unsigned long long *n_dev, int connectivity,
+                      int min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *r,
+                      fiesta_hip_cluster_info *info, bool dev);
   int64_t count_no_obstacle();
   void slice_distances(int z_vox, double *out);        // nx * ny doubles, x-major
   // GetPointCloud / GetSliceMarker as arrays; both return the total count (may exceed cap), order unspecified
@@ -359,6 +371,7 @@ class DenseMap {
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_;
   DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path and ray queries: staged inputs, plan / piece records, staged outputs
   ReachScratch reach_;
+  ClusterScratch cluster_;
   // raycast front-end state (per-frame stamp arrays = Fiesta::set_occ_/set_free_, include/Fiesta.h:107-110;
   // per-ray traversal lists), lazily allocated by raycast.hip
   struct RaycastState;

@@ -23,6 +23,7 @@
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
 #include "reach_path_kernels.hpp"
+#include "cluster_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
@@ -1617,6 +1618,16 @@ void HashMap::reach_paths(const int32_t *cost, const int32_t *box_lo, const int3
   use_device();
   reach_paths_run(stream_, reach_, path_in_, path_out_, g_.res, g_.org,
                   ReachPathArgs{cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, &r, dev});
+}
+
+// fiesta_hip_cluster_voxels[_dev] (cluster_kernels.hpp); arguments checked by the caller.  Nothing of the map is read but its
+// resolution and origin.
+void HashMap::cluster_voxels(const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const unsigned long long *n_dev, int connectivity,
+                             int min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *r,
+                             fiesta_hip_cluster_info *info, bool dev) {
+  use_device();
+  cluster_voxels_run(stream_, cluster_, path_in_, path_out_, g_.res, g_.org,
+                     ClusterArgs{vox, mask, key, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, r, info, dev});
 }
 
 // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller.  Every page answers, resident or parked.

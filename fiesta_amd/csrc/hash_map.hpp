@@ -101,6 +101,10 @@ class HashMap {
   // fiesta_hip_reach_paths[_dev] (reach_path_kernels.hpp); arguments checked by the caller
   void reach_paths(const int32_t *cost, const int32_t *box_lo, const int32_t *box_hi, const int32_t *targets, int64_t n_targets, int connectivity,
                    int flags, int max_span, int64_t capacity, const fiesta_hip_reach_paths_result &r, bool dev);
+  // fiesta_hip_cluster_voxels[_dev] (cluster_kernels.hpp); arguments checked by the caller
+  void cluster_voxels(const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const unsigned long long *n_dev, int connectivity,
+                      int min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *r,
+                      fiesta_hip_cluster_info *info, bool dev);
   void synchronize();
 
  private:
@@ -182,6 +186,7 @@ class HashMap {
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_, stage_d_;
   DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path and ray queries: staged inputs, plan / piece records, staged outputs
   ReachScratch reach_;
+  ClusterScratch cluster_;
 };
 
 void raycast_single(const double *start, const double *end, const double *minv, const double *maxv, double *out,

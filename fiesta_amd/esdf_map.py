@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachPathsResult, ReachResult, Stats, check
+from ._lib import ClusterInfo, ClusterResult, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachPathsResult, ReachResult, Stats, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -41,7 +41,10 @@ ENGINES = {"auto": 0, "rounds": 1, "bulk": 2, "levels": 3, "envelope": 4, "cells
 PATH_FIELDS = (("min_dist", np.float64, ()), ("min_index", np.int64, ()), ("min_pos", np.float64, (3,)),
                ("min_grad", np.float64, (3,)), ("first_below", np.int64, ()), ("first_below_pos", np.float64, (3,)),
                ("n_samples", np.int64, ()))
-PATH_MAX_RATIO = 2.0 ** 24   # a segment with L / step above this makes its path invalid
+# the per-cluster arrays of fiesta_hip_cluster_result, in struct order (label before, offsets and members after them)
+CLUSTER_FIELDS = (("size", np.int32, ()), ("root", np.int64, ()), ("box_lo", np.int32, (3,)), ("box_hi", np.int32, (3,)),
+                  ("centroid", np.float64, (3,)), ("mask_or", np.uint8, ()), ("key_min", np.int32, ()), ("key_argmin", np.int64, ()))
+PATH_MAX_RATIO = 2.0 ** 24  # a segment with L / step above this makes its path invalid
 
 
 def path_samples(waypoints, offsets, step):
@@ -349,6 +352,8 @@ class ESDFMap:
             cfg.shard_lo[:] = [int(v) for v in shard_lo]
             cfg.global_grid[:] = [int(v) for v in global_grid]
         self.mode = mode
+        self.device = int(device)
+        self._frontier_buffers, self._frontier_capacity = None, 1 << 16   # FrontierClusters' device buffers
         self.resolution = float(resolution)
         self.origin = _d3(origin)
         # PosInMap's range of an array-mode map as the library adds it up (ray_query_model's pos_range); a shard: the global map's
@@ -793,6 +798,99 @@ class ESDFMap:
         check(self._lib.fiesta_hip_reach_paths_dev(self._h, C.c_void_p(cost_dev_ptr or None), _p(blo), _p(bhi), C.c_void_p(targets_dev_ptr or None),
                                                    int(n_targets), int(connectivity), 1 if shortcut else 0, int(max_span), int(capacity),
                                                    C.byref(res)))
+
+    @staticmethod
+    def _cluster_info(info) -> dict:
+        return {k: int(getattr(info, k)) for k, _ in ClusterInfo._fields_}
+
+    def ClusterVoxels(self, vox, mask=None, key=None, connectivity=26, min_size=1) -> dict:
+        """fiesta_hip_cluster_voxels: the connected clusters (connectivity 6, 18 or 26) of the voxel list `vox` ((n, 3) map voxels, any
+        order, e.g. GetFrontierVoxels' output), those below `min_size` distinct voxels dropped, the rest numbered by their lowest entry
+        index.  mask ((n,) uint8) and key ((n,) int32, e.g. ReachField's target_cost) are optional per-entry data.  Returns label
+        ((n,) int32, -1: no cluster), per cluster size, root, box_lo, box_hi, centroid (metres), mask_or, key_min and key_argmin, the
+        CSR pair offsets / members (entry indices of each cluster's distinct voxels, unordered inside a cluster), and the totals of
+        fiesta_hip_cluster_info; fiesta_amd.cluster_model is the definition"""
+        v = np.ascontiguousarray(vox, dtype=np.int32).reshape(-1, 3)
+        n = len(v)
+        mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+        ky = None if key is None else np.ascontiguousarray(key, dtype=np.int32).reshape(-1)
+        if (mk is not None and len(mk) != n) or (ky is not None and len(ky) != n):
+            raise ValueError("mask and key need one value per entry")
+        info = ClusterInfo()
+        label = np.empty(n, np.int32)
+        members = np.empty(n, np.int64)
+        cap = min(n, 1 << 16)   # (clusters are few: one call serves unless there are more than this, then a second one with the total)
+        while True:
+            out = {name: np.empty((cap,) + shape, dtype) for name, dtype, shape in CLUSTER_FIELDS}
+            out["offsets"] = np.zeros(cap + 1, np.int64)
+            res = ClusterResult(label.ctypes.data, *[out[name].ctypes.data for name, _, _ in CLUSTER_FIELDS], out["offsets"].ctypes.data,
+                                members.ctypes.data)
+            check(self._lib.fiesta_hip_cluster_voxels(self._h, _p(v) if n else None, _p(mk), _p(ky), n, int(connectivity), int(min_size), cap, n,
+                                                      C.byref(res), C.byref(info)))
+            if info.n_clusters <= cap:
+                break
+            cap = int(info.n_clusters)
+        k = int(info.n_clusters)
+        out = {name: a[:k + 1] if name == "offsets" else a[:k] for name, a in out.items()}
+        out["label"], out["members"] = label, members[:int(info.n_members)]
+        out.update(self._cluster_info(info))
+        return out
+
+    def ClusterVoxelsDevice(self, vox_dev_ptr: int, n: int, info_dev_ptr: int, mask_dev_ptr: int = 0, key_dev_ptr: int = 0, n_dev_ptr: int = 0,
+                            connectivity=26, min_size=1, cluster_capacity: int = 0, member_capacity: int = 0, out=None):
+        """fiesta_hip_cluster_voxels_dev: every array resident on the device (`out` maps field names of fiesta_hip_cluster_result to
+        device pointers, missing fields are not written; info_dev_ptr: a device fiesta_hip_cluster_info, six int64).  n_dev_ptr: a
+        device 64-bit counter, the entry count is min(n, counter) -- GetFrontierVoxelsDevice's.  Only enqueued on the map's stream"""
+        out = out or {}
+        res = ClusterResult(*[int(out.get(name, 0)) or None for name, _ in ClusterResult._fields_])
+        check(self._lib.fiesta_hip_cluster_voxels_dev(self._h, C.c_void_p(vox_dev_ptr or None), C.c_void_p(mask_dev_ptr or None),
+                                                      C.c_void_p(key_dev_ptr or None), int(n), C.c_void_p(n_dev_ptr or None), int(connectivity),
+                                                      int(min_size), int(cluster_capacity), int(member_capacity), C.byref(res),
+                                                      C.c_void_p(info_dev_ptr or None)))
+
+    def FrontierClusters(self, lo=None, hi=None, min_clearance=0.0, connectivity=26, min_size=1) -> dict:
+        """GetFrontierVoxels and ClusterVoxels as one chain on the device: the frontier sweep writes into device buffers this object
+        keeps (torch tensors, grown on demand), its device counter feeds the clustering, and the host waits ONCE, at the end, before
+        it copies the results back: vox, mask, and everything ClusterVoxels returns for that list.  Only when the buffers turn out too
+        small for the frontier (the first call, a frontier that grew by more than a quarter) is the chain run a second time."""
+        import torch
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        dev = torch.device("cuda", self.device)
+        while True:
+            b = self._frontier_buffers
+            if b is None:
+                cap = self._frontier_capacity
+                b = {"vox": torch.empty((cap, 3), dtype=torch.int32, device=dev), "mask": torch.empty(cap, dtype=torch.uint8, device=dev),
+                     "label": torch.empty(cap, dtype=torch.int32, device=dev), "members": torch.empty(cap, dtype=torch.int64, device=dev),
+                     "offsets": torch.empty(cap + 1, dtype=torch.int64, device=dev),
+                     "head": torch.zeros(8, dtype=torch.int64, device=dev)}   # [0]: the frontier counter, [1 .. 6]: the cluster info
+                for name, dtype, shape in CLUSTER_FIELDS:
+                    b[name] = torch.empty((cap,) + shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
+                torch.cuda.synchronize(dev)   # (the map's stream does not wait for torch's)
+                self._frontier_buffers = b
+            cap = b["label"].shape[0]
+            head = b["head"].data_ptr()
+            self.GetFrontierVoxelsDevice(lo, hi, min_clearance, b["vox"].data_ptr(), b["mask"].data_ptr(), cap, head)
+            outs = {name: b[name].data_ptr() for name, _ in ClusterResult._fields_}
+            self.ClusterVoxelsDevice(b["vox"].data_ptr(), cap, head + 8, mask_dev_ptr=b["mask"].data_ptr(), n_dev_ptr=head,
+                                     connectivity=connectivity, min_size=min_size, cluster_capacity=cap, member_capacity=cap, out=outs)
+            self.synchronize()
+            h = b["head"].cpu().numpy()
+            n = int(h[0])
+            if n <= cap:
+                break
+            self._frontier_buffers, self._frontier_capacity = None, min(max(n + n // 4, 1024), 1 << 24)
+            if n > 1 << 24:
+                raise ValueError("the frontier holds more than 2^24 voxels: cluster it box by box")
+        info = {name: int(h[1 + i]) for i, (name, _) in enumerate(ClusterInfo._fields_)}
+        k = info["n_clusters"]
+        out = {name: b[name][:k].cpu().numpy() for name, _, _ in CLUSTER_FIELDS}
+        out["offsets"] = b["offsets"][:k + 1].cpu().numpy()
+        out["members"] = b["members"][:info["n_members"]].cpu().numpy()
+        out["vox"], out["mask"], out["label"] = b["vox"][:n].cpu().numpy(), b["mask"][:n].cpu().numpy(), b["label"][:n].cpu().numpy()
+        out.update(info)
+        return out
 
     def count_no_obstacle(self) -> int:
         """Observed voxels whose distance reads +10000 (on grids beyond 1024 per axis this includes everything farther than

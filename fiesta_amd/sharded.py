@@ -468,6 +468,13 @@ class ShardedESDFMap:
                 out[m] = self.shards[r].GetDistance(vox[m])
         return out
 
+    def ClusterVoxels(self, vox, mask=None, key=None, connectivity=26, min_size=1, rank=None):
+        """ESDFMap.ClusterVoxels on a shard of this process (`rank`; default: its first one).  The call reads nothing of a map but its
+        resolution and origin, which every shard shares, so any shard answers for any voxel list; clusters are not joined across
+        lists that different shards hold"""
+        sh = self.shards[min(self.shards) if rank is None else rank]
+        return sh.ClusterVoxels(vox, mask=mask, key=key, connectivity=connectivity, min_size=min_size)
+
     def download_owned(self, want=("d2", "coc", "occ")):
         """{rank: (lo, size, fields cropped to the owned box)} for the shards of this process."""
         out = {}

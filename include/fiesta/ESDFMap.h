@@ -373,6 +373,67 @@ class ESDFMap {
     }
     return out;
   }
+  // Voxel clusters (fiesta_hip_cluster_voxels, include/fiesta_hip.h): the connected groups (connectivity 6, 18 or 26) of a voxel list
+  // -- typically GetFrontierVoxels' -- with those below min_size distinct voxels dropped and the rest numbered by their lowest entry
+  // index.  mask (nullable): the frontier call's unknown-neighbour bits; key (nullable): one int32 per entry, e.g. ReachField's
+  // target_cost -- key_min / key_argmin then name each cluster's cheapest reachable member (negative keys are ignored; INT32_MAX
+  // and -1: none).  members / offsets: CSR over the entry indices of each cluster's distinct voxels, unordered inside a cluster.
+  struct VoxelClusters {
+    std::vector<int32_t> label;  // per entry; -1: invalid entry or dropped cluster
+    std::vector<int32_t> size;   // per cluster from here on
+    std::vector<int64_t> root;
+    std::vector<Eigen::Vector3i> box_lo, box_hi;  // inclusive
+    std::vector<Eigen::Vector3d> centroid;        // metres
+    std::vector<uint8_t> mask_or;
+    std::vector<int32_t> key_min;
+    std::vector<int64_t> key_argmin;
+    std::vector<int64_t> offsets, members;
+    fiesta_hip_cluster_info info{};
+    size_t count() const { return size.size(); }
+  };
+  VoxelClusters ClusterVoxels(const std::vector<Eigen::Vector3i> &vox, const std::vector<uint8_t> *mask = nullptr,
+                              const std::vector<int32_t> *key = nullptr, int32_t connectivity = 26, int32_t min_size = 1) {
+    Flush();
+    const int64_t n = (int64_t)vox.size();
+    if ((mask && (int64_t)mask->size() != n) || (key && (int64_t)key->size() != n))
+      throw std::invalid_argument("ClusterVoxels: mask and key need one value per entry");
+    std::vector<int32_t> v;
+    for (const auto &p : vox) v.insert(v.end(), {p(0), p(1), p(2)});
+    const int32_t *vp = v.empty() ? nullptr : v.data();
+    const uint8_t *mp = mask && n ? mask->data() : nullptr;
+    const int32_t *kp = key && n ? key->data() : nullptr;
+    VoxelClusters out;
+    ck(fiesta_hip_cluster_voxels(h_, vp, mp, kp, n, connectivity, min_size, 0, 0, nullptr, &out.info));  // sizes the buffers
+    const size_t k = (size_t)out.info.n_clusters;
+    out.label.assign((size_t)n + 1, -1);  // (one spare entry in every array: never a null pointer)
+    out.size.assign(k + 1, 0), out.root.assign(k + 1, 0), out.mask_or.assign(k + 1, 0), out.key_min.assign(k + 1, 0);
+    out.key_argmin.assign(k + 1, 0), out.offsets.assign(k + 1, 0), out.members.assign((size_t)out.info.n_members + 1, 0);
+    std::vector<int32_t> lo(3 * k + 1), hi(3 * k + 1);
+    std::vector<double> cen(3 * k + 1);
+    const fiesta_hip_cluster_result r{out.label.data(), out.size.data(), out.root.data(), lo.data(), hi.data(), cen.data(), out.mask_or.data(),
+                                      out.key_min.data(), out.key_argmin.data(), out.offsets.data(), out.members.data()};
+    ck(fiesta_hip_cluster_voxels(h_, vp, mp, kp, n, connectivity, min_size, (int64_t)k, out.info.n_members, &r, &out.info));
+    out.label.resize((size_t)n), out.size.resize(k), out.root.resize(k), out.mask_or.resize(k), out.key_min.resize(k);
+    out.key_argmin.resize(k), out.members.resize((size_t)out.info.n_members);
+    for (size_t c = 0; c < k; ++c) {
+      out.box_lo.push_back(Eigen::Vector3i(lo[3 * c], lo[3 * c + 1], lo[3 * c + 2]));
+      out.box_hi.push_back(Eigen::Vector3i(hi[3 * c], hi[3 * c + 1], hi[3 * c + 2]));
+      out.centroid.push_back(Eigen::Vector3d(cen[3 * c], cen[3 * c + 1], cen[3 * c + 2]));
+    }
+    return out;
+  }
+  // GetFrontierVoxels and ClusterVoxels composed (both null: the whole map): the frontier voxels, their masks and their clusters
+  VoxelClusters GetFrontierClusters(const Eigen::Vector3i *lo, const Eigen::Vector3i *hi, double min_clearance, int32_t connectivity,
+                                    int32_t min_size, std::vector<Eigen::Vector3i> &vox, std::vector<uint8_t> *mask = nullptr) {
+    if ((lo == nullptr) != (hi == nullptr)) throw std::invalid_argument("GetFrontierClusters: lo and hi must both be given or both be null");
+    std::vector<uint8_t> own;
+    std::vector<uint8_t> &mk = mask ? *mask : own;
+    if (lo)
+      GetFrontierVoxels(*lo, *hi, min_clearance, vox, &mk);
+    else
+      GetFrontierVoxels(min_clearance, vox, &mk);
+    return ClusterVoxels(vox, &mk, nullptr, connectivity, min_size);
+  }
   // The reference's own getters (include/ESDFMap.h:144-145, src/ESDFMap.cpp:544-699).  The message types are template
   // parameters so that this header builds without ROS; sensor_msgs::PointCloud and visualization_msgs::Marker fit as
   // they are (fields used: header.frame_id, points[i].x/y/z, and for the marker id, type, action, scale, pose.orientation,

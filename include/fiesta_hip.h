@@ -648,6 +648,85 @@ int fiesta_hip_reach_paths_dev(fiesta_hip_map *m, const int32_t *cost_dev, const
                                const int32_t *targets_dev, int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span,
                                int64_t capacity, const fiesta_hip_reach_paths_result *result);
 
+/* ---- voxel clusters: the connected groups of a voxel list, with per-cluster statistics, on the device ----
+ * The step between fiesta_hip_get_frontier_voxels and fiesta_hip_reach_field: a planner does not visit frontier voxels, it visits
+ * FRONTIERS -- it groups the voxels, drops the specks of sensor noise, takes each group's centre and extent to place a viewpoint
+ * and asks which group is cheapest to reach.  Read-only: nothing of the map is read but its resolution and origin, so the call is
+ * the same for dense maps, shards and hash-block maps (there is no shard-group call; clusters do not cross shards).  No reference
+ * counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.
+ * Inputs: vox, n entries of 3 int32 map voxel coordinates in any order (typically the frontier call's output; the call does not
+ *   care what the voxels are); mask, nullable, one uint8 per entry (the frontier call's unknown-neighbour mask); key, nullable, one
+ *   int32 per entry (e.g. target_cost of fiesta_hip_reach_field); connectivity 6, 18 or 26; min_size >= 1.
+ * INVALID entry: any coordinate with |c| >= 2^20 - 1.  It belongs to no cluster and does not affect the others (three coordinates
+ *   and their +-1 neighbours then pack into one 64-bit key).
+ * Representative: the lowest entry index among the valid entries that name the same voxel.  Later duplicates receive their voxel's
+ *   label but count for nothing: not for size, sums, box, mask, key or members.
+ * Adjacency: two distinct voxels are adjacent if they differ by at most 1 per axis and in at most 1 / 2 / 3 axes for connectivity
+ *   6 / 18 / 26.  Component: a connected component of the distinct valid voxels under that relation.  Size: its number of distinct
+ *   voxels.  Root: the lowest entry index in it.
+ * Components with size < min_size are dropped; the kept ones are numbered 0 .. K - 1 in increasing root order -- a function of the
+ *   input list alone.
+ * Outputs; every pointer of the result struct is nullable, and so is the struct:
+ *   label       int32 per entry: the cluster id; -1 for an invalid entry and for an entry of a dropped component
+ *   per cluster k, entries k < cluster_capacity written:
+ *   size        int32
+ *   root        int64 entry index
+ *   box_lo / box_hi  3 int32 each, inclusive
+ *   centroid    3 f64, metres: ((double)sum_c / (double)size + 0.5) * resolution + origin[c], sum_c the exact int64 coordinate sum over
+ *               the representatives; each operation rounded once, in this order (that of fiesta_hip_reach_paths' waypoints_pos)
+ *   mask_or     uint8: the OR of the representatives' masks; 0 if mask is NULL
+ *   key_min     int32, key_argmin int64 entry index: the minimum of key over representatives with key >= 0 and the lowest entry index
+ *               that attains it; INT32_MAX and -1 if there is none or key is NULL.  So -1 ("not traversable") and every negative
+ *               key are ignored; an INT32_MAX key ("out of reach") is >= 0 and takes part.
+ *   offsets     int64, CSR: the representatives of cluster k occupy members[offsets[k] .. offsets[k + 1]).  The array holds
+ *               cluster_capacity + 1 entries; entries 0 .. min(K, cluster_capacity) are written.
+ *   members     int64 entry indices; entries below member_capacity are written.  The order inside a cluster's segment is unspecified,
+ *               the set is exact.
+ *   info        whatever the capacities (so a call with capacities 0 sizes the buffers): n_clusters = K; n_members, the number of
+ *               representatives in kept clusters (= offsets[K]); n_invalid, invalid entries; n_duplicates, valid entries that are
+ *               not their voxel's representative; n_dropped_clusters; largest, the size of the largest kept cluster (0: none).
+ *   Every value is an integer but the centroid: every output other than the order inside a member segment has the same bits for any
+ *   launch shape, scheduling and hash-table size, and the bits of fiesta_amd.cluster_model (the definition in plain Python).
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): n < 0 or n > 2^24, connectivity not 6, 18 or
+ *   26, min_size < 1, a negative capacity, vox NULL with n > 0, info NULL.  The scratch memory (a hash table of the next power of
+ *   two >= 2 n slots, union-find arrays, per-cluster accumulators) belongs to the map: allocated on first use, grown on demand,
+ *   freed by fiesta_hip_destroy.
+ * fiesta_hip_cluster_voxels      host arrays; stages through the path queries' buffers, runs, synchronises, copies back label and
+ *                                min(total, capacity) of each cluster array.
+ * fiesta_hip_cluster_voxels_dev  every array, and info, is a device pointer (the result struct itself is a host object).  n_dev,
+ *                                nullable: a device counter; the entry count is min(n, *n_dev), read on the device -- so
+ *                                fiesta_hip_get_frontier_voxels_dev feeds this call with its own counter and buffers and no host
+ *                                round trip.  n is then the capacity that sizes the scratch (and is what the whole-call errors
+ *                                test); label beyond the device count is left untouched.  Only enqueued on the map's stream:
+ *                                nothing data-dependent is read back. */
+typedef struct fiesta_hip_cluster_result { /* every pointer nullable */
+  int32_t *label;                          /* per entry */
+  int32_t *size;                           /* per cluster */
+  int64_t *root;                           /* per cluster */
+  int32_t *box_lo;                         /* per cluster x 3 */
+  int32_t *box_hi;                         /* per cluster x 3 */
+  double *centroid;                        /* per cluster x 3, metres */
+  uint8_t *mask_or;                        /* per cluster */
+  int32_t *key_min;                        /* per cluster */
+  int64_t *key_argmin;                     /* per cluster */
+  int64_t *offsets;                        /* cluster_capacity + 1 */
+  int64_t *members;                        /* member_capacity */
+} fiesta_hip_cluster_result;
+typedef struct fiesta_hip_cluster_info {
+  int64_t n_clusters;
+  int64_t n_members;
+  int64_t n_invalid;
+  int64_t n_duplicates;
+  int64_t n_dropped_clusters;
+  int64_t largest;
+} fiesta_hip_cluster_info;
+int fiesta_hip_cluster_voxels(fiesta_hip_map *m, const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, int32_t connectivity,
+                              int32_t min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *result,
+                              fiesta_hip_cluster_info *info);
+int fiesta_hip_cluster_voxels_dev(fiesta_hip_map *m, const int32_t *vox_dev, const uint8_t *mask_dev, const int32_t *key_dev, int64_t n,
+                                  const unsigned long long *n_dev, int32_t connectivity, int32_t min_size, int64_t cluster_capacity,
+                                  int64_t member_capacity, const fiesta_hip_cluster_result *result, fiesta_hip_cluster_info *info_dev);
+
 /* ---- whole-field access (tests, visualisation, checkpoints) ----
  * Dense dump in the reference's linear order; each output is nullable.
  *   d2      int32  squared voxel distance to the closest obstacle; -1 never observed; INT32_MAX observed
