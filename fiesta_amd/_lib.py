@@ -115,6 +115,30 @@ class ClusterInfo(C.Structure):
                 ("n_dropped_clusters", C.c_int64), ("largest", C.c_int64)]
 
 
+class ViewSet(C.Structure):
+    """fiesta_hip_view_set: the candidate views of fiesta_hip_view_coverage, explicit (pos, dir, group, n_views) or ring (centroid, ring, n_ring)"""
+    _fields_ = [("pos", C.c_void_p), ("dir", C.c_void_p), ("group", C.c_void_p), ("n_views", C.c_int64), ("centroid", C.c_void_p),
+                ("ring", C.c_void_p), ("n_ring", C.c_int64)]
+
+
+class ViewSensor(C.Structure):
+    """fiesta_hip_view_sensor"""
+    _fields_ = [("min_range", C.c_double), ("max_range", C.c_double), ("tan_h", C.c_double), ("tan_v", C.c_double),
+                ("min_clearance", C.c_double), ("block_mask", C.c_int32), ("flags", C.c_int32), ("min_visible", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class ViewResult(C.Structure):
+    """fiesta_hip_view_result: one array per output of fiesta_hip_view_coverage, every pointer nullable"""
+    _fields_ = [("view_class", C.c_void_p), ("n_in_view", C.c_void_p), ("n_visible", C.c_void_p), ("cover_count", C.c_void_p),
+                ("first_view", C.c_void_p), ("best_view", C.c_void_p), ("best_count", C.c_void_p)]
+
+
+class ViewInfo(C.Structure):
+    """fiesta_hip_view_info: the totals of one fiesta_hip_view_coverage call"""
+    _fields_ = [("n_usable", C.c_int64), ("n_pairs", C.c_int64), ("n_in_view", C.c_int64), ("n_visible", C.c_int64)]
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/fiesta_hip.h declares (used by the CPU export test)."""
     text = open(header_path).read()
@@ -220,6 +244,8 @@ def load():
         "fiesta_hip_reach_paths_dev": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
         "fiesta_hip_cluster_voxels": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, i64, vp, vp]),
         "fiesta_hip_cluster_voxels_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, i32, i64, i64, vp, vp]),
+        "fiesta_hip_view_coverage": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, vp]),
+        "fiesta_hip_view_coverage_dev": (C.c_int, [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp]),
         "fiesta_hip_get_occupancy_vox": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_get_occupancy_pos": (C.c_int, [vp, vp, i64, vp]),
         "fiesta_hip_download_field": (C.c_int, [vp, vp, vp, vp, vp]),

@@ -130,6 +130,34 @@ void cluster_args(fiesta_hip_map *m, const int32_t *vox, int64_t n, int32_t conn
   need(vox != nullptr || n == 0, "cluster_voxels: vox is null");
   need(m != nullptr, "null map handle");
 }
+// the whole-call errors of fiesta_hip_view_coverage[_dev] (include/fiesta_hip.h); none of them needs a device
+void view_args(fiesta_hip_map *m, const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups, int64_t n_members,
+               const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *s, const void *info) {
+  constexpr int64_t cap = 1ll << 24;
+  need(views != nullptr && s != nullptr, "view_coverage: views or sensor is null");
+  need(info != nullptr, "view_coverage: info is null");
+  need(n >= 0 && n <= cap, "view_coverage: the entry count must lie in 0 .. 2^24");
+  need(n_groups >= 0 && n_groups <= cap, "view_coverage: the group count must lie in 0 .. 2^24");
+  need(members == nullptr || (n_members >= 0 && n_members <= cap), "view_coverage: the member count must lie in 0 .. 2^24");  // (ignored without members)
+  need(vox != nullptr || n == 0, "view_coverage: vox is null");
+  need((views->pos != nullptr) != (views->centroid != nullptr), "view_coverage: exactly one view form (pos, or centroid and ring) must be given");
+  const bool omni = (s->flags & FIESTA_HIP_VIEW_OMNI) != 0;
+  if (views->pos) {
+    need(views->n_views >= 0 && views->n_views <= cap, "view_coverage: the view count must lie in 0 .. 2^24");
+    need(views->dir != nullptr || omni, "view_coverage: dir is null without FIESTA_HIP_VIEW_OMNI");
+  } else {
+    need(views->ring != nullptr && views->n_ring >= 0 && views->n_ring <= cap, "view_coverage: the ring form needs ring and 0 <= n_ring <= 2^24");
+    need((offsets ? n_groups : 1) * views->n_ring <= cap, "view_coverage: the view count must lie in 0 .. 2^24");
+  }
+  // (a NaN fails every comparison)
+  need(s->min_range >= 0 && s->max_range >= 0 && s->min_range <= s->max_range, "view_coverage: the range must satisfy 0 <= min_range <= max_range");
+  need(s->tan_h >= 0 && s->tan_v >= 0, "view_coverage: the tangents must be >= 0");
+  need(s->min_clearance == s->min_clearance, "view_coverage: min_clearance is NaN");
+  need(s->block_mask >= 0 && s->block_mask <= 7, "view_coverage: block_mask must be a subset of OCCUPIED | UNKNOWN | OUTSIDE");
+  need((s->flags & ~FIESTA_HIP_VIEW_OMNI) == 0, "view_coverage: unknown flag bits");
+  need(s->min_visible >= 1, "view_coverage: min_visible must be >= 1");
+  need(m != nullptr, "null map handle");
+}
 }  // namespace
 
 extern "C" {
@@ -640,6 +668,28 @@ int fiesta_hip_cluster_voxels_dev(fiesta_hip_map *m, const int32_t *vox_dev, con
       m->dense->cluster_voxels(vox_dev, mask_dev, key_dev, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, result, info_dev, true);
     else
       m->hash->cluster_voxels(vox_dev, mask_dev, key_dev, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, result, info_dev, true);
+  });
+}
+int fiesta_hip_view_coverage(fiesta_hip_map *m, const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups,
+                             int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor,
+                             const fiesta_hip_view_result *result, fiesta_hip_view_info *info) {
+  return guarded([&] {
+    view_args(m, vox, n, offsets, members, n_groups, n_members, views, sensor, info);
+    if (m->dense)
+      m->dense->view_coverage(vox, n, offsets, members, n_groups, nullptr, n_members, views, sensor, result, info, false);
+    else
+      m->hash->view_coverage(vox, n, offsets, members, n_groups, nullptr, n_members, views, sensor, result, info, false);
+  });
+}
+int fiesta_hip_view_coverage_dev(fiesta_hip_map *m, const int32_t *vox_dev, int64_t n, const int64_t *offsets_dev, const int64_t *members_dev,
+                                 int64_t n_groups, const int64_t *n_groups_dev, int64_t n_members, const fiesta_hip_view_set *views,
+                                 const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *result, fiesta_hip_view_info *info_dev) {
+  return guarded([&] {
+    view_args(m, vox_dev, n, offsets_dev, members_dev, n_groups, n_members, views, sensor, info_dev);
+    if (m->dense)
+      m->dense->view_coverage(vox_dev, n, offsets_dev, members_dev, n_groups, n_groups_dev, n_members, views, sensor, result, info_dev, true);
+    else
+      m->hash->view_coverage(vox_dev, n, offsets_dev, members_dev, n_groups, n_groups_dev, n_members, views, sensor, result, info_dev, true);
   });
 }
 int fiesta_hip_get_slice(fiesta_hip_map *m, int32_t z_vox, double *out) {

@@ -29,6 +29,7 @@
 #include "reach_kernels.hpp"
 #include "reach_path_kernels.hpp"
 #include "cluster_kernels.hpp"
+#include "view_kernels.hpp"
 #include "ft_kernels.hpp"
 #include "nn_kernels.hpp"
 #include "mask_kernels.hpp"
@@ -2669,6 +2670,21 @@ void DenseMap::cluster_voxels(const int32_t *vox, const uint8_t *mask, const int
   use_device();
   cluster_voxels_run(stream_, cluster_, path_in_, path_out_, g_.res, g_.org,
                      ClusterArgs{vox, mask, key, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, r, info, dev});
+}
+
+// fiesta_hip_view_coverage[_dev] (view_kernels.hpp); arguments checked by the caller.  The ray query's source, the frontier call's
+// distance (local array coordinates: a FREE voxel lies inside the array).
+void DenseMap::view_coverage(const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups, const int64_t *n_groups_dev,
+                             int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *r,
+                             fiesta_hip_view_info *info, bool dev) {
+  use_device();
+  if (g_.sharded) {  // (the halo exchange does not keep obsbits_ in ghost cells: see frontier_voxels)
+    hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
+    FIESTA_HIP_CHECK(hipGetLastError());
+  }
+  const ViewSource<DenseRaySource, DenseFrontierDist> vs{DenseRaySource(g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_),
+                                                         DenseFrontierDist{g_, (const vox_t *)coc_}, {g_.gx0, g_.gy0, g_.gz0}};
+  view_coverage_run(stream_, view_, path_in_, path_out_, vs, ViewArgs{vox, n, offsets, members, n_groups, n_groups_dev, n_members, views, sensor, r, info, dev});
 }
 
 // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller

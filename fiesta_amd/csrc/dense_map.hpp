@@ -69,6 +69,16 @@ struct ClusterScratch {
   DevBuf<uint32_t> mor;
 };
 
+// scratch of fiesta_hip_view_coverage (view_kernels.hpp), owned by a map: the ring form's expanded views, the per-view pair counts
+// and their scan, the per-view and per-group accumulators and four counters; O(views + groups), grown on demand, freed with the map
+struct ViewScratch {
+  DevBuf<int64_t> P;
+  DevBuf<int32_t> vin, vvis, group;
+  DevBuf<unsigned long long> best, ctr;
+  DevBuf<double> pos, dir;
+  DevBuf<unsigned char> call;  // one ViewCall
+};
+
 // Device-side counters, one 64-bit word each.
 enum Counter {
   C_TOUCHED = 0,   // length of the touched-voxel list (the reference's occupancy_queue_)
@@ -190,6 +200,10 @@ class DenseMap {
   void cluster_voxels(const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const unsigned long long *n_dev, int connectivity,
                       int min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *r,
                       fiesta_hip_cluster_info *info, bool dev);
+  // fiesta_hip_view_coverage[_dev] (view_kernels.hpp); arguments checked by the caller
+  void view_coverage(const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups, const int64_t *n_groups_dev,
+                     int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *r,
+                     fiesta_hip_view_info *info, bool dev);
   int64_t count_no_obstacle();
   void slice_distances(int z_vox, double *out);        // nx * ny doubles, x-major
   // GetPointCloud / GetSliceMarker as arrays; both return the total count (may exceed cap), order unspecified
@@ -372,6 +386,7 @@ class DenseMap {
   DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path and ray queries: staged inputs, plan / piece records, staged outputs
   ReachScratch reach_;
   ClusterScratch cluster_;
+  ViewScratch view_;
   // raycast front-end state (per-frame stamp arrays = Fiesta::set_occ_/set_free_, include/Fiesta.h:107-110;
   // per-ray traversal lists), lazily allocated by raycast.hip
   struct RaycastState;

@@ -24,6 +24,7 @@
 #include "reach_kernels.hpp"
 #include "reach_path_kernels.hpp"
 #include "cluster_kernels.hpp"
+#include "view_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
@@ -1628,6 +1629,19 @@ void HashMap::cluster_voxels(const int32_t *vox, const uint8_t *mask, const int3
   use_device();
   cluster_voxels_run(stream_, cluster_, path_in_, path_out_, g_.res, g_.org,
                      ClusterArgs{vox, mask, key, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, r, info, dev});
+}
+
+// fiesta_hip_view_coverage[_dev] (view_kernels.hpp); arguments checked by the caller.  The ray query's source, the frontier call's
+// distance (map voxel coordinates).  Every page answers, resident or parked.
+void HashMap::view_coverage(const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups, const int64_t *n_groups_dev,
+                            int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *r,
+                            fiesta_hip_view_info *info, bool dev) {
+  use_device();
+  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
+  const ViewSource<HashRaySource, HashFrontierPages> vs{
+      HashRaySource{ray_geom(g_), g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p},
+      HashFrontierPages{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}, {0, 0, 0}};
+  view_coverage_run(stream_, view_, path_in_, path_out_, vs, ViewArgs{vox, n, offsets, members, n_groups, n_groups_dev, n_members, views, sensor, r, info, dev});
 }
 
 // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller.  Every page answers, resident or parked.

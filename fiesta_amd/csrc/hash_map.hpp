@@ -105,6 +105,10 @@ class HashMap {
   void cluster_voxels(const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const unsigned long long *n_dev, int connectivity,
                       int min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *r,
                       fiesta_hip_cluster_info *info, bool dev);
+  // fiesta_hip_view_coverage[_dev] (view_kernels.hpp); arguments checked by the caller
+  void view_coverage(const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups, const int64_t *n_groups_dev,
+                     int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *r,
+                     fiesta_hip_view_info *info, bool dev);
   void synchronize();
 
  private:
@@ -187,6 +191,7 @@ class HashMap {
   DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path and ray queries: staged inputs, plan / piece records, staged outputs
   ReachScratch reach_;
   ClusterScratch cluster_;
+  ViewScratch view_;
 };
 
 void raycast_single(const double *start, const double *end, const double *minv, const double *maxv, double *out,

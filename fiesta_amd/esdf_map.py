@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterInfo, ClusterResult, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachPathsResult, ReachResult, Stats, check
+from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachPathsResult, ReachResult, Stats, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -44,6 +44,11 @@ PATH_FIELDS = (("min_dist", np.float64, ()), ("min_index", np.int64, ()), ("min_
 # the per-cluster arrays of fiesta_hip_cluster_result, in struct order (label before, offsets and members after them)
 CLUSTER_FIELDS = (("size", np.int32, ()), ("root", np.int64, ()), ("box_lo", np.int32, (3,)), ("box_hi", np.int32, (3,)),
                   ("centroid", np.float64, (3,)), ("mask_or", np.uint8, ()), ("key_min", np.int32, ()), ("key_argmin", np.int64, ()))
+# the arrays of fiesta_hip_view_result, in struct order: (name, dtype, which count sizes it)
+VIEW_FIELDS = (("view_class", np.uint8, "views"), ("n_in_view", np.int32, "views"), ("n_visible", np.int32, "views"),
+               ("cover_count", np.int32, "entries"), ("first_view", np.int32, "entries"), ("best_view", np.int64, "groups"),
+               ("best_count", np.int32, "groups"))
+VIEW_INFO_KEYS = ("n_usable", "n_pairs", "pairs_in_view", "pairs_visible")   # fiesta_hip_view_info, as the dicts name it
 PATH_MAX_RATIO = 2.0 ** 24  # a segment with L / step above this makes its path invalid
 
 
@@ -354,6 +359,8 @@ class ESDFMap:
         self.mode = mode
         self.device = int(device)
         self._frontier_buffers, self._frontier_capacity = None, 1 << 16   # FrontierClusters' device buffers
+        self._view_cluster_capacity = 1024                                # FrontierViews: clusters that get views
+        self._view_ring = None                                            # FrontierViews: (the ring's bytes, its device copy)
         self.resolution = float(resolution)
         self.origin = _d3(origin)
         # PosInMap's range of an array-mode map as the library adds it up (ray_query_model's pos_range); a shard: the global map's
@@ -848,6 +855,23 @@ class ESDFMap:
                                                       int(min_size), int(cluster_capacity), int(member_capacity), C.byref(res),
                                                       C.c_void_p(info_dev_ptr or None)))
 
+    def _frontier_alloc(self) -> dict:
+        """the device buffers FrontierClusters and FrontierViews share (torch tensors of self._frontier_capacity entries), made on demand"""
+        import torch
+        b = self._frontier_buffers
+        if b is None:
+            dev = torch.device("cuda", self.device)
+            cap = self._frontier_capacity
+            b = {"vox": torch.empty((cap, 3), dtype=torch.int32, device=dev), "mask": torch.empty(cap, dtype=torch.uint8, device=dev),
+                 "label": torch.empty(cap, dtype=torch.int32, device=dev), "members": torch.empty(cap, dtype=torch.int64, device=dev),
+                 "offsets": torch.empty(cap + 1, dtype=torch.int64, device=dev),
+                 "head": torch.zeros(8, dtype=torch.int64, device=dev)}   # [0]: the frontier counter, [1 .. 6]: the cluster info
+            for name, dtype, shape in CLUSTER_FIELDS:
+                b[name] = torch.empty((cap,) + shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
+            torch.cuda.synchronize(dev)   # (the map's stream does not wait for torch's)
+            self._frontier_buffers = b
+        return b
+
     def FrontierClusters(self, lo=None, hi=None, min_clearance=0.0, connectivity=26, min_size=1) -> dict:
         """GetFrontierVoxels and ClusterVoxels as one chain on the device: the frontier sweep writes into device buffers this object
         keeps (torch tensors, grown on demand), its device counter feeds the clustering, and the host waits ONCE, at the end, before
@@ -858,17 +882,7 @@ class ESDFMap:
             raise ValueError("lo and hi must both be given or both be None")
         dev = torch.device("cuda", self.device)
         while True:
-            b = self._frontier_buffers
-            if b is None:
-                cap = self._frontier_capacity
-                b = {"vox": torch.empty((cap, 3), dtype=torch.int32, device=dev), "mask": torch.empty(cap, dtype=torch.uint8, device=dev),
-                     "label": torch.empty(cap, dtype=torch.int32, device=dev), "members": torch.empty(cap, dtype=torch.int64, device=dev),
-                     "offsets": torch.empty(cap + 1, dtype=torch.int64, device=dev),
-                     "head": torch.zeros(8, dtype=torch.int64, device=dev)}   # [0]: the frontier counter, [1 .. 6]: the cluster info
-                for name, dtype, shape in CLUSTER_FIELDS:
-                    b[name] = torch.empty((cap,) + shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
-                torch.cuda.synchronize(dev)   # (the map's stream does not wait for torch's)
-                self._frontier_buffers = b
+            b = self._frontier_alloc()
             cap = b["label"].shape[0]
             head = b["head"].data_ptr()
             self.GetFrontierVoxelsDevice(lo, hi, min_clearance, b["vox"].data_ptr(), b["mask"].data_ptr(), cap, head)
@@ -890,6 +904,164 @@ class ESDFMap:
         out["members"] = b["members"][:info["n_members"]].cpu().numpy()
         out["vox"], out["mask"], out["label"] = b["vox"][:n].cpu().numpy(), b["mask"][:n].cpu().numpy(), b["label"][:n].cpu().numpy()
         out.update(info)
+        return out
+
+    @staticmethod
+    def _view_sensor(min_range, max_range, tan_h, tan_v, block_mask, omni, min_clearance, min_visible):
+        return ViewSensor(float(min_range), float(max_range), float(tan_h), float(tan_v), float(min_clearance), int(block_mask),
+                          1 if omni else 0, int(min_visible), 0)
+
+    def ViewCoverage(self, vox, pos=None, dir=None, group=None, centroid=None, ring=None, offsets=None, members=None, min_range=0.0,
+                     max_range=np.inf, tan_h=np.inf, tan_v=np.inf, block_mask=1, omni=False, min_clearance=0.0, min_visible=1) -> dict:
+        """fiesta_hip_view_coverage: candidate views against the target voxels `vox` ((n, 3) map voxels) of their group.  Views: pos
+        (V, 3) metres, dir (V, 2) the horizontal unit forward vector, group (V,) -- or centroid (n_groups, 3) and ring (M, 5; see
+        fiesta_amd.view_ring): ring j around centroid k is view k * M + j of group k.  offsets / members: the CSR pair of ClusterVoxels
+        (both optional: one group of all entries; offsets alone: segments of vox itself).  Sensor: range in metres, the tangents of
+        the half angles, block_mask (RAY_OCCUPIED | RAY_UNKNOWN | RAY_OUTSIDE: what ends a ray), omni (no forward direction),
+        min_clearance (a view must stand this far from obstacles), min_visible (below it a view is nobody's best).  Returns per view
+        view_class, n_in_view, n_visible (-1: unusable view); per entry cover_count, first_view; per group best_view, best_count; and
+        n_usable, n_pairs, pairs_in_view, pairs_visible; fiesta_amd.view_coverage_model is the definition"""
+        v = np.ascontiguousarray(vox, dtype=np.int32).reshape(-1, 3)
+        n = len(v)
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        mem = None if members is None else np.ascontiguousarray(members, dtype=np.int64).reshape(-1)
+        G = 1 if off is None else len(off) - 1
+        if G < 0:
+            raise ValueError("offsets needs n_groups + 1 entries")
+        vs = ViewSet()
+        keep = []
+        if pos is not None:
+            ps = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+            V = len(ps)
+            dr = None if dir is None else np.ascontiguousarray(dir, dtype=np.float64).reshape(-1, 2)
+            gr = None if group is None else np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+            if (dr is not None and len(dr) != V) or (gr is not None and len(gr) != V):
+                raise ValueError("dir and group need one row per view")
+            # (a zero-length array still has to read as "given": the library tells the two forms apart by the pointers)
+            one = np.zeros(3)
+            vs.pos, vs.n_views = (ps if V else one).ctypes.data, V
+            vs.dir = None if dr is None else (dr if V else one).ctypes.data
+            vs.group = None if gr is None or not V else gr.ctypes.data
+            keep += [ps, dr, gr, one]
+        if centroid is not None:
+            cn = np.ascontiguousarray(centroid, dtype=np.float64).reshape(-1, 3)
+            rg = np.ascontiguousarray(ring if ring is not None else np.zeros((0, 5)), dtype=np.float64).reshape(-1, 5)
+            if len(cn) != G:
+                raise ValueError("centroid needs one row per group")
+            one = np.zeros(5)
+            vs.centroid, vs.ring, vs.n_ring = (cn if G else one).ctypes.data, (rg if len(rg) else one).ctypes.data if ring is not None else None, len(rg)
+            V = G * len(rg)
+            keep += [cn, rg, one]
+        if pos is None and centroid is None:
+            V = 0
+        sizes = {"views": V, "entries": n, "groups": G}
+        out = {name: np.empty(sizes[size], dtype) for name, dtype, size in VIEW_FIELDS}
+        res = ViewResult(*[out[name].ctypes.data for name, _, _ in VIEW_FIELDS])
+        sn = self._view_sensor(min_range, max_range, tan_h, tan_v, block_mask, omni, min_clearance, min_visible)
+        info = ViewInfo()
+        check(self._lib.fiesta_hip_view_coverage(self._h, _p(v) if n else None, n, _p(off), None if mem is None else _p(mem if len(mem) else np.zeros(1, np.int64)), G,
+                                                 0 if mem is None else len(mem), C.byref(vs), C.byref(sn), C.byref(res), C.byref(info)))
+        out.update(zip(VIEW_INFO_KEYS, (int(info.n_usable), int(info.n_pairs), int(info.n_in_view), int(info.n_visible))))
+        return out
+
+    def ViewCoverageDevice(self, vox_dev_ptr: int, n: int, info_dev_ptr: int, pos_dev_ptr: int = 0, dir_dev_ptr: int = 0, group_dev_ptr: int = 0,
+                           n_views: int = 0, centroid_dev_ptr: int = 0, ring_dev_ptr: int = 0, n_ring: int = 0, offsets_dev_ptr: int = 0,
+                           members_dev_ptr: int = 0, n_groups: int = 1, n_groups_dev_ptr: int = 0, n_members: int = 0, min_range=0.0,
+                           max_range=np.inf, tan_h=np.inf, tan_v=np.inf, block_mask=1, omni=False, min_clearance=0.0, min_visible=1, out=None):
+        """fiesta_hip_view_coverage_dev: every array resident on the device (`out` maps field names of fiesta_hip_view_result to device
+        pointers, missing fields are not written; info_dev_ptr: a device fiesta_hip_view_info, four int64).  n_groups_dev_ptr: a
+        device int64, the effective group count is min(n_groups, that) -- ClusterVoxelsDevice's info.  Only enqueued on the map's stream"""
+        out = out or {}
+        vs = ViewSet(pos_dev_ptr or None, dir_dev_ptr or None, group_dev_ptr or None, int(n_views), centroid_dev_ptr or None, ring_dev_ptr or None,
+                     int(n_ring))
+        res = ViewResult(*[int(out.get(name, 0)) or None for name, _ in ViewResult._fields_])
+        sn = self._view_sensor(min_range, max_range, tan_h, tan_v, block_mask, omni, min_clearance, min_visible)
+        check(self._lib.fiesta_hip_view_coverage_dev(self._h, C.c_void_p(vox_dev_ptr or None), int(n), C.c_void_p(offsets_dev_ptr or None),
+                                                     C.c_void_p(members_dev_ptr or None), int(n_groups), C.c_void_p(n_groups_dev_ptr or None),
+                                                     int(n_members), C.byref(vs), C.byref(sn), C.byref(res), C.c_void_p(info_dev_ptr or None)))
+
+    def FrontierViews(self, lo=None, hi=None, min_clearance=0.0, connectivity=26, min_size=1, ring=None, min_range=0.0, max_range=np.inf,
+                      tan_h=np.inf, tan_v=np.inf, block_mask=1, omni=False, view_clearance=0.0, min_visible=1) -> dict:
+        """GetFrontierVoxels, ClusterVoxels and ViewCoverage (ring form: `ring` around every cluster's centroid, against the cluster's
+        own members) as one chain on the device, in FrontierClusters' buffers: the frontier counter feeds the clustering, the cluster
+        count and the CSR pair feed the coverage, and the host waits ONCE, at the end -- after a wait for torch's stream when a new ring
+        was uploaded or buffers were made (the first call with a ring), and unless the buffers turn out too small for the
+        frontier or the clusters (the first call, a frontier that grew by more than a quarter): then the chain runs a second time.
+        Returns everything FrontierClusters returns and, for the views k * len(ring) + j, view_class, n_in_view, n_visible, view_pos, view_dir; per frontier voxel cover_count,
+        first_view; per cluster best_view, best_count, best_pos, best_dir (NaN where best_view is -1); and ViewCoverage's totals"""
+        import torch
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        rg = np.ascontiguousarray(ring, dtype=np.float64).reshape(-1, 5)
+        M = len(rg)
+        dev = torch.device("cuda", self.device)
+        fresh = self._view_ring is None or self._view_ring[0] != rg.tobytes()    # (the uploaded ring is kept: a planner reuses it)
+        if fresh:
+            self._view_ring = (rg.tobytes(), torch.from_numpy(rg).to(dev) if M else torch.zeros((1, 5), dtype=torch.float64, device=dev))
+        ring_dev = self._view_ring[1]
+        while True:
+            b = self._frontier_alloc()
+            cap = b["label"].shape[0]
+            # the clusters get a capacity of their own (they are few): it sizes the views, kcap * len(ring) of them
+            kcap = min(cap, self._view_cluster_capacity)
+            if kcap * max(M, 1) > 1 << 24:
+                raise ValueError("more than 2^24 views: use a smaller ring, a larger min_size or a smaller box")
+            vb = b.get("views")
+            if vb is None or vb["n_visible"].shape[0] < kcap * max(M, 1):
+                nv = kcap * max(M, 1)
+                vb = {"view_class": torch.empty(nv, dtype=torch.uint8, device=dev), "n_in_view": torch.empty(nv, dtype=torch.int32, device=dev),
+                      "n_visible": torch.empty(nv, dtype=torch.int32, device=dev), "cover_count": torch.empty(cap, dtype=torch.int32, device=dev),
+                      "first_view": torch.empty(cap, dtype=torch.int32, device=dev), "best_view": torch.empty(cap, dtype=torch.int64, device=dev),
+                      "best_count": torch.empty(cap, dtype=torch.int32, device=dev), "info": torch.zeros(4, dtype=torch.int64, device=dev)}
+                b["views"] = vb
+                fresh = True
+            if fresh:
+                torch.cuda.synchronize(dev)   # (the map's stream does not wait for torch's: the ring upload, fresh buffers)
+                fresh = False
+            head = b["head"].data_ptr()
+            self.GetFrontierVoxelsDevice(lo, hi, min_clearance, b["vox"].data_ptr(), b["mask"].data_ptr(), cap, head)
+            outs = {name: b[name].data_ptr() for name, _ in ClusterResult._fields_}
+            self.ClusterVoxelsDevice(b["vox"].data_ptr(), cap, head + 8, mask_dev_ptr=b["mask"].data_ptr(), n_dev_ptr=head,
+                                     connectivity=connectivity, min_size=min_size, cluster_capacity=kcap, member_capacity=cap, out=outs)
+            # (kcap groups; the device count -- info.n_clusters at head + 8 -- cuts them down to the clusters there are)
+            self.ViewCoverageDevice(b["vox"].data_ptr(), cap, vb["info"].data_ptr(), centroid_dev_ptr=b["centroid"].data_ptr(),
+                                    ring_dev_ptr=ring_dev.data_ptr(), n_ring=M, offsets_dev_ptr=b["offsets"].data_ptr(),
+                                    members_dev_ptr=b["members"].data_ptr(), n_groups=kcap, n_groups_dev_ptr=head + 8, n_members=cap,
+                                    min_range=min_range, max_range=max_range, tan_h=tan_h, tan_v=tan_v, block_mask=block_mask, omni=omni,
+                                    min_clearance=view_clearance, min_visible=min_visible,
+                                    out={name: vb[name].data_ptr() for name, _ in ViewResult._fields_})
+            self.synchronize()
+            h = b["head"].cpu().numpy()
+            n = int(h[0])
+            if n > 1 << 24:
+                raise ValueError("the frontier holds more than 2^24 voxels: cluster it box by box")
+            if n > cap:
+                self._frontier_buffers, self._frontier_capacity = None, min(max(n + n // 4, 1024), 1 << 24)
+                continue
+            if int(h[1]) > kcap:
+                self._view_cluster_capacity = int(h[1]) + int(h[1]) // 4
+                continue
+            break
+        info = {name: int(h[1 + i]) for i, (name, _) in enumerate(ClusterInfo._fields_)}
+        k = info["n_clusters"]
+        out = {name: b[name][:k].cpu().numpy() for name, _, _ in CLUSTER_FIELDS}
+        out["offsets"] = b["offsets"][:k + 1].cpu().numpy()
+        out["members"] = b["members"][:info["n_members"]].cpu().numpy()
+        out["vox"], out["mask"], out["label"] = b["vox"][:n].cpu().numpy(), b["mask"][:n].cpu().numpy(), b["label"][:n].cpu().numpy()
+        out.update(info)
+        for name in ("view_class", "n_in_view", "n_visible"):
+            out[name] = vb[name][:k * M].cpu().numpy()
+        for name in ("cover_count", "first_view"):
+            out[name] = vb[name][:n].cpu().numpy()
+        for name in ("best_view", "best_count"):
+            out[name] = vb[name][:k].cpu().numpy()
+        out.update(zip(VIEW_INFO_KEYS, (int(x) for x in vb["info"].cpu().numpy())))
+        out["view_pos"] = (out["centroid"][:, None, :] + rg[None, :, :3]).reshape(-1, 3)
+        out["view_dir"] = np.broadcast_to(rg[None, :, 3:5], (k, M, 2)).reshape(-1, 2).copy()
+        has = out["best_view"] >= 0
+        at = np.where(has, out["best_view"], 0)
+        out["best_pos"] = np.where(has[:, None], out["view_pos"][at] if k * M else np.zeros((k, 3)), np.nan)
+        out["best_dir"] = np.where(has[:, None], out["view_dir"][at] if k * M else np.zeros((k, 2)), np.nan)
         return out
 
     def count_no_obstacle(self) -> int:

@@ -17,6 +17,7 @@
 //   * closest-obstacle ids are tie-equivalent, not FIFO-order-identical (parity contract).
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -434,6 +435,90 @@ class ESDFMap {
       GetFrontierVoxels(min_clearance, vox, &mk);
     return ClusterVoxels(vox, &mk, nullptr, connectivity, min_size);
   }
+  // View coverage (fiesta_hip_view_coverage, include/fiesta_hip.h): candidate viewpoints against the target voxels of their group --
+  // per view how many targets lie in the sensor's range and field of view and how many of those it sees (no voxel of
+  // sensor.block_mask before the target), per target how many views see it and the first of them, per group the best view.
+  // offsets / members (both nullable): the CSR pair of ClusterVoxels; without them all targets are one group.
+  struct ViewPose {
+    Eigen::Vector3d pos;  // metres
+    double dx, dy;        // the horizontal unit forward vector: cos / sin of the yaw
+    int32_t group;
+  };
+  typedef std::array<double, 5> RingRow;  // ox, oy, oz, dx, dy
+  struct ViewCoverageResult {
+    std::vector<uint8_t> view_class;            // per view from here on
+    std::vector<int32_t> n_in_view, n_visible;  // -1: unusable view
+    std::vector<int32_t> cover_count, first_view;  // per target
+    std::vector<int64_t> best_view;                // per group; -1: none
+    std::vector<int32_t> best_count;
+    fiesta_hip_view_info info{};
+  };
+  static fiesta_hip_view_sensor ViewSensor(double min_range, double max_range, double tan_h, double tan_v, int32_t block_mask = FIESTA_HIP_RAY_OCCUPIED,
+                                           bool omni = false, double min_clearance = 0.0, int32_t min_visible = 1) {
+    return fiesta_hip_view_sensor{min_range, max_range, tan_h, tan_v, min_clearance, block_mask, omni ? FIESTA_HIP_VIEW_OMNI : 0, min_visible, 0};
+  }
+  // a ring of view offsets around a centre, looking back at it: per radius, height and angle (r cos phi, r sin phi, h, -cos phi, -sin phi)
+  static std::vector<RingRow> ViewRing(const std::vector<double> &radii, int n_angles, const std::vector<double> &heights) {
+    std::vector<RingRow> ring;
+    for (double r : radii)
+      for (double h : heights)
+        for (int i = 0; i < n_angles; ++i) {
+          const double phi = 2.0 * 3.141592653589793 * i / n_angles, c = std::cos(phi), s = std::sin(phi);
+          ring.push_back(RingRow{r * c, r * s, h, -c, -s});
+        }
+    return ring;
+  }
+  ViewCoverageResult ViewCoverage(const std::vector<Eigen::Vector3i> &vox, const std::vector<ViewPose> &views, const fiesta_hip_view_sensor &sensor,
+                                  const std::vector<int64_t> *offsets = nullptr, const std::vector<int64_t> *members = nullptr) {
+    std::vector<double> pos(3 * views.size() + 1), dir(2 * views.size() + 1);  // (one spare entry: never a null pointer)
+    std::vector<int32_t> group(views.size() + 1);
+    for (size_t i = 0; i < views.size(); ++i) {
+      for (int c = 0; c < 3; ++c) pos[3 * i + c] = views[i].pos(c);
+      dir[2 * i] = views[i].dx, dir[2 * i + 1] = views[i].dy, group[i] = views[i].group;
+    }
+    const fiesta_hip_view_set set{pos.data(), dir.data(), group.data(), (int64_t)views.size(), nullptr, nullptr, 0};
+    return view_coverage(vox, set, (int64_t)views.size(), sensor, offsets, members);
+  }
+  // ring form: view k * ring.size() + j stands at centroid[k] + ring[j]'s offset, looks along ring[j]'s direction and belongs to group k
+  ViewCoverageResult ViewCoverage(const std::vector<Eigen::Vector3i> &vox, const std::vector<Eigen::Vector3d> &centroid, const std::vector<RingRow> &ring,
+                                  const fiesta_hip_view_sensor &sensor, const std::vector<int64_t> *offsets = nullptr,
+                                  const std::vector<int64_t> *members = nullptr) {
+    if (centroid.size() != (offsets ? offsets->size() - 1 : 1)) throw std::invalid_argument("ViewCoverage: one centroid per group");
+    std::vector<double> cen(3 * centroid.size() + 1), rg(5 * ring.size() + 1);
+    for (size_t k = 0; k < centroid.size(); ++k)
+      for (int c = 0; c < 3; ++c) cen[3 * k + c] = centroid[k](c);
+    for (size_t j = 0; j < ring.size(); ++j)
+      for (int c = 0; c < 5; ++c) rg[5 * j + c] = ring[j][c];
+    const fiesta_hip_view_set set{nullptr, nullptr, nullptr, 0, cen.data(), rg.data(), (int64_t)ring.size()};
+    return view_coverage(vox, set, (int64_t)(centroid.size() * ring.size()), sensor, offsets, members);
+  }
+  // GetFrontierClusters and the ring form of ViewCoverage composed: the clusters of the frontier, and for every cluster the best of
+  // the ring's poses around its centroid against its own members (best_pos / best_dx / best_dy; coverage.best_view -1: none)
+  struct FrontierViewSet {
+    VoxelClusters clusters;
+    ViewCoverageResult coverage;
+    std::vector<Eigen::Vector3d> best_pos;
+    std::vector<double> best_dx, best_dy;
+  };
+  FrontierViewSet GetFrontierViews(const Eigen::Vector3i *lo, const Eigen::Vector3i *hi, double min_clearance, int32_t connectivity, int32_t min_size,
+                                   const std::vector<RingRow> &ring, const fiesta_hip_view_sensor &sensor, std::vector<Eigen::Vector3i> &vox,
+                                   std::vector<uint8_t> *mask = nullptr) {
+    FrontierViewSet out;
+    out.clusters = GetFrontierClusters(lo, hi, min_clearance, connectivity, min_size, vox, mask);
+    out.coverage = ViewCoverage(vox, out.clusters.centroid, ring, sensor, &out.clusters.offsets, &out.clusters.members);
+    for (size_t k = 0; k < out.clusters.count(); ++k) {
+      const int64_t b = out.coverage.best_view[k];
+      const double nan = std::nan("");
+      if (b < 0) {
+        out.best_pos.push_back(Eigen::Vector3d(nan, nan, nan)), out.best_dx.push_back(nan), out.best_dy.push_back(nan);
+        continue;
+      }
+      const RingRow &r = ring[(size_t)b % ring.size()];
+      const Eigen::Vector3d &c = out.clusters.centroid[k];
+      out.best_pos.push_back(Eigen::Vector3d(c(0) + r[0], c(1) + r[1], c(2) + r[2])), out.best_dx.push_back(r[3]), out.best_dy.push_back(r[4]);
+    }
+    return out;
+  }
   // The reference's own getters (include/ESDFMap.h:144-145, src/ESDFMap.cpp:544-699).  The message types are template
   // parameters so that this header builds without ROS; sensor_msgs::PointCloud and visualization_msgs::Marker fit as
   // they are (fields used: header.frame_id, points[i].x/y/z, and for the marker id, type, action, scale, pose.orientation,
@@ -552,6 +637,28 @@ class ESDFMap {
     ck(fiesta_hip_grid_size(h_, gs_));
     ck(fiesta_hip_grid_total_size(h_, &n));
     grid_total_size_ = (int)n;
+  }
+
+  ViewCoverageResult view_coverage(const std::vector<Eigen::Vector3i> &vox, const fiesta_hip_view_set &set, int64_t n_views,
+                                   const fiesta_hip_view_sensor &sensor, const std::vector<int64_t> *offsets, const std::vector<int64_t> *members) {
+    Flush();
+    if (offsets && offsets->empty()) throw std::invalid_argument("ViewCoverage: offsets needs n_groups + 1 entries");
+    const int64_t n = (int64_t)vox.size(), groups = offsets ? (int64_t)offsets->size() - 1 : 1;
+    std::vector<int32_t> v;
+    for (const auto &p : vox) v.insert(v.end(), {p(0), p(1), p(2)});
+    ViewCoverageResult out;
+    out.view_class.assign((size_t)n_views + 1, 0), out.n_in_view.assign((size_t)n_views + 1, 0), out.n_visible.assign((size_t)n_views + 1, 0);
+    out.cover_count.assign((size_t)n + 1, 0), out.first_view.assign((size_t)n + 1, 0);
+    out.best_view.assign((size_t)groups + 1, 0), out.best_count.assign((size_t)groups + 1, 0);
+    const fiesta_hip_view_result r{out.view_class.data(), out.n_in_view.data(), out.n_visible.data(), out.cover_count.data(), out.first_view.data(),
+                                   out.best_view.data(), out.best_count.data()};
+    const int64_t none = 0;  // (an empty member list is still a member list: never a null pointer)
+    ck(fiesta_hip_view_coverage(h_, v.empty() ? nullptr : v.data(), n, offsets ? offsets->data() : nullptr,
+                                members ? (members->empty() ? &none : members->data()) : nullptr, groups, members ? (int64_t)members->size() : 0, &set, &sensor,
+                                &r, &out.info));
+    out.view_class.resize((size_t)n_views), out.n_in_view.resize((size_t)n_views), out.n_visible.resize((size_t)n_views);
+    out.cover_count.resize((size_t)n), out.first_view.resize((size_t)n), out.best_view.resize((size_t)groups), out.best_count.resize((size_t)groups);
+    return out;
   }
   static void ck(int status) {
     if (status != FIESTA_HIP_OK) throw std::runtime_error(std::string("fiesta::ESDFMap: ") + fiesta_hip_last_error());

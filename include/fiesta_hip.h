@@ -727,6 +727,98 @@ int fiesta_hip_cluster_voxels_dev(fiesta_hip_map *m, const int32_t *vox_dev, con
                                   const unsigned long long *n_dev, int32_t connectivity, int32_t min_size, int64_t cluster_capacity,
                                   int64_t member_capacity, const fiesta_hip_cluster_result *result, fiesta_hip_cluster_info *info_dev);
 
+/* ---- view coverage: which target voxels would a sensor at each candidate viewpoint see, per view, per target and per group ----
+ * The step after fiesta_hip_cluster_voxels: a frontier planner samples candidate poses around each cluster, counts how many of the
+ * cluster's voxels each pose would see -- inside the sensor's range and field of view, nothing blocking the ray -- and keeps the
+ * best pose per cluster.  One fused call instead of building, culling, uploading and reducing every (view, member) segment by
+ * hand around fiesta_hip_ray_query.  Read-only; dense maps, shards (a shard answers for its own array, like the ray query; there is
+ * no shard-group call) and hash-block maps.  No reference counterpart.  fiesta_hip_version() is still 101: detect these two calls
+ * by symbol lookup.
+ * Targets: vox, n entries of 3 int32 map voxel coordinates, n <= 2^24.  The centre of entry i is
+ *   p[c] = ((double)vox[3 i + c] + 0.5) * resolution + origin[c]   (the order of the cluster centroid and of waypoints_pos).
+ * Groups (the CSR pair of the cluster call): offsets, int64, n_groups + 1 entries, and members, int64 entry indices into vox,
+ *   n_members of them; both nullable.  Every offset is clamped into [0, n_members] when it is read; group g lists
+ *   members[lo .. hi) with lo = offsets[g], hi = offsets[g + 1] (an empty group if hi <= lo).  members NULL: the segment indexes
+ *   vox directly (n_members is ignored and taken as n).  offsets NULL: ONE group, [0, n_members), and n_groups is taken as 1.  A
+ *   member index outside [0, n) contributes no pair.  n_groups, n_members <= 2^24.
+ * Views, V <= 2^24 of them, in one of two forms (fiesta_hip_view_set; exactly one of pos and centroid is non-NULL):
+ *   explicit  pos, V x 3 f64 metres; dir, V x 2 f64, the horizontal unit forward vector (the caller's cos / sin of the yaw: no
+ *             trigonometry is part of the contract), nullable only with FIESTA_HIP_VIEW_OMNI; group, V int32, nullable: every view
+ *             looks at group 0.  n_views = V; ring / n_ring unused.
+ *   ring      centroid, n_groups x 3 f64 (the cluster call's output), and ring, n_ring rows of 5 f64 (ox, oy, oz, dx, dy): view
+ *             k * n_ring + j has pos[c] = centroid[3 k + c] + ring[5 j + c] (one add), dir = (dx_j, dy_j) and group k;
+ *             V = n_groups * n_ring; n_views is ignored.
+ * Sensor (fiesta_hip_view_sensor): min_range <= max_range, tan_h, tan_v, all >= 0 and no NaN (+inf allowed); block_mask, a subset
+ *   of FIESTA_HIP_RAY_OCCUPIED | UNKNOWN | OUTSIDE; flags, FIESTA_HIP_VIEW_OMNI or 0; min_clearance (metres; <= 0: no test);
+ *   min_visible >= 1.
+ * Effective group count: n_groups, in the _dev call min(n_groups, *n_groups_dev).
+ * A view is USABLE iff its position is finite with |pos[c] / resolution| < 2^30, its group g satisfies 0 <= g < the effective
+ *   group count, the class (fiesta_hip_ray_query's, of the walk voxel floor(pos / resolution): the map voxel of that voxel's centre)
+ *   is FREE and, when min_clearance > 0, GetDistance(Vector3i) of that map voxel is >= min_clearance (the frontier call's test).
+ * Pairs: a usable view forms one pair with every listed member of its group (a member listed twice makes two pairs).  With
+ *   q[c] = p[c] - pos[c], every product and sum rounded once, sums left to right:
+ *   in range  d2 = q0*q0 + q1*q1 + q2*q2;  min_range*min_range <= d2 && d2 <= max_range*max_range
+ *   in view   without OMNI: fwd = q0*dx + q1*dy, lat = q1*dx - q0*dy;  fwd > 0 && fabs(lat) <= tan_h*fwd && fabs(q2) <= tan_v*fwd
+ *             with OMNI:    fabs(q2) <= tan_v * sqrt(q0*q0 + q1*q1)
+ *   visible   in range and in view, the ray pos -> p is valid under fiesta_hip_ray_query's rule, and its walk W (exactly that
+ *             call's) has no k < |W| - 1 with class(W[k]) & block_mask.  The last voxel of W is the target's own and is never
+ *             tested: a frontier voxel borders unknown space, and a target may itself be unknown.
+ * Outputs; every pointer of the result struct is nullable:
+ *   view_class  uint8 per view: the class of the view's voxel; 0 if the position is invalid
+ *   n_in_view   int32 per view: its pairs in range and in view;  n_visible  int32 per view: its visible pairs; both -1 for an
+ *               unusable view
+ *   cover_count int32 per target entry: the visible pairs that name it;  first_view  int32 per entry: the lowest view index that
+ *               sees it, -1 if none
+ *   best_view   int64 per group (n_groups entries): among the usable views of the group with n_visible >= min_visible the one with
+ *               the largest n_visible, the lowest index among equals; -1 if none.  best_count  int32: its n_visible, 0 if none
+ *   info        n_usable views, n_pairs, n_in_view and n_visible pairs in total
+ *   Every value is an integer; every decision is an f64 comparison in the order above: the same bits for any launch shape, and the
+ *   bits of fiesta_amd.view_coverage_model (the definition in numpy over fiesta_amd.ray_walk).
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): views, sensor or info NULL; vox NULL with
+ *   n > 0; both view forms or neither; ring NULL or n_ring < 0 in ring form; dir NULL without OMNI; a negative count or one above
+ *   2^24 (n, n_groups, n_members, V); a NaN or negative range or tangent; min_range > max_range; block_mask outside 0 .. 7; unknown
+ *   flag bits; min_visible < 1.  V = 0 or n = 0 writes the identities.  The scratch (O(V + n_groups)) belongs to the map.
+ * fiesta_hip_view_coverage      host arrays; stages through the path queries' buffers, runs, synchronises, copies back.
+ * fiesta_hip_view_coverage_dev  every array, and info, is a device pointer (the structs themselves are host objects).
+ *                               n_groups_dev, nullable: a device int64, e.g. &info_dev->n_clusters of
+ *                               fiesta_hip_cluster_voxels_dev -- frontier -> clusters -> coverage needs no host round trip.  Only
+ *                               enqueued on the map's stream. */
+#define FIESTA_HIP_VIEW_OMNI 1
+typedef struct fiesta_hip_view_set {
+  const double *pos;      /* explicit form: V x 3 */
+  const double *dir;      /* V x 2 */
+  const int32_t *group;   /* V, nullable */
+  int64_t n_views;        /* V of the explicit form */
+  const double *centroid; /* ring form: n_groups x 3 */
+  const double *ring;     /* n_ring x 5 */
+  int64_t n_ring;
+} fiesta_hip_view_set;
+typedef struct fiesta_hip_view_sensor {
+  double min_range, max_range, tan_h, tan_v, min_clearance;
+  int32_t block_mask, flags, min_visible, reserved; /* reserved: ignored */
+} fiesta_hip_view_sensor;
+typedef struct fiesta_hip_view_result { /* every pointer nullable */
+  uint8_t *view_class;                  /* per view */
+  int32_t *n_in_view;                   /* per view */
+  int32_t *n_visible;                   /* per view */
+  int32_t *cover_count;                 /* per target entry */
+  int32_t *first_view;                  /* per target entry */
+  int64_t *best_view;                   /* per group */
+  int32_t *best_count;                  /* per group */
+} fiesta_hip_view_result;
+typedef struct fiesta_hip_view_info {
+  int64_t n_usable;
+  int64_t n_pairs;
+  int64_t n_in_view;
+  int64_t n_visible;
+} fiesta_hip_view_info;
+int fiesta_hip_view_coverage(fiesta_hip_map *m, const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members,
+                             int64_t n_groups, int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor,
+                             const fiesta_hip_view_result *result, fiesta_hip_view_info *info);
+int fiesta_hip_view_coverage_dev(fiesta_hip_map *m, const int32_t *vox_dev, int64_t n, const int64_t *offsets_dev, const int64_t *members_dev,
+                                 int64_t n_groups, const int64_t *n_groups_dev, int64_t n_members, const fiesta_hip_view_set *views,
+                                 const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *result, fiesta_hip_view_info *info_dev);
+
 /* ---- whole-field access (tests, visualisation, checkpoints) ----
  * Dense dump in the reference's linear order; each output is nullable.
  *   d2      int32  squared voxel distance to the closest obstacle; -1 never observed; INT32_MAX observed
