@@ -7,9 +7,16 @@
 #include <string>
 
 #include "../../include/fiesta_hip.h"
+#include "cluster_kernels.hpp"  // (the eight planner headers: for the calls' argument aggregates; no kernel is used here)
 #include "dense_map.hpp"
+#include "frontier_kernels.hpp"
 #include "hash_map.hpp"
+#include "path_cost_kernels.hpp"
+#include "ray_query_kernels.hpp"
+#include "reach_kernels.hpp"
+#include "reach_path_kernels.hpp"
 #include "shard_group.hpp"
+#include "view_kernels.hpp"
 
 using fiesta::DenseMap;
 using fiesta::Error;
@@ -47,99 +54,116 @@ int guarded(F &&f) {
 void need(bool ok, const char *msg) {
   if (!ok) throw Error(FIESTA_HIP_ERR_INVALID, msg);
 }
+// f on the map's store: f(DenseMap &) or f(HashMap &), whichever the handle holds
+template <typename F>
+auto on_store(fiesta_hip_map *m, F &&f) {
+  return m->dense ? f(*m->dense) : f(*m->hash);
+}
 DenseMap &dense(fiesta_hip_map *m, const char *what) {
   need(m != nullptr, "null map handle");
   if (!m->dense) throw Error(FIESTA_HIP_ERR_INVALID, std::string(what) + ": only available on array-mode maps");
   return *m->dense;
 }
-// the whole-call errors shared by fiesta_hip_path_clearance[_dev] and fiesta_hip_path_cost[_dev] (include/fiesta_hip.h; r: the
-// call's result struct); host_offsets: the CSR rules as well
-void path_args(fiesta_hip_map *m, const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-               const void *r, bool host_offsets) {
-  need(m && w && off && r, "null argument");
-  need(n_wp >= 0 && n_paths >= 0, "negative count");
-  need(std::isfinite(step) && step > 0, "path query: step must be finite and > 0");
-  need(!std::isnan(margin), "path query: margin is NaN");
-  if (!host_offsets) return;
-  need(off[0] == 0 && off[n_paths] == n_wp, "path query: offsets[0] must be 0 and offsets[n_paths] = n_waypoints");
-  for (int64_t p = 0; p < n_paths; ++p) need(off[p] <= off[p + 1], "path query: offsets must be non-decreasing");
+// The planner calls: one body per host / _dev pair.  Each checks the whole-call errors of include/fiesta_hip.h on the arguments as
+// the ABI took them (the aggregate of the call's kernel header), then hands the same object to the map's store.
+
+// shared by path_clearance and path_cost (R: the call's result struct); a host batch: the CSR rules as well
+template <typename R>
+void path_checks(fiesta_hip_map *m, const fiesta::PathArgs<R> &a) {
+  need(m && a.w && a.off && a.res, "null argument");
+  need(a.n_wp >= 0 && a.n_paths >= 0, "negative count");
+  need(std::isfinite(a.step) && a.step > 0, "path query: step must be finite and > 0");
+  need(!std::isnan(a.margin), "path query: margin is NaN");
+  if (a.dev) return;
+  need(a.off[0] == 0 && a.off[a.n_paths] == a.n_wp, "path query: offsets[0] must be 0 and offsets[n_paths] = n_waypoints");
+  for (int64_t p = 0; p < a.n_paths; ++p) need(a.off[p] <= a.off[p + 1], "path query: offsets must be non-decreasing");
 }
-// the whole-call errors of fiesta_hip_get_frontier_voxels[_dev] (include/fiesta_hip.h)
-void frontier_args(fiesta_hip_map *m, const int32_t *lo, const int32_t *hi, double min_clearance, int64_t capacity, const void *n_out) {
+void path_clearance(fiesta_hip_map *m, const fiesta::PathClearanceArgs &a) {
+  path_checks(m, a);
+  on_store(m, [&](auto &s) { s.path_clearance(a); });
+}
+void path_cost(fiesta_hip_map *m, const fiesta::PathCostArgs &a) {
+  path_checks(m, a);
+  need(std::isfinite(a.margin), "path_cost: margin must be finite");
+  on_store(m, [&](auto &s) { s.path_cost(a); });
+}
+// n_out: the variant's total (host or device pointer); returns the host variant's total
+int64_t frontier_voxels(fiesta_hip_map *m, const fiesta::FrontierArgs &a, const void *n_out) {
   need(m != nullptr, "null map handle");
   need(n_out != nullptr, "get_frontier_voxels: n_out is null");
-  need(!std::isnan(min_clearance), "get_frontier_voxels: min_clearance is NaN");
-  need((lo == nullptr) == (hi == nullptr), "get_frontier_voxels: lo and hi must both be given or both be null");
-  need(capacity >= 0, "get_frontier_voxels: negative capacity");
+  need(!std::isnan(a.min_clearance), "get_frontier_voxels: min_clearance is NaN");
+  need((a.lo == nullptr) == (a.hi == nullptr), "get_frontier_voxels: lo and hi must both be given or both be null");
+  need(a.capacity >= 0, "get_frontier_voxels: negative capacity");
+  return on_store(m, [&](auto &s) { return s.frontier_voxels(a); });
 }
-// the whole-call errors of fiesta_hip_ray_query[_dev] (include/fiesta_hip.h)
-void ray_args(fiesta_hip_map *m, const double *start, const double *end, int64_t n, int32_t stop_mask, const void *r) {
+void ray_query(fiesta_hip_map *m, const fiesta::RayArgs &a) {
   need(m != nullptr, "null map handle");
-  need(start && end && r, "ray_query: start, end or result is null");
-  need(n >= 0, "ray_query: negative count");
-  need(stop_mask >= 0 && stop_mask <= 7, "ray_query: stop_mask must be a subset of OCCUPIED | UNKNOWN | OUTSIDE (0..7)");
+  need(a.start && a.end && a.res, "ray_query: start, end or result is null");
+  need(a.n >= 0, "ray_query: negative count");
+  need(a.stop_mask >= 0 && a.stop_mask <= 7, "ray_query: stop_mask must be a subset of OCCUPIED | UNKNOWN | OUTSIDE (0..7)");
+  on_store(m, [&](auto &s) { s.ray_query(a); });
 }
-// the whole-call errors of fiesta_hip_reach_field[_dev] (include/fiesta_hip.h) that need no device -- checked before the handle is
-// touched; the clipped box's volume is checked by the map, before anything is launched
-void reach_args(fiesta_hip_map *m, const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets,
-                int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags, const fiesta_hip_reach_result *r) {
-  need(r != nullptr, "reach_field: result is null");
-  need(!std::isnan(min_clearance), "reach_field: min_clearance is NaN");
-  need((lo == nullptr) == (hi == nullptr), "reach_field: lo and hi must both be given or both be null");
-  need(connectivity == 6 || connectivity == 26, "reach_field: connectivity must be 6 or 26");
-  need((flags & ~FIESTA_HIP_REACH_THROUGH_UNKNOWN) == 0, "reach_field: unknown flag bits");
-  need(n_seeds >= 0 && n_targets >= 0, "reach_field: negative count");
-  need(seeds != nullptr || n_seeds == 0, "reach_field: seeds is null");
-  need(targets != nullptr || n_targets == 0, "reach_field: targets is null");
-  need(targets != nullptr || r->target_cost == nullptr, "reach_field: target_cost given without targets");
+// none of these errors needs a device: they are checked before the handle is touched; the clipped box's volume is checked by the
+// map, before anything is launched
+void reach_field(fiesta_hip_map *m, const fiesta::ReachArgs &a) {
+  need(a.res != nullptr, "reach_field: result is null");
+  need(!std::isnan(a.min_clearance), "reach_field: min_clearance is NaN");
+  need((a.lo == nullptr) == (a.hi == nullptr), "reach_field: lo and hi must both be given or both be null");
+  need(a.connectivity == 6 || a.connectivity == 26, "reach_field: connectivity must be 6 or 26");
+  need((a.flags & ~FIESTA_HIP_REACH_THROUGH_UNKNOWN) == 0, "reach_field: unknown flag bits");
+  need(a.n_seeds >= 0 && a.n_targets >= 0, "reach_field: negative count");
+  need(a.seeds != nullptr || a.n_seeds == 0, "reach_field: seeds is null");
+  need(a.targets != nullptr || a.n_targets == 0, "reach_field: targets is null");
+  need(a.targets != nullptr || a.res->target_cost == nullptr, "reach_field: target_cost given without targets");
   need(m != nullptr, "null map handle");
-  need(m->dense != nullptr || lo != nullptr, "reach_field: a hash-block map has no outside, the box is mandatory");
+  need(m->dense != nullptr || a.lo != nullptr, "reach_field: a hash-block map has no outside, the box is mandatory");
+  on_store(m, [&](auto &s) { s.reach_field(a); });
 }
-// the whole-call errors of fiesta_hip_reach_paths[_dev] (include/fiesta_hip.h); none of them needs a device, and all but the last
-// are checked before the handle is touched
-void reach_paths_args(fiesta_hip_map *m, const int32_t *cost, const int32_t *lo, const int32_t *hi, const int32_t *targets, int64_t n_targets,
-                      int32_t connectivity, int32_t flags, int32_t max_span, int64_t capacity, const fiesta_hip_reach_paths_result *r) {
-  need(r != nullptr, "reach_paths: result is null");
-  need(r->offsets != nullptr, "reach_paths: result->offsets is null");
-  need(connectivity == 6 || connectivity == 26, "reach_paths: connectivity must be 6 or 26");
-  need((flags & ~FIESTA_HIP_REACH_PATHS_SHORTCUT) == 0, "reach_paths: unknown flag bits");
-  need(!(flags & FIESTA_HIP_REACH_PATHS_SHORTCUT) || max_span >= 1, "reach_paths: max_span must be >= 1 with SHORTCUT");
-  need(n_targets >= 0, "reach_paths: negative count");
-  need(capacity >= 0, "reach_paths: negative capacity");
-  need(targets != nullptr || n_targets == 0, "reach_paths: targets is null");
-  need((cost == nullptr) == (lo == nullptr) && (lo == nullptr) == (hi == nullptr),
+// none of these errors needs a device, and all but the last are checked before the handle is touched
+void reach_paths(fiesta_hip_map *m, const fiesta::ReachPathArgs &a) {
+  need(a.res != nullptr, "reach_paths: result is null");
+  need(a.res->offsets != nullptr, "reach_paths: result->offsets is null");
+  need(a.connectivity == 6 || a.connectivity == 26, "reach_paths: connectivity must be 6 or 26");
+  need((a.flags & ~FIESTA_HIP_REACH_PATHS_SHORTCUT) == 0, "reach_paths: unknown flag bits");
+  need(!(a.flags & FIESTA_HIP_REACH_PATHS_SHORTCUT) || a.max_span >= 1, "reach_paths: max_span must be >= 1 with SHORTCUT");
+  need(a.n_targets >= 0, "reach_paths: negative count");
+  need(a.capacity >= 0, "reach_paths: negative capacity");
+  need(a.targets != nullptr || a.n_targets == 0, "reach_paths: targets is null");
+  need((a.cost == nullptr) == (a.box_lo == nullptr) && (a.box_lo == nullptr) == (a.box_hi == nullptr),
        "reach_paths: cost, box_lo and box_hi must all be given or all be null");
-  if (cost) {
+  if (a.cost) {
     int64_t nvox = 1;
     for (int c = 0; c < 3; ++c) {
-      need(lo[c] <= hi[c], "reach_paths: the box is empty (box_lo > box_hi)");
-      nvox *= std::min<int64_t>((int64_t)hi[c] - lo[c] + 1, (1ll << 28) + 1);  // (three factors of at most 2^28 + 1 would overflow:
-      need(nvox <= (1ll << 28), "reach_paths: the box holds more than 2^28 voxels");  //  checked after every factor)
+      need(a.box_lo[c] <= a.box_hi[c], "reach_paths: the box is empty (box_lo > box_hi)");
+      nvox *= std::min<int64_t>((int64_t)a.box_hi[c] - a.box_lo[c] + 1, (1ll << 28) + 1);  // (three factors of at most 2^28 + 1 would overflow:
+      need(nvox <= (1ll << 28), "reach_paths: the box holds more than 2^28 voxels");       //  checked after every factor)
     }
   }
   need(m != nullptr, "null map handle");
+  on_store(m, [&](auto &s) { s.reach_paths(a); });
 }
-// the whole-call errors of fiesta_hip_cluster_voxels[_dev] (include/fiesta_hip.h); none of them needs a device
-void cluster_args(fiesta_hip_map *m, const int32_t *vox, int64_t n, int32_t connectivity, int32_t min_size, int64_t cluster_capacity,
-                  int64_t member_capacity, const void *info) {
-  need(info != nullptr, "cluster_voxels: info is null");
-  need(n >= 0 && n <= (1ll << 24), "cluster_voxels: the entry count must lie in 0 .. 2^24");
-  need(connectivity == 6 || connectivity == 18 || connectivity == 26, "cluster_voxels: connectivity must be 6, 18 or 26");
-  need(min_size >= 1, "cluster_voxels: min_size must be >= 1");
-  need(cluster_capacity >= 0 && member_capacity >= 0, "cluster_voxels: negative capacity");
-  need(vox != nullptr || n == 0, "cluster_voxels: vox is null");
+// none of these errors needs a device
+void cluster_voxels(fiesta_hip_map *m, const fiesta::ClusterArgs &a) {
+  need(a.info != nullptr, "cluster_voxels: info is null");
+  need(a.n >= 0 && a.n <= (1ll << 24), "cluster_voxels: the entry count must lie in 0 .. 2^24");
+  need(a.connectivity == 6 || a.connectivity == 18 || a.connectivity == 26, "cluster_voxels: connectivity must be 6, 18 or 26");
+  need(a.min_size >= 1, "cluster_voxels: min_size must be >= 1");
+  need(a.cluster_capacity >= 0 && a.member_capacity >= 0, "cluster_voxels: negative capacity");
+  need(a.vox != nullptr || a.n == 0, "cluster_voxels: vox is null");
   need(m != nullptr, "null map handle");
+  on_store(m, [&](auto &s) { s.cluster_voxels(a); });
 }
-// the whole-call errors of fiesta_hip_view_coverage[_dev] (include/fiesta_hip.h); none of them needs a device
-void view_args(fiesta_hip_map *m, const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups, int64_t n_members,
-               const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *s, const void *info) {
+// none of these errors needs a device
+void view_coverage(fiesta_hip_map *m, const fiesta::ViewArgs &a) {
   constexpr int64_t cap = 1ll << 24;
+  const fiesta_hip_view_set *views = a.views;
+  const fiesta_hip_view_sensor *s = a.sensor;
   need(views != nullptr && s != nullptr, "view_coverage: views or sensor is null");
-  need(info != nullptr, "view_coverage: info is null");
-  need(n >= 0 && n <= cap, "view_coverage: the entry count must lie in 0 .. 2^24");
-  need(n_groups >= 0 && n_groups <= cap, "view_coverage: the group count must lie in 0 .. 2^24");
-  need(members == nullptr || (n_members >= 0 && n_members <= cap), "view_coverage: the member count must lie in 0 .. 2^24");  // (ignored without members)
-  need(vox != nullptr || n == 0, "view_coverage: vox is null");
+  need(a.info != nullptr, "view_coverage: info is null");
+  need(a.n >= 0 && a.n <= cap, "view_coverage: the entry count must lie in 0 .. 2^24");
+  need(a.n_groups >= 0 && a.n_groups <= cap, "view_coverage: the group count must lie in 0 .. 2^24");
+  need(a.members == nullptr || (a.n_members >= 0 && a.n_members <= cap), "view_coverage: the member count must lie in 0 .. 2^24");  // (ignored without members)
+  need(a.vox != nullptr || a.n == 0, "view_coverage: vox is null");
   need((views->pos != nullptr) != (views->centroid != nullptr), "view_coverage: exactly one view form (pos, or centroid and ring) must be given");
   const bool omni = (s->flags & FIESTA_HIP_VIEW_OMNI) != 0;
   if (views->pos) {
@@ -147,7 +171,7 @@ void view_args(fiesta_hip_map *m, const int32_t *vox, int64_t n, const int64_t *
     need(views->dir != nullptr || omni, "view_coverage: dir is null without FIESTA_HIP_VIEW_OMNI");
   } else {
     need(views->ring != nullptr && views->n_ring >= 0 && views->n_ring <= cap, "view_coverage: the ring form needs ring and 0 <= n_ring <= 2^24");
-    need((offsets ? n_groups : 1) * views->n_ring <= cap, "view_coverage: the view count must lie in 0 .. 2^24");
+    need((a.offsets ? a.n_groups : 1) * views->n_ring <= cap, "view_coverage: the view count must lie in 0 .. 2^24");
   }
   // (a NaN fails every comparison)
   need(s->min_range >= 0 && s->max_range >= 0 && s->min_range <= s->max_range, "view_coverage: the range must satisfy 0 <= min_range <= max_range");
@@ -157,6 +181,7 @@ void view_args(fiesta_hip_map *m, const int32_t *vox, int64_t n, const int64_t *
   need((s->flags & ~FIESTA_HIP_VIEW_OMNI) == 0, "view_coverage: unknown flag bits");
   need(s->min_visible >= 1, "view_coverage: min_visible must be >= 1");
   need(m != nullptr, "null map handle");
+  on_store(m, [&](auto &st) { st.view_coverage(a); });
 }
 }  // namespace
 
@@ -224,7 +249,7 @@ int fiesta_hip_grid_size(fiesta_hip_map *m, int32_t out[3]) {
 int fiesta_hip_grid_total_size(fiesta_hip_map *m, int64_t *out) {
   return guarded([&] {
     need(m && out, "null argument");
-    *out = m->dense ? m->dense->total() : m->hash->allocated_voxels();
+    *out = m->dense ? m->dense->total() : m->hash->allocated_voxels();  // (two different questions: nothing to share)
   });
 }
 
@@ -263,28 +288,19 @@ int fiesta_hip_set_prob_params(fiesta_hip_map *m, double p_hit, double p_miss, d
                                double p_occ) {
   return guarded([&] {
     need(m != nullptr, "null map handle");
-    if (m->dense)
-      m->dense->set_prob_params(p_hit, p_miss, p_min, p_max, p_occ);
-    else
-      m->hash->set_prob_params(p_hit, p_miss, p_min, p_max, p_occ);
+    on_store(m, [&](auto &s) { s.set_prob_params(p_hit, p_miss, p_min, p_max, p_occ); });
   });
 }
 int fiesta_hip_set_update_range(fiesta_hip_map *m, const double mn[3], const double mx[3], int new_vec) {
   return guarded([&] {
     need(m && mn && mx, "null argument");
-    if (m->dense)
-      m->dense->set_update_range(mn, mx, new_vec != 0);
-    else
-      m->hash->set_update_range(mn, mx, new_vec != 0);
+    on_store(m, [&](auto &s) { s.set_update_range(mn, mx, new_vec != 0); });
   });
 }
 int fiesta_hip_set_original_range(fiesta_hip_map *m) {
   return guarded([&] {
     need(m != nullptr, "null map handle");
-    if (m->dense)
-      m->dense->set_original_range();
-    else
-      m->hash->set_original_range();
+    on_store(m, [&](auto &s) { s.set_original_range(); });
   });
 }
 
@@ -292,17 +308,15 @@ int fiesta_hip_set_update_engine(fiesta_hip_map *m, int32_t engine) {
   return guarded([&] {
     need(m != nullptr, "null map handle");
     need(engine >= 0 && engine <= 6, "unknown update_engine");
-    if (m->dense)
-      m->dense->set_update_engine(engine);
-    else
-      m->hash->set_update_engine(engine > 3 ? 0 : engine);  // (no transform on a hash-block map: 2, 4, 5 and 6 mean 0 there)
+    // (no transform on a hash-block map: 2, 4, 5 and 6 mean 0 there)
+    on_store(m, [&](auto &s) { s.set_update_engine(m->hash && engine > 3 ? 0 : engine); });
   });
 }
 
 int fiesta_hip_level_trace(fiesta_hip_map *m, uint32_t out[48], int32_t *n_levels) {
   return guarded([&] {
     need(m && out && n_levels, "bad argument");
-    *n_levels = m->dense ? m->dense->level_trace(out) : m->hash->level_trace(out);
+    *n_levels = on_store(m, [&](auto &s) { return s.level_trace(out); });
   });
 }
 
@@ -311,48 +325,33 @@ int fiesta_hip_level_tuning(fiesta_hip_map *m, int32_t grid_groups, int64_t spin
     need(m != nullptr, "null map handle");
     need(grid_groups <= 32, "at most 32 work-groups (the CUs of one XCD)");
     need(spin_limit <= 0xFFFFFFFFll, "spin_limit does not fit 32 bits");
-    if (m->dense)
-      m->dense->level_tuning(grid_groups, spin_limit);
-    else
-      m->hash->level_tuning(grid_groups, spin_limit);
+    on_store(m, [&](auto &s) { s.level_tuning(grid_groups, spin_limit); });
   });
 }
 
 int fiesta_hip_set_occupancy_vox(fiesta_hip_map *m, const int32_t *vox, const int32_t *occ, int64_t n, int32_t *ret) {
   return guarded([&] {
     need(m && (n == 0 || (vox && occ)) && n >= 0, "bad argument");
-    if (m->dense)
-      m->dense->observe_vox(vox, occ, n, ret, false);
-    else
-      m->hash->observe_vox(vox, occ, n, ret);
+    on_store(m, [&](auto &s) { s.observe_vox(vox, occ, n, ret, false); });
   });
 }
 int fiesta_hip_set_occupancy_pos(fiesta_hip_map *m, const double *pos, const int32_t *occ, int64_t n, int32_t *ret) {
   return guarded([&] {
     need(m && (n == 0 || (pos && occ)) && n >= 0, "bad argument");
-    if (m->dense)
-      m->dense->observe_pos(pos, occ, n, ret);
-    else
-      m->hash->observe_pos(pos, occ, n, ret);
+    on_store(m, [&](auto &s) { s.observe_pos(pos, occ, n, ret); });
   });
 }
 int fiesta_hip_set_occupancy_vox_dev(fiesta_hip_map *m, const int32_t *vox_dev, const int32_t *occ_dev, int64_t n) {
   return guarded([&] {
     need(m && (n == 0 || (vox_dev && occ_dev)) && n >= 0, "bad argument");
-    if (m->dense)
-      m->dense->observe_vox(vox_dev, occ_dev, n, nullptr, true);
-    else
-      m->hash->observe_vox(vox_dev, occ_dev, n, nullptr, true);
+    on_store(m, [&](auto &s) { s.observe_vox(vox_dev, occ_dev, n, nullptr, true); });
   });
 }
 
 int fiesta_hip_set_occupancy_box(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], int32_t occ) {
   return guarded([&] {
     need(m && lo && hi && (occ == 0 || occ == 1), "bad argument");
-    if (m->dense)
-      m->dense->observe_box(lo, hi, occ);
-    else
-      m->hash->observe_box(lo, hi, occ);
+    on_store(m, [&](auto &s) { s.observe_box(lo, hi, occ); });
   });
 }
 
@@ -360,20 +359,14 @@ int fiesta_hip_raycast_frame(fiesta_hip_map *m, const float *points, int64_t n, 
                              const double origin[3], const fiesta_hip_raycast_params *p) {
   return guarded([&] {
     need(m && (n == 0 || points) && T && origin && p && n >= 0, "bad argument");
-    if (m->dense)
-      m->dense->raycast_frame(points, n, T, origin, p, false);
-    else
-      m->hash->raycast_frame(points, n, T, origin, p, false);
+    on_store(m, [&](auto &s) { s.raycast_frame(points, n, T, origin, p, false); });
   });
 }
 int fiesta_hip_raycast_frame_dev(fiesta_hip_map *m, const float *points_dev, int64_t n, const double T[16],
                                  const double origin[3], const fiesta_hip_raycast_params *p) {
   return guarded([&] {
     need(m && (n == 0 || points_dev) && T && origin && p && n >= 0, "bad argument");
-    if (m->dense)
-      m->dense->raycast_frame(points_dev, n, T, origin, p, true);
-    else
-      m->hash->raycast_frame(points_dev, n, T, origin, p, true);
+    on_store(m, [&](auto &s) { s.raycast_frame(points_dev, n, T, origin, p, true); });
   });
 }
 int fiesta_hip_raycast_depth(fiesta_hip_map *m, const uint16_t *depth, int32_t rows, int32_t cols, double fx,
@@ -381,10 +374,7 @@ int fiesta_hip_raycast_depth(fiesta_hip_map *m, const uint16_t *depth, int32_t r
                              const fiesta_hip_raycast_params *p) {
   return guarded([&] {
     need(m && depth && rows > 0 && cols > 0 && T && origin && p, "bad argument");
-    if (m->dense)
-      m->dense->raycast_depth(depth, rows, cols, fx, fy, cx, cy, T, origin, p);
-    else
-      m->hash->raycast_depth(depth, rows, cols, fx, fy, cx, cy, T, origin, p);
+    on_store(m, [&](auto &s) { s.raycast_depth(depth, rows, cols, fx, fy, cx, cy, T, origin, p); });
   });
 }
 int fiesta_hip_raycast_depth_filtered(fiesta_hip_map *m, const uint16_t *depth, int32_t rows, int32_t cols, double fx, double fy,
@@ -392,10 +382,7 @@ int fiesta_hip_raycast_depth_filtered(fiesta_hip_map *m, const uint16_t *depth, 
                                       const fiesta_hip_raycast_params *p, const fiesta_hip_depth_filter *f) {
   return guarded([&] {
     need(m && depth && rows > 0 && cols > 0 && T && origin && p && f, "bad argument");
-    if (m->dense)
-      m->dense->raycast_depth(depth, rows, cols, fx, fy, cx, cy, T, origin, p, f);
-    else
-      m->hash->raycast_depth(depth, rows, cols, fx, fy, cx, cy, T, origin, p, f);
+    on_store(m, [&](auto &s) { s.raycast_depth(depth, rows, cols, fx, fy, cx, cy, T, origin, p, f); });
   });
 }
 int fiesta_hip_depth_conversion(fiesta_hip_map *m, const uint16_t *depth, int32_t rows, int32_t cols, double fx, double fy,
@@ -417,52 +404,41 @@ int fiesta_hip_raycast_single(const double start[3], const double end[3], const 
 int fiesta_hip_check_update(fiesta_hip_map *m, int32_t *out) {
   return guarded([&] {
     need(m && out, "null argument");
-    *out = (m->dense ? m->dense->check_update() : m->hash->check_update()) ? 1 : 0;
+    *out = on_store(m, [&](auto &s) { return s.check_update(); }) ? 1 : 0;
   });
 }
 int fiesta_hip_update_occupancy(fiesta_hip_map *m, int32_t global_map, int64_t *n_insert, int64_t *n_delete,
                                 int32_t *any) {
   return guarded([&] {
     need(m != nullptr, "null map handle");
-    const bool r = m->dense ? m->dense->update_occupancy(global_map != 0, n_insert, n_delete)
-                            : m->hash->update_occupancy(global_map != 0, n_insert, n_delete);
+    const bool r = on_store(m, [&](auto &s) { return s.update_occupancy(global_map != 0, n_insert, n_delete); });
     if (any) *any = r ? 1 : 0;
   });
 }
 int fiesta_hip_update_esdf(fiesta_hip_map *m, fiesta_hip_stats *stats) {
   return guarded([&] {
     need(m != nullptr, "null map handle");
-    if (m->dense) {
-      m->dense->update_esdf(stats);
-      if (stats) stats->path_notes = (int64_t)m->dense->path_notes();
-    } else {
-      m->hash->update_esdf(stats);
-    }
+    on_store(m, [&](auto &s) { s.update_esdf(stats); });
+    if (stats && m->dense) stats->path_notes = (int64_t)m->dense->path_notes();
   });
 }
 
 int fiesta_hip_get_distance_vox(fiesta_hip_map *m, const int32_t *vox, int64_t n, double *out) {
   return guarded([&] {
     need(m && (n == 0 || (vox && out)) && n >= 0, "bad argument");
-    if (m->dense)
-      m->dense->get_distance_vox(vox, n, out);
-    else
-      m->hash->get_distance_vox(vox, n, out);
+    on_store(m, [&](auto &s) { s.get_distance_vox(vox, n, out); });
   });
 }
 int fiesta_hip_get_distance_pos(fiesta_hip_map *m, const double *pos, int64_t n, double *out) {
   return guarded([&] {
     need(m && (n == 0 || (pos && out)) && n >= 0, "bad argument");
-    if (m->dense)
-      m->dense->get_distance_pos(pos, n, out);
-    else
-      m->hash->get_distance_pos(pos, n, out);
+    on_store(m, [&](auto &s) { s.get_distance_pos(pos, n, out); });
   });
 }
 int fiesta_hip_get_dist_grad(fiesta_hip_map *m, const double *pos, int64_t n, double *dist, double *grad) {
   return guarded([&] {
     need(m && (n == 0 || (pos && dist)) && n >= 0, "bad argument");
-    if (m->dense)
+    if (m->dense)  // (the array store's member serves the _dev variant too)
       m->dense->get_dist_grad(pos, n, dist, grad, false);
     else
       m->hash->get_dist_grad(pos, n, dist, grad);
@@ -477,68 +453,36 @@ int fiesta_hip_get_dist_grad_dev(fiesta_hip_map *m, const double *pos_dev, int64
 }
 int fiesta_hip_path_clearance(fiesta_hip_map *m, const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step,
                               double margin, const fiesta_hip_path_result *r) {
-  return guarded([&] {
-    path_args(m, w, n_wp, off, n_paths, step, margin, r, true);
-    if (m->dense)
-      m->dense->path_clearance(w, n_wp, off, n_paths, step, margin, *r, false);
-    else
-      m->hash->path_clearance(w, n_wp, off, n_paths, step, margin, *r, false);
-  });
+  return guarded([&] { path_clearance(m, {w, n_wp, off, n_paths, step, margin, r, false}); });
 }
 int fiesta_hip_path_clearance_dev(fiesta_hip_map *m, const double *w_dev, int64_t n_wp, const int64_t *off_dev, int64_t n_paths,
                                   double step, double margin, const fiesta_hip_path_result *r) {
-  return guarded([&] {
-    path_args(m, w_dev, n_wp, off_dev, n_paths, step, margin, r, false);
-    if (m->dense)
-      m->dense->path_clearance(w_dev, n_wp, off_dev, n_paths, step, margin, *r, true);
-    else
-      m->hash->path_clearance(w_dev, n_wp, off_dev, n_paths, step, margin, *r, true);
-  });
+  return guarded([&] { path_clearance(m, {w_dev, n_wp, off_dev, n_paths, step, margin, r, true}); });
 }
 int fiesta_hip_path_cost(fiesta_hip_map *m, const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
                          const fiesta_hip_path_cost_result *r) {
-  return guarded([&] {
-    path_args(m, w, n_wp, off, n_paths, step, margin, r, true);
-    need(std::isfinite(margin), "path_cost: margin must be finite");
-    if (m->dense)
-      m->dense->path_cost(w, n_wp, off, n_paths, step, margin, *r, false);
-    else
-      m->hash->path_cost(w, n_wp, off, n_paths, step, margin, *r, false);
-  });
+  return guarded([&] { path_cost(m, {w, n_wp, off, n_paths, step, margin, r, false}); });
 }
 int fiesta_hip_path_cost_dev(fiesta_hip_map *m, const double *w_dev, int64_t n_wp, const int64_t *off_dev, int64_t n_paths, double step,
                              double margin, const fiesta_hip_path_cost_result *r) {
-  return guarded([&] {
-    path_args(m, w_dev, n_wp, off_dev, n_paths, step, margin, r, false);
-    need(std::isfinite(margin), "path_cost: margin must be finite");
-    if (m->dense)
-      m->dense->path_cost(w_dev, n_wp, off_dev, n_paths, step, margin, *r, true);
-    else
-      m->hash->path_cost(w_dev, n_wp, off_dev, n_paths, step, margin, *r, true);
-  });
+  return guarded([&] { path_cost(m, {w_dev, n_wp, off_dev, n_paths, step, margin, r, true}); });
 }
 int fiesta_hip_host_cache_fetches(fiesta_hip_map *m, int64_t *fetches) {
   return guarded([&] {
     need(m && fetches, "bad argument");
-    *fetches = m->dense ? m->dense->host_brick_fetches() : m->hash->host_brick_fetches();
+    *fetches = on_store(m, [&](auto &s) { return s.host_brick_fetches(); });
   });
 }
 int fiesta_hip_get_occupancy_vox(fiesta_hip_map *m, const int32_t *vox, int64_t n, int32_t *out) {
   return guarded([&] {
     need(m && (n == 0 || (vox && out)) && n >= 0, "bad argument");
-    if (m->dense)
-      m->dense->get_occupancy_vox(vox, n, out);
-    else
-      m->hash->get_occupancy_vox(vox, n, out);
+    on_store(m, [&](auto &s) { s.get_occupancy_vox(vox, n, out); });
   });
 }
 int fiesta_hip_get_occupancy_pos(fiesta_hip_map *m, const double *pos, int64_t n, int32_t *out) {
   return guarded([&] {
     need(m && (n == 0 || (pos && out)) && n >= 0, "bad argument");
-    if (m->dense)
-      m->dense->get_occupancy_pos(pos, n, out);
-    else
-      m->hash->get_occupancy_pos(pos, n, out);
+    on_store(m, [&](auto &s) { s.get_occupancy_pos(pos, n, out); });
   });
 }
 
@@ -548,10 +492,7 @@ int fiesta_hip_download_field(fiesta_hip_map *m, int32_t *d2, int32_t *coc, uint
 int fiesta_hip_download_counts(fiesta_hip_map *m, int32_t *num_hit, int32_t *num_miss) {
   return guarded([&] {
     need(m != nullptr, "null map");
-    if (m->dense)
-      m->dense->download_counts(num_hit, num_miss);
-    else
-      m->hash->download_counts(num_hit, num_miss);
+    on_store(m, [&](auto &s) { s.download_counts(num_hit, num_miss); });
   });
 }
 int fiesta_hip_count_no_obstacle(fiesta_hip_map *m, int64_t *n_out) {
@@ -568,128 +509,62 @@ int fiesta_hip_get_occupied_voxels(fiesta_hip_map *m, int32_t *vox, int64_t capa
 }
 int fiesta_hip_get_frontier_voxels(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance, int32_t *vox,
                                    uint8_t *mask, int64_t capacity, int64_t *n_out) {
-  return guarded([&] {
-    frontier_args(m, lo, hi, min_clearance, capacity, n_out);
-    *n_out = m->dense ? m->dense->frontier_voxels(lo, hi, min_clearance, vox, mask, capacity, nullptr, false)
-                      : m->hash->frontier_voxels(lo, hi, min_clearance, vox, mask, capacity, nullptr, false);
-  });
+  return guarded([&] { *n_out = frontier_voxels(m, {lo, hi, min_clearance, vox, mask, capacity, nullptr, false}, n_out); });
 }
 int fiesta_hip_get_frontier_voxels_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance, int32_t *vox_dev,
                                        uint8_t *mask_dev, int64_t capacity, unsigned long long *n_out_dev) {
-  return guarded([&] {
-    frontier_args(m, lo, hi, min_clearance, capacity, n_out_dev);
-    if (m->dense)
-      m->dense->frontier_voxels(lo, hi, min_clearance, vox_dev, mask_dev, capacity, n_out_dev, true);
-    else
-      m->hash->frontier_voxels(lo, hi, min_clearance, vox_dev, mask_dev, capacity, n_out_dev, true);
-  });
+  return guarded([&] { frontier_voxels(m, {lo, hi, min_clearance, vox_dev, mask_dev, capacity, n_out_dev, true}, n_out_dev); });
 }
 int fiesta_hip_ray_query(fiesta_hip_map *m, const double *start, const double *end, int64_t n, int32_t stop_mask,
                          const fiesta_hip_ray_result *r) {
-  return guarded([&] {
-    ray_args(m, start, end, n, stop_mask, r);
-    if (m->dense)
-      m->dense->ray_query(start, end, n, stop_mask, *r, false);
-    else
-      m->hash->ray_query(start, end, n, stop_mask, *r, false);
-  });
+  return guarded([&] { ray_query(m, {start, end, n, stop_mask, r, false}); });
 }
 int fiesta_hip_ray_query_dev(fiesta_hip_map *m, const double *start_dev, const double *end_dev, int64_t n, int32_t stop_mask,
                              const fiesta_hip_ray_result *r) {
-  return guarded([&] {
-    ray_args(m, start_dev, end_dev, n, stop_mask, r);
-    if (m->dense)
-      m->dense->ray_query(start_dev, end_dev, n, stop_mask, *r, true);
-    else
-      m->hash->ray_query(start_dev, end_dev, n, stop_mask, *r, true);
-  });
+  return guarded([&] { ray_query(m, {start_dev, end_dev, n, stop_mask, r, true}); });
 }
 int fiesta_hip_reach_field(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds, int64_t n_seeds,
                            const int32_t *targets, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
                            const fiesta_hip_reach_result *result, fiesta_hip_reach_info *info) {
-  return guarded([&] {
-    reach_args(m, lo, hi, seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, result);
-    if (m->dense)
-      m->dense->reach_field(lo, hi, seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, *result, info, false);
-    else
-      m->hash->reach_field(lo, hi, seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, *result, info, false);
-  });
+  return guarded([&] { reach_field(m, {lo, hi, seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, result, info, false}); });
 }
 int fiesta_hip_reach_field_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds_dev, int64_t n_seeds,
                                const int32_t *targets_dev, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
                                const fiesta_hip_reach_result *result, fiesta_hip_reach_info *info) {
-  return guarded([&] {
-    reach_args(m, lo, hi, seeds_dev, n_seeds, targets_dev, n_targets, min_clearance, connectivity, flags, result);
-    if (m->dense)
-      m->dense->reach_field(lo, hi, seeds_dev, n_seeds, targets_dev, n_targets, min_clearance, connectivity, flags, *result, info, true);
-    else
-      m->hash->reach_field(lo, hi, seeds_dev, n_seeds, targets_dev, n_targets, min_clearance, connectivity, flags, *result, info, true);
-  });
+  return guarded([&] { reach_field(m, {lo, hi, seeds_dev, n_seeds, targets_dev, n_targets, min_clearance, connectivity, flags, result, info, true}); });
 }
 int fiesta_hip_reach_paths(fiesta_hip_map *m, const int32_t *cost, const int32_t box_lo[3], const int32_t box_hi[3], const int32_t *targets,
                            int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span, int64_t capacity,
                            const fiesta_hip_reach_paths_result *result) {
-  return guarded([&] {
-    reach_paths_args(m, cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, result);
-    if (m->dense)
-      m->dense->reach_paths(cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, *result, false);
-    else
-      m->hash->reach_paths(cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, *result, false);
-  });
+  return guarded([&] { reach_paths(m, {cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, result, false}); });
 }
 int fiesta_hip_reach_paths_dev(fiesta_hip_map *m, const int32_t *cost_dev, const int32_t box_lo[3], const int32_t box_hi[3],
                                const int32_t *targets_dev, int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span,
                                int64_t capacity, const fiesta_hip_reach_paths_result *result) {
-  return guarded([&] {
-    reach_paths_args(m, cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, result);
-    if (m->dense)
-      m->dense->reach_paths(cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, *result, true);
-    else
-      m->hash->reach_paths(cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, *result, true);
-  });
+  return guarded([&] { reach_paths(m, {cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, result, true}); });
 }
 int fiesta_hip_cluster_voxels(fiesta_hip_map *m, const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, int32_t connectivity,
                               int32_t min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *result,
                               fiesta_hip_cluster_info *info) {
-  return guarded([&] {
-    cluster_args(m, vox, n, connectivity, min_size, cluster_capacity, member_capacity, info);
-    if (m->dense)
-      m->dense->cluster_voxels(vox, mask, key, n, nullptr, connectivity, min_size, cluster_capacity, member_capacity, result, info, false);
-    else
-      m->hash->cluster_voxels(vox, mask, key, n, nullptr, connectivity, min_size, cluster_capacity, member_capacity, result, info, false);
-  });
+  return guarded([&] { cluster_voxels(m, {vox, mask, key, n, nullptr, connectivity, min_size, cluster_capacity, member_capacity, result, info, false}); });
 }
 int fiesta_hip_cluster_voxels_dev(fiesta_hip_map *m, const int32_t *vox_dev, const uint8_t *mask_dev, const int32_t *key_dev, int64_t n,
                                   const unsigned long long *n_dev, int32_t connectivity, int32_t min_size, int64_t cluster_capacity,
                                   int64_t member_capacity, const fiesta_hip_cluster_result *result, fiesta_hip_cluster_info *info_dev) {
   return guarded([&] {
-    cluster_args(m, vox_dev, n, connectivity, min_size, cluster_capacity, member_capacity, info_dev);
-    if (m->dense)
-      m->dense->cluster_voxels(vox_dev, mask_dev, key_dev, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, result, info_dev, true);
-    else
-      m->hash->cluster_voxels(vox_dev, mask_dev, key_dev, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, result, info_dev, true);
+    cluster_voxels(m, {vox_dev, mask_dev, key_dev, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, result, info_dev, true});
   });
 }
 int fiesta_hip_view_coverage(fiesta_hip_map *m, const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups,
                              int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor,
                              const fiesta_hip_view_result *result, fiesta_hip_view_info *info) {
-  return guarded([&] {
-    view_args(m, vox, n, offsets, members, n_groups, n_members, views, sensor, info);
-    if (m->dense)
-      m->dense->view_coverage(vox, n, offsets, members, n_groups, nullptr, n_members, views, sensor, result, info, false);
-    else
-      m->hash->view_coverage(vox, n, offsets, members, n_groups, nullptr, n_members, views, sensor, result, info, false);
-  });
+  return guarded([&] { view_coverage(m, {vox, n, offsets, members, n_groups, nullptr, n_members, views, sensor, result, info, false}); });
 }
 int fiesta_hip_view_coverage_dev(fiesta_hip_map *m, const int32_t *vox_dev, int64_t n, const int64_t *offsets_dev, const int64_t *members_dev,
                                  int64_t n_groups, const int64_t *n_groups_dev, int64_t n_members, const fiesta_hip_view_set *views,
                                  const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *result, fiesta_hip_view_info *info_dev) {
   return guarded([&] {
-    view_args(m, vox_dev, n, offsets_dev, members_dev, n_groups, n_members, views, sensor, info_dev);
-    if (m->dense)
-      m->dense->view_coverage(vox_dev, n, offsets_dev, members_dev, n_groups, n_groups_dev, n_members, views, sensor, result, info_dev, true);
-    else
-      m->hash->view_coverage(vox_dev, n, offsets_dev, members_dev, n_groups, n_groups_dev, n_members, views, sensor, result, info_dev, true);
+    view_coverage(m, {vox_dev, n, offsets_dev, members_dev, n_groups, n_groups_dev, n_members, views, sensor, result, info_dev, true});
   });
 }
 int fiesta_hip_get_slice(fiesta_hip_map *m, int32_t z_vox, double *out) {
@@ -701,35 +576,27 @@ int fiesta_hip_get_slice(fiesta_hip_map *m, int32_t z_vox, double *out) {
 int fiesta_hip_save(fiesta_hip_map *m, const char *path) {
   return guarded([&] {
     need(m && path, "null argument");
-    if (m->dense)
-      m->dense->checkpoint(path, true);
-    else
-      m->hash->checkpoint(path, true);
+    on_store(m, [&](auto &s) { s.checkpoint(path, true); });
   });
 }
 int fiesta_hip_load(fiesta_hip_map *m, const char *path) {
   return guarded([&] {
     need(m && path, "null argument");
-    if (m->dense)
-      m->dense->checkpoint(path, false);
-    else
-      m->hash->checkpoint(path, false);
+    on_store(m, [&](auto &s) { s.checkpoint(path, false); });
   });
 }
 int fiesta_hip_get_point_cloud(fiesta_hip_map *m, int32_t vis_lower_bound, int32_t vis_upper_bound, float *xyz,
                                int64_t capacity, int64_t *n_out) {
   return guarded([&] {
     need(m && n_out && capacity >= 0, "bad argument");
-    *n_out = m->dense ? m->dense->point_cloud(vis_lower_bound, vis_upper_bound, xyz, capacity)
-                      : m->hash->point_cloud(vis_lower_bound, vis_upper_bound, xyz, capacity);
+    *n_out = on_store(m, [&](auto &s) { return s.point_cloud(vis_lower_bound, vis_upper_bound, xyz, capacity); });
   });
 }
 int fiesta_hip_get_slice_marker(fiesta_hip_map *m, int32_t slice, double max_dist, double *xyz, float *rgba,
                                 int64_t capacity, int64_t *n_out) {
   return guarded([&] {
     need(m && n_out && capacity >= 0, "bad argument");
-    *n_out = m->dense ? m->dense->slice_marker(slice, max_dist, xyz, rgba, capacity)
-                      : m->hash->slice_marker(slice, max_dist, xyz, rgba, capacity);
+    *n_out = on_store(m, [&](auto &s) { return s.slice_marker(slice, max_dist, xyz, rgba, capacity); });
   });
 }
 int fiesta_hip_download_hash(fiesta_hip_map *m, int64_t *n_out, int32_t *vox, int32_t *d2, int32_t *coc,
@@ -744,12 +611,10 @@ int fiesta_hip_download_hash(fiesta_hip_map *m, int64_t *n_out, int32_t *vox, in
 int fiesta_hip_snapshot_save(fiesta_hip_map *m, int32_t slot) {
   return guarded([&] {
     need(m != nullptr, "null map");
-    if (m->dense) {
-      m->dense->snapshot_save(slot);
-    } else {  // hash-block maps keep ONE copy of the state words, enough for the "updated voxels" unit (no restore)
-      need(slot == 0, "hash-mode maps have snapshot slot 0 only");
-      m->hash->snapshot_save();
-    }
+    if (m->dense) return m->dense->snapshot_save(slot);
+    // hash-block maps keep ONE copy of the state words, enough for the "updated voxels" unit (no restore)
+    need(slot == 0, "hash-mode maps have snapshot slot 0 only");
+    m->hash->snapshot_save();
   });
 }
 int fiesta_hip_snapshot_restore(fiesta_hip_map *m, int32_t slot) {
@@ -759,12 +624,8 @@ int fiesta_hip_snapshot_count_updated(fiesta_hip_map *m, int32_t slot, int64_t *
   return guarded([&] {
     need(updated != nullptr, "null argument");
     need(m != nullptr, "null map");
-    if (m->dense) {
-      *updated = m->dense->snapshot_count_updated(slot);
-    } else {
-      need(slot == 0, "hash-mode maps have snapshot slot 0 only");
-      *updated = m->hash->snapshot_count_updated();
-    }
+    if (!m->dense) need(slot == 0, "hash-mode maps have snapshot slot 0 only");
+    *updated = m->dense ? m->dense->snapshot_count_updated(slot) : m->hash->snapshot_count_updated();
   });
 }
 
@@ -959,10 +820,7 @@ int fiesta_hip_shard_group_update_esdf(fiesta_hip_shard_group *g, fiesta_hip_sta
 int fiesta_hip_synchronize(fiesta_hip_map *m) {
   return guarded([&] {
     need(m != nullptr, "null map handle");
-    if (m->dense)
-      m->dense->synchronize();
-    else
-      m->hash->synchronize();
+    on_store(m, [&](auto &s) { s.synchronize(); });
   });
 }
 

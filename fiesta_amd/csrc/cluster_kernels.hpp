@@ -28,6 +28,19 @@
 #include "dense_map.hpp"
 
 namespace fiesta {
+struct ClusterArgs {  // the call's arguments as fiesta_hip_cluster_voxels[_dev] takes them, already checked
+  const int32_t *vox;
+  const uint8_t *mask;
+  const int32_t *key;
+  int64_t n;
+  const unsigned long long *n_dev;
+  int connectivity, min_size;
+  int64_t cluster_capacity, member_capacity;
+  const fiesta_hip_cluster_result *res;
+  fiesta_hip_cluster_info *info;
+  bool dev;
+};
+
 namespace {  // (this header is included by two translation units)
 
 constexpr int64_t kClusterMaxEntries = 1ll << 24;
@@ -416,19 +429,6 @@ __global__ __launch_bounds__(kClusterBlock) void k_cluster_finish(ClusterWork w,
   }
 }
 
-struct ClusterArgs {  // the call's arguments as fiesta_hip_cluster_voxels[_dev] takes them, already checked
-  const int32_t *vox;
-  const uint8_t *mask;
-  const int32_t *key;
-  int64_t n;
-  const unsigned long long *n_dev;
-  int connectivity, min_size;
-  int64_t cluster_capacity, member_capacity;
-  const fiesta_hip_cluster_result *res;
-  fiesta_hip_cluster_info *info;
-  bool dev;
-};
-
 // enqueue the passes; every pointer of `in` and `o` is a device pointer
 inline void cluster_enqueue(hipStream_t st, ClusterScratch &S, const ClusterIn &in, const ClusterOut &o, int connectivity, int min_size, double res,
                             const double *org) {
@@ -463,11 +463,11 @@ inline void cluster_enqueue(hipStream_t st, ClusterScratch &S, const ClusterIn &
   FIESTA_HIP_CHECK(hipGetLastError());
 }
 
-// Both variants of the call on a map's stream; res / org: the map's resolution and origin.  The device variant only enqueues.  The
-// host variant stages the inputs through `in` and every output through `out`, synchronises, reads the totals and copies back the
-// labels and min(total, capacity) of each cluster array.
-inline void cluster_voxels_run(hipStream_t st, ClusterScratch &S, DevBuf<unsigned char> &in, DevBuf<unsigned char> &out, double res, const double *org,
-                               const ClusterArgs &a) {
+// Both variants of the call on a map's stream; res / org: the map's resolution and origin -- nothing else of a map is read, so
+// both stores share this function.  The device variant only enqueues.  The host variant stages the inputs through P.in and every
+// output through P.out, synchronises, reads the totals and copies back the labels and min(total, capacity) of each cluster array.
+inline void cluster_voxels_run(hipStream_t st, PlannerScratch &P, double res, const double *org, const ClusterArgs &a) {
+  ClusterScratch &S = P.cluster;
   const fiesta_hip_cluster_result none{};
   const fiesta_hip_cluster_result &r = a.res ? *a.res : none;
   if (a.dev) {
@@ -478,37 +478,26 @@ inline void cluster_voxels_run(hipStream_t st, ClusterScratch &S, DevBuf<unsigne
     return;
   }
   const size_t n = (size_t)a.n, C = (size_t)std::min<int64_t>(a.n, a.cluster_capacity), M = (size_t)std::min<int64_t>(a.n, a.member_capacity);
-  const auto up8 = [](size_t b) { return (b + 7) / 8 * 8; };
-  // inputs: vox, key, mask (8-byte aligned sections)
-  const size_t i_vox = 0, i_key = up8(n * 12), i_mask = i_key + up8(a.key ? n * 4 : 0), i_end = i_mask + up8(a.mask ? n : 0);
-  in.ensure(std::max<size_t>(i_end, 8), st);
-  if (n) FIESTA_HIP_CHECK(hipMemcpyAsync(in.p + i_vox, a.vox, n * 12, hipMemcpyHostToDevice, st));
-  if (n && a.key) FIESTA_HIP_CHECK(hipMemcpyAsync(in.p + i_key, a.key, n * 4, hipMemcpyHostToDevice, st));
-  if (n && a.mask) FIESTA_HIP_CHECK(hipMemcpyAsync(in.p + i_mask, a.mask, n, hipMemcpyHostToDevice, st));
-  const ClusterIn ci{(const int32_t *)(in.p + i_vox), a.mask ? (const uint8_t *)(in.p + i_mask) : nullptr, a.key ? (const int32_t *)(in.p + i_key) : nullptr,
-                     nullptr, a.n};
-  // outputs: info, then the 8-byte arrays, then the 4-byte ones, then the bytes
-  const size_t o_info = 0, o_root = up8(sizeof(fiesta_hip_cluster_info)), o_arg = o_root + C * 8, o_off = o_arg + C * 8, o_mem = o_off + (C + 1) * 8,
-               o_cen = o_mem + M * 8, o_lab = o_cen + C * 24, o_size = o_lab + up8(n * 4), o_lo = o_size + up8(C * 4), o_hi = o_lo + up8(C * 12),
-               o_kmin = o_hi + up8(C * 12), o_mor = o_kmin + up8(C * 4), o_end = o_mor + up8(C);
-  out.ensure(o_end, st);
-  unsigned char *b = out.p;
-  const ClusterOut co{r.label ? (int32_t *)(b + o_lab) : nullptr, r.size ? (int32_t *)(b + o_size) : nullptr, r.root ? (int64_t *)(b + o_root) : nullptr,
-                      r.box_lo ? (int32_t *)(b + o_lo) : nullptr, r.box_hi ? (int32_t *)(b + o_hi) : nullptr, r.centroid ? (double *)(b + o_cen) : nullptr,
-                      r.mask_or ? (uint8_t *)(b + o_mor) : nullptr, r.key_min ? (int32_t *)(b + o_kmin) : nullptr,
-                      r.key_argmin ? (int64_t *)(b + o_arg) : nullptr, r.offsets ? (int64_t *)(b + o_off) : nullptr,
-                      r.members ? (int64_t *)(b + o_mem) : nullptr, (fiesta_hip_cluster_info *)(b + o_info), (int64_t)C, (int64_t)M};
+  Staging in{P.in, st}, out{P.out, st};
+  const auto vox = in.add(a.vox, 3 * n), key = in.add(a.key, n);
+  const auto mask = in.add(a.mask, n);
+  in.alloc(), in.up(vox, 3 * n), in.up(key, n), in.up(mask, n);
+  const ClusterIn ci{in.dev(vox), in.dev(mask), in.dev(key), nullptr, a.n};
+  const auto info = out.add(a.info, 1);
+  const auto root = out.add(r.root, C), key_argmin = out.add(r.key_argmin, C), offsets = out.add(r.offsets, C + 1), members = out.add(r.members, M);
+  const auto centroid = out.add(r.centroid, 3 * C);
+  const auto label = out.add(r.label, n), size = out.add(r.size, C), box_lo = out.add(r.box_lo, 3 * C), box_hi = out.add(r.box_hi, 3 * C),
+             key_min = out.add(r.key_min, C);
+  const auto mask_or = out.add(r.mask_or, C);
+  out.alloc();
+  const ClusterOut co{out.dev(label),   out.dev(size),    out.dev(root),       out.dev(box_lo),  out.dev(box_hi),  out.dev(centroid), out.dev(mask_or),
+                      out.dev(key_min), out.dev(key_argmin), out.dev(offsets), out.dev(members), out.dev(info),    (int64_t)C,        (int64_t)M};
   cluster_enqueue(st, S, ci, co, a.connectivity, a.min_size, res, org);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(a.info, b + o_info, sizeof(fiesta_hip_cluster_info), hipMemcpyDeviceToHost, st));
-  if (r.label && n) FIESTA_HIP_CHECK(hipMemcpyAsync(r.label, b + o_lab, n * 4, hipMemcpyDeviceToHost, st));
+  out.back(info, 1), out.back(label, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(st));
   const size_t k = (size_t)std::min<int64_t>(a.info->n_clusters, (int64_t)C), mm = (size_t)std::min<int64_t>(a.info->n_members, (int64_t)M);
-  const auto back = [&](void *dst, size_t off, size_t bytes) {
-    if (dst && bytes) FIESTA_HIP_CHECK(hipMemcpyAsync(dst, b + off, bytes, hipMemcpyDeviceToHost, st));
-  };
-  back(r.size, o_size, k * 4), back(r.root, o_root, k * 8), back(r.box_lo, o_lo, k * 12), back(r.box_hi, o_hi, k * 12);
-  back(r.centroid, o_cen, k * 24), back(r.mask_or, o_mor, k), back(r.key_min, o_kmin, k * 4), back(r.key_argmin, o_arg, k * 8);
-  back(r.offsets, o_off, (k + 1) * 8), back(r.members, o_mem, mm * 8);
+  out.back(size, k), out.back(root, k), out.back(box_lo, 3 * k), out.back(box_hi, 3 * k), out.back(centroid, 3 * k), out.back(mask_or, k);
+  out.back(key_min, k), out.back(key_argmin, k), out.back(offsets, k + 1), out.back(members, mm);
   FIESTA_HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -2453,31 +2453,27 @@ void DenseMap::get_dist_grad(const double *pos, int64_t n, double *dist, double 
   if (grad) FIESTA_HIP_CHECK(hipMemcpyAsync(grad, stage_b_.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
-void DenseMap::path_clearance(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-                              const fiesta_hip_path_result &r, bool dev) {
-  if (n_paths <= 0) return;
-  if (!dev && path_host_samples(w, off, n_paths, step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
+void DenseMap::path_clearance(const PathClearanceArgs &a) {
+  if (a.n_paths <= 0) return;
+  if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
     HostWords wd{this};
     auto ev = [&](const double *p, double *grad) { return query_trilinear(g_, wd, p, grad); };
-    path_host(ev, w, off, n_paths, step, margin, r);
+    path_host(ev, a.w, a.off, a.n_paths, a.step, a.margin, *a.res);
     return;
   }
   use_device();
-  path_clearance_run(stream_, path_in_, path_tmp_, path_out_, DensePathEval{g_, (const vox_t *)coc_}, w, n_wp, off, n_paths, step,
-                     margin, r, dev);
+  path_clearance_run(stream_, planner_, DensePathEval{g_, (const vox_t *)coc_}, a);
 }
-void DenseMap::path_cost(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-                         const fiesta_hip_path_cost_result &r, bool dev) {
-  if (n_paths <= 0) return;
-  if (!dev && path_host_samples(w, off, n_paths, step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
+void DenseMap::path_cost(const PathCostArgs &a) {
+  if (a.n_paths <= 0) return;
+  if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
     HostWords wd{this};
     auto ev = [&](const double *p, double *grad) { return query_trilinear(g_, wd, p, grad); };
-    path_cost_host(ev, w, n_wp, off, n_paths, step, margin, r);
+    path_cost_host(ev, a.w, a.n_wp, a.off, a.n_paths, a.step, a.margin, *a.res);
     return;
   }
   use_device();
-  path_cost_run(stream_, path_in_, path_tmp_, path_out_, DensePathEval{g_, (const vox_t *)coc_}, w, n_wp, off, n_paths, step, margin, r,
-                dev);
+  path_cost_run(stream_, planner_, DensePathEval{g_, (const vox_t *)coc_}, a);
 }
 void DenseMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n <= 0) return;
@@ -2580,123 +2576,93 @@ int64_t DenseMap::occupied_voxels(int32_t *vox, int64_t cap) {
   return n;
 }
 
-// fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp); arguments checked by the caller.  dev: vox / mask / n_out_dev are
-// device pointers and the call is only enqueued; else host pointers, and the total is returned.
-int64_t DenseMap::frontier_voxels(const int32_t *lo, const int32_t *hi, double min_clearance, int32_t *vox, uint8_t *mask, int64_t cap,
-                                  unsigned long long *n_out_dev, bool dev) {
+void DenseMap::sync_obsbits() {
+  if (!g_.sharded) return;
+  hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
+  FIESTA_HIP_CHECK(hipGetLastError());
+}
+bool DenseMap::clip_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]) const {
+  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0}, dims[3] = {g_.nx, g_.ny, g_.nz};
+  bool any = true;
+  for (int c = 0; c < 3; ++c) {
+    blo[c] = lo ? std::max<int64_t>((int64_t)lo[c] - g0[c], 0) : 0;
+    bhi[c] = hi ? std::min<int64_t>((int64_t)hi[c] - g0[c], dims[c] - 1) : dims[c] - 1;
+    any = any && blo[c] <= bhi[c];
+  }
+  return any;
+}
+
+// fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp).  dev: vox / mask / n_out_dev are device pointers and the call is
+// only enqueued; else host pointers, and the total is returned.
+int64_t DenseMap::frontier_voxels(const FrontierArgs &a) {
   use_device();
-  unsigned long long *count = dev ? n_out_dev : &counters_[C_SCRATCH];
-  if (dev)
+  unsigned long long *count = a.dev ? a.n_out_dev : &counters_[C_SCRATCH];
+  if (a.dev)
     hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, stream_, count, 1);
   else
     zero_counter(C_SCRATCH);
   FIESTA_HIP_CHECK(hipGetLastError());
-  // the box in local array coordinates, intersected with the array
-  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0}, dims[3] = {g_.nx, g_.ny, g_.nz};
-  int64_t blo[3], bhi[3], nvox = 1;
-  for (int c = 0; c < 3; ++c) {
-    blo[c] = lo ? std::max<int64_t>((int64_t)lo[c] - g0[c], 0) : 0;
-    bhi[c] = hi ? std::min<int64_t>((int64_t)hi[c] - g0[c], dims[c] - 1) : dims[c] - 1;
-    nvox = blo[c] > bhi[c] ? 0 : nvox * (bhi[c] - blo[c] + 1);
-  }
-  cap = std::min(cap, nvox);
-  int32_t *dvox = dev ? vox : nullptr;
-  uint8_t *dmask = dev ? mask : nullptr;
-  if (!dev && cap > 0) {
-    if (vox) stage_a_.ensure((size_t)cap * 3 * sizeof(int32_t), stream_), dvox = (int32_t *)stage_a_.p;
-    if (mask) stage_b_.ensure((size_t)cap, stream_), dmask = (uint8_t *)stage_b_.p;
-  }
-  if (nvox > 0 && g_.sharded) {
-    // a shard's ghost cells are written by the halo exchange, which does not keep obsbits_: bring the bitmap in line with the field
-    hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
-    FIESTA_HIP_CHECK(hipGetLastError());
+  int64_t blo[3], bhi[3];
+  const int64_t nvox = clip_box(a.lo, a.hi, blo, bhi) ? (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * (bhi[2] - blo[2] + 1) : 0;
+  const int64_t cap = std::min(a.capacity, nvox);
+  int32_t *dvox = a.dev ? a.vox : nullptr;
+  uint8_t *dmask = a.dev ? a.mask : nullptr;
+  if (!a.dev && cap > 0) {
+    if (a.vox) stage_a_.ensure((size_t)cap * 3 * sizeof(int32_t), stream_), dvox = (int32_t *)stage_a_.p;
+    if (a.mask) stage_b_.ensure((size_t)cap, stream_), dmask = (uint8_t *)stage_b_.p;
   }
   if (nvox > 0) {
+    sync_obsbits();
     const FrontierBox b{(int)blo[0], (int)blo[1], (int)blo[2], (int)bhi[0], (int)bhi[1], (int)bhi[2]};
     const int64_t nwords = (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * ((bhi[2] >> 5) - (blo[2] >> 5) + 1);
     hipLaunchKernelGGL(k_frontier_dense<DenseFrontierDist>, dim3(grid_for(nwords, 256, 8192)), dim3(256), 0, stream_, g_,
-                       (const uint32_t *)obsbits_, (const uint32_t *)occbits_, b, DenseFrontierDist{g_, (const vox_t *)coc_}, min_clearance,
+                       (const uint32_t *)obsbits_, (const uint32_t *)occbits_, b, DenseFrontierDist{g_, (const vox_t *)coc_}, a.min_clearance,
                        FrontierOut{dvox, dmask, (unsigned long long)cap, count});
     FIESTA_HIP_CHECK(hipGetLastError());
   }
-  if (dev) return 0;
+  if (a.dev) return 0;
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
   const size_t k = (size_t)std::min(n, cap);
-  if (dvox && k) FIESTA_HIP_CHECK(hipMemcpyAsync(vox, dvox, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(mask, dmask, k, hipMemcpyDeviceToHost, stream_));
+  if (dvox && k) FIESTA_HIP_CHECK(hipMemcpyAsync(a.vox, dvox, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(a.mask, dmask, k, hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }
 
-// fiesta_hip_reach_field[_dev] (reach_kernels.hpp); arguments checked by the caller.  The box in local array coordinates,
-// intersected with the array; the padding bits of a row's last bitmap word lie past the clipped box and are masked there.
-void DenseMap::reach_field(const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets, int64_t n_targets,
-                           double min_clearance, int connectivity, int flags, const fiesta_hip_reach_result &r, fiesta_hip_reach_info *info,
-                           bool dev) {
+// fiesta_hip_reach_field[_dev] (reach_kernels.hpp).  The padding bits of a row's last bitmap word lie past the clipped box and are
+// masked there.
+void DenseMap::reach_field(const ReachArgs &a) {
   use_device();
-  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0}, dims[3] = {g_.nx, g_.ny, g_.nz};
+  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0};
   int64_t blo[3], bhi[3];
-  bool empty = false;
-  for (int c = 0; c < 3; ++c) {
-    blo[c] = lo ? std::max<int64_t>((int64_t)lo[c] - g0[c], 0) : 0;
-    bhi[c] = hi ? std::min<int64_t>((int64_t)hi[c] - g0[c], dims[c] - 1) : dims[c] - 1;
-    empty = empty || blo[c] > bhi[c];
-  }
+  const bool empty = !clip_box(a.lo, a.hi, blo, bhi);
   if (empty) blo[0] = 1, bhi[0] = 0;
   if (!empty && (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * (bhi[2] - blo[2] + 1) > kReachMaxVoxels)  // (before anything is launched)
     throw Error(FIESTA_HIP_ERR_INVALID, "reach_field: the clipped box holds more than 2^28 voxels");
-  if (!empty && g_.sharded) {  // (the halo exchange does not keep obsbits_ in ghost cells: see frontier_voxels)
-    hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
-    FIESTA_HIP_CHECK(hipGetLastError());
-  }
-  reach_run(stream_, reach_, path_in_, path_out_, DenseReachSource{g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, (const vox_t *)coc_}, blo,
-            bhi, g0, ReachArgs{seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, &r, info, dev});
+  if (!empty) sync_obsbits();
+  reach_run(stream_, planner_, DenseReachSource{g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, (const vox_t *)coc_}, blo, bhi, g0, a);
 }
 
-// fiesta_hip_reach_paths[_dev] (reach_path_kernels.hpp); arguments checked by the caller.  Nothing of the map is read but its
-// resolution and origin, and the cost field the reachability scratch retains (or the caller's).
-void DenseMap::reach_paths(const int32_t *cost, const int32_t *box_lo, const int32_t *box_hi, const int32_t *targets, int64_t n_targets,
-                      int connectivity, int flags, int max_span, int64_t capacity, const fiesta_hip_reach_paths_result &r, bool dev) {
-  use_device();
-  reach_paths_run(stream_, reach_, path_in_, path_out_, g_.res, g_.org,
-                  ReachPathArgs{cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, &r, dev});
-}
+// fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin
+void DenseMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
+void DenseMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
 
-// fiesta_hip_cluster_voxels[_dev] (cluster_kernels.hpp); arguments checked by the caller.  Nothing of the map is read but its
-// resolution and origin.
-void DenseMap::cluster_voxels(const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const unsigned long long *n_dev, int connectivity,
-                              int min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *r,
-                              fiesta_hip_cluster_info *info, bool dev) {
+// fiesta_hip_view_coverage[_dev] (view_kernels.hpp).  The ray query's source, the frontier call's distance (local array
+// coordinates: a FREE voxel lies inside the array).
+void DenseMap::view_coverage(const ViewArgs &a) {
   use_device();
-  cluster_voxels_run(stream_, cluster_, path_in_, path_out_, g_.res, g_.org,
-                     ClusterArgs{vox, mask, key, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, r, info, dev});
-}
-
-// fiesta_hip_view_coverage[_dev] (view_kernels.hpp); arguments checked by the caller.  The ray query's source, the frontier call's
-// distance (local array coordinates: a FREE voxel lies inside the array).
-void DenseMap::view_coverage(const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups, const int64_t *n_groups_dev,
-                             int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *r,
-                             fiesta_hip_view_info *info, bool dev) {
-  use_device();
-  if (g_.sharded) {  // (the halo exchange does not keep obsbits_ in ghost cells: see frontier_voxels)
-    hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
-    FIESTA_HIP_CHECK(hipGetLastError());
-  }
+  sync_obsbits();
   const ViewSource<DenseRaySource, DenseFrontierDist> vs{DenseRaySource(g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_),
                                                          DenseFrontierDist{g_, (const vox_t *)coc_}, {g_.gx0, g_.gy0, g_.gz0}};
-  view_coverage_run(stream_, view_, path_in_, path_out_, vs, ViewArgs{vox, n, offsets, members, n_groups, n_groups_dev, n_members, views, sensor, r, info, dev});
+  view_coverage_run(stream_, planner_, vs, a);
 }
 
-// fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller
-void DenseMap::ray_query(const double *start, const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev) {
-  if (n <= 0) return;
+// fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp)
+void DenseMap::ray_query(const RayArgs &a) {
+  if (a.n <= 0) return;
   use_device();
-  if (g_.sharded) {  // (the halo exchange does not keep obsbits_ in ghost cells: see frontier_voxels)
-    hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
-    FIESTA_HIP_CHECK(hipGetLastError());
-  }
-  ray_query_run(stream_, path_in_, path_out_, DenseRaySource(g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_), start, end, n,
-                stop_mask, r, dev);
+  sync_obsbits();
+  ray_query_run(stream_, planner_, DenseRaySource(g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_), a);
 }
 
 int64_t DenseMap::point_cloud(int vis_lower_bound, int vis_upper_bound, float *xyz, int64_t cap) {

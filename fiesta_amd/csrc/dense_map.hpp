@@ -1,6 +1,7 @@
 // fiesta_amd/csrc/dense_map.hpp -- dense-array ESDF map resident in HBM (host-side class).
 // Replaces the dense flavour of fiesta::ESDFMap (include/ESDFMap.h:37-166, src/ESDFMap.cpp).
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <vector>
 
@@ -78,6 +79,58 @@ struct ViewScratch {
   DevBuf<double> pos, dir;
   DevBuf<unsigned char> call;  // one ViewCall
 };
+
+// what the planner calls (path clearance ... view coverage) keep between calls, one per map: the staged inputs of a host variant,
+// the path calls' plan / piece records, the staged outputs, and the three calls' own scratch
+struct PlannerScratch {
+  DevBuf<unsigned char> in, tmp, out;
+  ReachScratch reach;
+  ClusterScratch cluster;
+  ViewScratch view;
+};
+
+// A host variant's staged sections in one of PlannerScratch's buffers: add() every section (8-byte aligned, in order), alloc(),
+// then dev() / up() / back().  A section whose host pointer is null has no device pointer and is never copied.
+struct Staging {
+  template <typename T>
+  struct Sec {
+    T *host;
+    size_t off;
+  };
+  DevBuf<unsigned char> &buf;
+  hipStream_t st;
+  size_t end = 0;
+  static size_t up8(size_t b) { return (b + 7) / 8 * 8; }
+  template <typename T>
+  Sec<T> add(T *host, size_t count) {
+    const Sec<T> s{host, end};
+    end += up8(count * sizeof(T));
+    return s;
+  }
+  void alloc(size_t keep = 0) { buf.ensure(std::max<size_t>(end, 8), st, keep); }  // keep: bytes of an earlier alloc() to preserve
+  template <typename T>
+  T *dev(const Sec<T> &s) const {
+    return s.host ? (T *)(buf.p + s.off) : nullptr;
+  }
+  template <typename T>
+  void up(const Sec<T> &s, size_t count) const {
+    if (s.host && count) FIESTA_HIP_CHECK(hipMemcpyAsync(buf.p + s.off, s.host, count * sizeof(T), hipMemcpyHostToDevice, st));
+  }
+  template <typename T>
+  void back(const Sec<T> &s, size_t count) const {
+    if (s.host && count) FIESTA_HIP_CHECK(hipMemcpyAsync(s.host, buf.p + s.off, count * sizeof(T), hipMemcpyDeviceToHost, st));
+  }
+};
+
+// the planner calls' arguments as the C ABI takes them, already checked: each defined in its kernel header, built once by c_api.hip
+template <typename R>
+struct PathArgs;
+struct FrontierArgs;
+struct RayArgs;
+struct ReachArgs;
+struct ReachPathArgs;
+struct ClusterArgs;
+struct ViewArgs;
 
 // Device-side counters, one 64-bit word each.
 enum Counter {
@@ -174,36 +227,20 @@ class DenseMap {
   void get_dist_grad(const double *pos, int64_t n, double *dist, double *grad, bool dev);
   void get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out);
   void get_occupancy_pos(const double *pos, int64_t n, int32_t *out);
-  // fiesta_hip_path_clearance[_dev] (path_kernels.hpp); arguments checked by the caller
-  void path_clearance(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-                      const fiesta_hip_path_result &r, bool dev);
-  // fiesta_hip_path_cost[_dev] (path_cost_kernels.hpp); arguments checked by the caller
-  void path_cost(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-                 const fiesta_hip_path_cost_result &r, bool dev);
+  // the planner calls: the arguments are checked and packed by the caller (c_api.hip)
+  void path_clearance(const PathArgs<fiesta_hip_path_result> &a);
+  void path_cost(const PathArgs<fiesta_hip_path_cost_result> &a);
   int64_t host_brick_fetches() const;  // bricks fetched for scalar queries so far (tests, bench)
 
   void download_field(int32_t *d2, int32_t *coc, uint8_t *occ, double *logodds);
   void download_counts(int32_t *num_hit, int32_t *num_miss);
   int64_t occupied_voxels(int32_t *vox, int64_t cap);  // returns the total count (may exceed cap)
-  // fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp); returns the total count (host variant; may exceed cap)
-  int64_t frontier_voxels(const int32_t *lo, const int32_t *hi, double min_clearance, int32_t *vox, uint8_t *mask, int64_t cap,
-                          unsigned long long *n_out_dev, bool dev);
-  // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller
-  void ray_query(const double *start, const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev);
-  // fiesta_hip_reach_field[_dev] (reach_kernels.hpp); arguments checked by the caller
-  void reach_field(const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets, int64_t n_targets,
-                   double min_clearance, int connectivity, int flags, const fiesta_hip_reach_result &r, fiesta_hip_reach_info *info, bool dev);
-  // fiesta_hip_reach_paths[_dev] (reach_path_kernels.hpp); arguments checked by the caller
-  void reach_paths(const int32_t *cost, const int32_t *box_lo, const int32_t *box_hi, const int32_t *targets, int64_t n_targets, int connectivity,
-                   int flags, int max_span, int64_t capacity, const fiesta_hip_reach_paths_result &r, bool dev);
-  // fiesta_hip_cluster_voxels[_dev] (cluster_kernels.hpp); arguments checked by the caller
-  void cluster_voxels(const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const unsigned long long *n_dev, int connectivity,
-                      int min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *r,
-                      fiesta_hip_cluster_info *info, bool dev);
-  // fiesta_hip_view_coverage[_dev] (view_kernels.hpp); arguments checked by the caller
-  void view_coverage(const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups, const int64_t *n_groups_dev,
-                     int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *r,
-                     fiesta_hip_view_info *info, bool dev);
+  int64_t frontier_voxels(const FrontierArgs &a);  // returns the total count (host variant; may exceed the capacity)
+  void ray_query(const RayArgs &a);
+  void reach_field(const ReachArgs &a);
+  void reach_paths(const ReachPathArgs &a);
+  void cluster_voxels(const ClusterArgs &a);
+  void view_coverage(const ViewArgs &a);
   int64_t count_no_obstacle();
   void slice_distances(int z_vox, double *out);        // nx * ny doubles, x-major
   // GetPointCloud / GetSliceMarker as arrays; both return the total count (may exceed cap), order unspecified
@@ -278,6 +315,11 @@ class DenseMap {
   void reset_stats_counters(bool lists = false, bool queues = false);
   void enable_distance_tracking();
   void collect_stats(fiesta_hip_stats *st);
+  // a shard's ghost cells are written by the halo exchange, which does not keep obsbits_: bring the bitmap in line with the field
+  // (nothing to do on an unsharded map)
+  void sync_obsbits();
+  // a caller's box (null: everything) in local array coordinates, intersected with the array; false: nothing is left
+  bool clip_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]) const;
 
   Geom g_;
   ProbParams pp_;
@@ -383,10 +425,7 @@ class DenseMap {
 
   // staging
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_;
-  DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path and ray queries: staged inputs, plan / piece records, staged outputs
-  ReachScratch reach_;
-  ClusterScratch cluster_;
-  ViewScratch view_;
+  PlannerScratch planner_;
   // raycast front-end state (per-frame stamp arrays = Fiesta::set_occ_/set_free_, include/Fiesta.h:107-110;
   // per-ray traversal lists), lazily allocated by raycast.hip
   struct RaycastState;

@@ -35,6 +35,8 @@ constexpr int kWin = HashMap::kWin, kHalf = HashMap::kHalf;
 constexpr int kNTY = HashMap::kNTY, kNTZ = HashMap::kNTZ, kNTiles = HashMap::kNTiles;
 constexpr int kPageVox = HashMap::kPageVox;
 constexpr int C_OUTSIDE = C_REMOTE_DEL;  // (dense shards only use that slot) a batch held a voxel outside the window
+// a caller's voxel coordinate or range bound clamped to +-2^30 (map coordinates lie well inside): kernels' differences stay in range
+inline int clamp30(int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, -(1ll << 30)), 1ll << 30); }
 
 __device__ inline int tile_id(int x, int y, int z) { return ((x >> 4) * kNTY + (y >> 4)) * kNTZ + (z >> 5); }
 __device__ inline bool in_win(int x, int y, int z) {
@@ -1451,31 +1453,27 @@ void HashMap::get_dist_grad(const double *pos, int64_t n, double *dist, double *
   if (grad) FIESTA_HIP_CHECK(hipMemcpyAsync(grad, stage_b_.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
-void HashMap::path_clearance(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-                             const fiesta_hip_path_result &r, bool dev) {
-  if (n_paths <= 0) return;
-  if (!dev && path_host_samples(w, off, n_paths, step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
+void HashMap::path_clearance(const PathClearanceArgs &a) {
+  if (a.n_paths <= 0) return;
+  if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
     auto corner = [&](int vx, int vy, int vz) { return host_distance(vx, vy, vz); };
     auto ev = [&](const double *p, double *grad) { return h_trilinear(g_, corner, p, grad); };
-    path_host(ev, w, off, n_paths, step, margin, r);
+    path_host(ev, a.w, a.off, a.n_paths, a.step, a.margin, *a.res);
     return;
   }
   use_device();
-  path_clearance_run(stream_, path_in_, path_tmp_, path_out_, HashPathEval{g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p}, w,
-                     n_wp, off, n_paths, step, margin, r, dev);
+  path_clearance_run(stream_, planner_, HashPathEval{g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p}, a);
 }
-void HashMap::path_cost(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-                        const fiesta_hip_path_cost_result &r, bool dev) {
-  if (n_paths <= 0) return;
-  if (!dev && path_host_samples(w, off, n_paths, step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
+void HashMap::path_cost(const PathCostArgs &a) {
+  if (a.n_paths <= 0) return;
+  if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
     auto corner = [&](int vx, int vy, int vz) { return host_distance(vx, vy, vz); };
     auto ev = [&](const double *p, double *grad) { return h_trilinear(g_, corner, p, grad); };
-    path_cost_host(ev, w, n_wp, off, n_paths, step, margin, r);
+    path_cost_host(ev, a.w, a.n_wp, a.off, a.n_paths, a.step, a.margin, *a.res);
     return;
   }
   use_device();
-  path_cost_run(stream_, path_in_, path_tmp_, path_out_, HashPathEval{g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p}, w, n_wp,
-                off, n_paths, step, margin, r, dev);
+  path_cost_run(stream_, planner_, HashPathEval{g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p}, a);
 }
 void HashMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n > 0 && n <= kHostQueries) {
@@ -1539,11 +1537,10 @@ int64_t HashMap::point_cloud(int vis_lower_bound, int vis_upper_bound, float *xy
     stage_a_.ensure((size_t)cap * 3 * sizeof(float), stream_);
     dout = (float *)stage_a_.p;
   }
-  auto c = [](int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, -(1ll << 30)), 1ll << 30); };
   const int64_t nrows = npages_ * kPageRows;
   if (nrows)
     hipLaunchKernelGGL(k_h_point_cloud, dim3(grid_for(nrows, 256, 8192)), dim3(256), 0, stream_, g_, (const int32_t *)page_gtile_.p, nrows,
-                       (const uint32_t *)occbits_.p, c(ur_[0]), c(ur_[3]), c(ur_[1]), c(ur_[4]), vis_lower_bound, vis_upper_bound, dout,
+                       (const uint32_t *)occbits_.p, clamp30(ur_[0]), clamp30(ur_[3]), clamp30(ur_[1]), clamp30(ur_[4]), vis_lower_bound, vis_upper_bound, dout,
                        (unsigned long long)(dout ? cap : 0), &counters_[C_SCRATCH]);
   FIESTA_HIP_CHECK(hipGetLastError());
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
@@ -1552,53 +1549,47 @@ int64_t HashMap::point_cloud(int vis_lower_bound, int vis_upper_bound, float *xy
   return n;
 }
 
-// fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp); arguments checked by the caller.  Every page, resident or parked; a
-// null box is the whole map.
-int64_t HashMap::frontier_voxels(const int32_t *lo, const int32_t *hi, double min_clearance, int32_t *vox, uint8_t *mask, int64_t cap,
-                                 unsigned long long *n_out_dev, bool dev) {
+// fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp).  Every page, resident or parked; a null box is the whole map.
+int64_t HashMap::frontier_voxels(const FrontierArgs &a) {
   use_device();
   const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
-  unsigned long long *count = dev ? n_out_dev : &counters_[C_SCRATCH];
+  unsigned long long *count = a.dev ? a.n_out_dev : &counters_[C_SCRATCH];
   hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, stream_, count, 1);
   FIESTA_HIP_CHECK(hipGetLastError());
   // (page coordinates stay within +-2^25: clamping the box there changes nothing and keeps the kernel's differences in range)
-  auto c = [](int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, -(1ll << 30)), 1ll << 30); };
-  FrontierBox b{c(INT32_MIN), c(INT32_MIN), c(INT32_MIN), c(INT32_MAX), c(INT32_MAX), c(INT32_MAX)};
-  if (lo) b = FrontierBox{c(lo[0]), c(lo[1]), c(lo[2]), c(hi[0]), c(hi[1]), c(hi[2])};
+  FrontierBox b{clamp30(INT32_MIN), clamp30(INT32_MIN), clamp30(INT32_MIN), clamp30(INT32_MAX), clamp30(INT32_MAX), clamp30(INT32_MAX)};
+  if (a.lo) b = FrontierBox{clamp30(a.lo[0]), clamp30(a.lo[1]), clamp30(a.lo[2]), clamp30(a.hi[0]), clamp30(a.hi[1]), clamp30(a.hi[2])};
   const bool empty = b.x0 > b.x1 || b.y0 > b.y1 || b.z0 > b.z1 || npages_ == 0;
-  cap = std::min<int64_t>(cap, npages_ * kPageVox);
-  int32_t *dvox = dev ? vox : nullptr;
-  uint8_t *dmask = dev ? mask : nullptr;
-  if (!dev && cap > 0) {
-    if (vox) stage_a_.ensure((size_t)cap * 3 * sizeof(int32_t), stream_), dvox = (int32_t *)stage_a_.p;
-    if (mask) stage_b_.ensure((size_t)cap, stream_), dmask = (uint8_t *)stage_b_.p;
+  const int64_t cap = std::min<int64_t>(a.capacity, npages_ * kPageVox);
+  int32_t *dvox = a.dev ? a.vox : nullptr;
+  uint8_t *dmask = a.dev ? a.mask : nullptr;
+  if (!a.dev && cap > 0) {
+    if (a.vox) stage_a_.ensure((size_t)cap * 3 * sizeof(int32_t), stream_), dvox = (int32_t *)stage_a_.p;
+    if (a.mask) stage_b_.ensure((size_t)cap, stream_), dmask = (uint8_t *)stage_b_.p;
   }
   if (!empty) {
     hipLaunchKernelGGL(k_frontier_hash<HashFrontierPages>, dim3(grid_for(npages_, 1, 8192)), dim3(256), 0, stream_,
                        (const int32_t *)page_gtile_.p, npages_, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p, b,
-                       HashFrontierPages{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}, min_clearance,
+                       HashFrontierPages{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}, a.min_clearance,
                        FrontierOut{dvox, dmask, (unsigned long long)cap, count});
     FIESTA_HIP_CHECK(hipGetLastError());
   }
-  if (dev) return 0;
+  if (a.dev) return 0;
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
   const size_t k = (size_t)std::min(n, cap);
-  if (dvox && k) FIESTA_HIP_CHECK(hipMemcpyAsync(vox, dvox, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(mask, dmask, k, hipMemcpyDeviceToHost, stream_));
+  if (dvox && k) FIESTA_HIP_CHECK(hipMemcpyAsync(a.vox, dvox, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(a.mask, dmask, k, hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }
 
-// fiesta_hip_reach_field[_dev] (reach_kernels.hpp); arguments checked by the caller.  The map has no outside: the box is taken as
-// given (clamped like the frontier call's); every page answers, resident or parked, and a tile without a page is unknown.
-void HashMap::reach_field(const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets, int64_t n_targets,
-                          double min_clearance, int connectivity, int flags, const fiesta_hip_reach_result &r, fiesta_hip_reach_info *info,
-                          bool dev) {
+// fiesta_hip_reach_field[_dev] (reach_kernels.hpp).  The map has no outside: the box is taken as given (clamped like the frontier
+// call's); every page answers, resident or parked, and a tile without a page is unknown.
+void HashMap::reach_field(const ReachArgs &a) {
   use_device();
-  auto c = [](int64_t v) { return std::min<int64_t>(std::max<int64_t>(v, -(1ll << 30)), 1ll << 30); };
   int64_t blo[3], bhi[3];
   bool empty = false;
-  for (int k = 0; k < 3; ++k) blo[k] = c(lo[k]), bhi[k] = c(hi[k]), empty = empty || blo[k] > bhi[k];
+  for (int k = 0; k < 3; ++k) blo[k] = clamp30(a.lo[k]), bhi[k] = clamp30(a.hi[k]), empty = empty || blo[k] > bhi[k];
   if (empty) blo[0] = 1, bhi[0] = 0;
   if (!empty) {  // (before anything is launched; each extent is below 2^32)
     const int64_t ex = bhi[0] - blo[0] + 1, ey = bhi[1] - blo[1] + 1, ez = bhi[2] - blo[2] + 1;
@@ -1607,50 +1598,30 @@ void HashMap::reach_field(const int32_t *lo, const int32_t *hi, const int32_t *s
   }
   const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
   const int off[3] = {0, 0, 0};
-  reach_run(stream_, reach_, path_in_, path_out_,
-            HashReachSource{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p}, blo, bhi, off,
-            ReachArgs{seeds, n_seeds, targets, n_targets, min_clearance, connectivity, flags, &r, info, dev});
+  reach_run(stream_, planner_, HashReachSource{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p}, blo, bhi, off, a);
 }
 
-// fiesta_hip_reach_paths[_dev] (reach_path_kernels.hpp); arguments checked by the caller.  Nothing of the map is read but its
-// resolution and origin, and the cost field the reachability scratch retains (or the caller's).
-void HashMap::reach_paths(const int32_t *cost, const int32_t *box_lo, const int32_t *box_hi, const int32_t *targets, int64_t n_targets,
-                     int connectivity, int flags, int max_span, int64_t capacity, const fiesta_hip_reach_paths_result &r, bool dev) {
-  use_device();
-  reach_paths_run(stream_, reach_, path_in_, path_out_, g_.res, g_.org,
-                  ReachPathArgs{cost, box_lo, box_hi, targets, n_targets, connectivity, flags, max_span, capacity, &r, dev});
-}
+// fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin
+void HashMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
+void HashMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
 
-// fiesta_hip_cluster_voxels[_dev] (cluster_kernels.hpp); arguments checked by the caller.  Nothing of the map is read but its
-// resolution and origin.
-void HashMap::cluster_voxels(const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const unsigned long long *n_dev, int connectivity,
-                             int min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *r,
-                             fiesta_hip_cluster_info *info, bool dev) {
-  use_device();
-  cluster_voxels_run(stream_, cluster_, path_in_, path_out_, g_.res, g_.org,
-                     ClusterArgs{vox, mask, key, n, n_dev, connectivity, min_size, cluster_capacity, member_capacity, r, info, dev});
-}
-
-// fiesta_hip_view_coverage[_dev] (view_kernels.hpp); arguments checked by the caller.  The ray query's source, the frontier call's
-// distance (map voxel coordinates).  Every page answers, resident or parked.
-void HashMap::view_coverage(const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups, const int64_t *n_groups_dev,
-                            int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *r,
-                            fiesta_hip_view_info *info, bool dev) {
+// fiesta_hip_view_coverage[_dev] (view_kernels.hpp).  The ray query's source, the frontier call's distance (map voxel
+// coordinates).  Every page answers, resident or parked.
+void HashMap::view_coverage(const ViewArgs &a) {
   use_device();
   const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
   const ViewSource<HashRaySource, HashFrontierPages> vs{
       HashRaySource{ray_geom(g_), g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p},
       HashFrontierPages{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}, {0, 0, 0}};
-  view_coverage_run(stream_, view_, path_in_, path_out_, vs, ViewArgs{vox, n, offsets, members, n_groups, n_groups_dev, n_members, views, sensor, r, info, dev});
+  view_coverage_run(stream_, planner_, vs, a);
 }
 
-// fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller.  Every page answers, resident or parked.
-void HashMap::ray_query(const double *start, const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev) {
-  if (n <= 0) return;
+// fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp).  Every page answers, resident or parked.
+void HashMap::ray_query(const RayArgs &a) {
+  if (a.n <= 0) return;
   use_device();
   const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
-  ray_query_run(stream_, path_in_, path_out_, HashRaySource{ray_geom(g_), g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p},
-                start, end, n, stop_mask, r, dev);
+  ray_query_run(stream_, planner_, HashRaySource{ray_geom(g_), g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p}, a);
 }
 
 int64_t HashMap::slice_marker(int slice, double max_dist, double *xyz, float *rgba, int64_t cap) {
@@ -1663,10 +1634,9 @@ int64_t HashMap::slice_marker(int slice, double max_dist, double *xyz, float *rg
     stage_b_.ensure((size_t)cap * 4 * sizeof(float), stream_);
     dx = (double *)stage_a_.p, dc = (float *)stage_b_.p;
   }
-  auto c = [](int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, -(1ll << 30)), 1ll << 30); };
   if (npages_)
     hipLaunchKernelGGL(k_h_slice_marker, dim3(grid_for(npages_ * kPageRows, 256, 8192)), dim3(256), 0, stream_, g_,
-                       (const int32_t *)page_gtile_.p, npages_, (const vox_t *)coc_.p, c(ur_[0]), c(ur_[3]), c(ur_[1]), c(ur_[4]), slice,
+                       (const int32_t *)page_gtile_.p, npages_, (const vox_t *)coc_.p, clamp30(ur_[0]), clamp30(ur_[3]), clamp30(ur_[1]), clamp30(ur_[4]), slice,
                        max_dist, dx, dc, (unsigned long long)(dx ? cap : 0), &counters_[C_SCRATCH]);
   FIESTA_HIP_CHECK(hipGetLastError());
   const int64_t n = (int64_t)read_counter(C_SCRATCH);

@@ -78,37 +78,21 @@ class HashMap {
   void get_dist_grad(const double *pos, int64_t n, double *dist, double *grad);
   void get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out);
   void get_occupancy_pos(const double *pos, int64_t n, int32_t *out);
-  // fiesta_hip_path_clearance[_dev] (path_kernels.hpp); arguments checked by the caller
-  void path_clearance(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-                      const fiesta_hip_path_result &r, bool dev);
-  // fiesta_hip_path_cost[_dev] (path_cost_kernels.hpp); arguments checked by the caller
-  void path_cost(const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-                 const fiesta_hip_path_cost_result &r, bool dev);
+  // the planner calls, as DenseMap's (reach_field: lo / hi are not null here)
+  void path_clearance(const PathArgs<fiesta_hip_path_result> &a);
+  void path_cost(const PathArgs<fiesta_hip_path_cost_result> &a);
+  int64_t frontier_voxels(const FrontierArgs &a);
+  void ray_query(const RayArgs &a);
+  void reach_field(const ReachArgs &a);
+  void reach_paths(const ReachPathArgs &a);
+  void cluster_voxels(const ClusterArgs &a);
+  void view_coverage(const ViewArgs &a);
   // every voxel of every allocated page, page order: vox (map voxel coordinates), d2, coc, occ; returns the count
   int64_t download(int32_t *vox, int32_t *d2, int32_t *coc, uint8_t *occ);
   void download_counts(int32_t *num_hit, int32_t *num_miss);  // same order as download()
   void checkpoint(const char *path, bool write);  // raw dump / load of the whole state (checkpoint.hpp)
   int64_t point_cloud(int vis_lower_bound, int vis_upper_bound, float *xyz, int64_t cap);  // GetPointCloud, as arrays
   int64_t slice_marker(int slice, double max_dist, double *xyz, float *rgba, int64_t cap);  // GetSliceMarker
-  // fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp); returns the total count (host variant; may exceed cap)
-  int64_t frontier_voxels(const int32_t *lo, const int32_t *hi, double min_clearance, int32_t *vox, uint8_t *mask, int64_t cap,
-                          unsigned long long *n_out_dev, bool dev);
-  // fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp); arguments checked by the caller
-  void ray_query(const double *start, const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev);
-  // fiesta_hip_reach_field[_dev] (reach_kernels.hpp); arguments checked by the caller (lo / hi are not null here)
-  void reach_field(const int32_t *lo, const int32_t *hi, const int32_t *seeds, int64_t n_seeds, const int32_t *targets, int64_t n_targets,
-                   double min_clearance, int connectivity, int flags, const fiesta_hip_reach_result &r, fiesta_hip_reach_info *info, bool dev);
-  // fiesta_hip_reach_paths[_dev] (reach_path_kernels.hpp); arguments checked by the caller
-  void reach_paths(const int32_t *cost, const int32_t *box_lo, const int32_t *box_hi, const int32_t *targets, int64_t n_targets, int connectivity,
-                   int flags, int max_span, int64_t capacity, const fiesta_hip_reach_paths_result &r, bool dev);
-  // fiesta_hip_cluster_voxels[_dev] (cluster_kernels.hpp); arguments checked by the caller
-  void cluster_voxels(const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const unsigned long long *n_dev, int connectivity,
-                      int min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *r,
-                      fiesta_hip_cluster_info *info, bool dev);
-  // fiesta_hip_view_coverage[_dev] (view_kernels.hpp); arguments checked by the caller
-  void view_coverage(const int32_t *vox, int64_t n, const int64_t *offsets, const int64_t *members, int64_t n_groups, const int64_t *n_groups_dev,
-                     int64_t n_members, const fiesta_hip_view_set *views, const fiesta_hip_view_sensor *sensor, const fiesta_hip_view_result *r,
-                     fiesta_hip_view_info *info, bool dev);
   void synchronize();
 
  private:
@@ -188,10 +172,7 @@ class HashMap {
   int64_t dropped_host_ = 0;  // voxels of observe_box() requests clipped away by the window (added to C_DROPPED in stats)
   unsigned long long *counters_ = nullptr, *h_counters_ = nullptr;
   DevBuf<unsigned char> stage_a_, stage_b_, stage_c_, stage_d_;
-  DevBuf<unsigned char> path_in_, path_tmp_, path_out_;  // path and ray queries: staged inputs, plan / piece records, staged outputs
-  ReachScratch reach_;
-  ClusterScratch cluster_;
-  ViewScratch view_;
+  PlannerScratch planner_;
 };
 
 void raycast_single(const double *start, const double *end, const double *minv, const double *maxv, double *out,

@@ -25,6 +25,8 @@
 #include "path_kernels.hpp"
 
 namespace fiesta {
+using PathCostArgs = PathArgs<fiesta_hip_path_cost_result>;
+
 namespace {  // (this header is included by two translation units)
 
 constexpr int kCostSegBlocks = 512;  // grid of k_cost_segments (a grid-stride loop over the piece records)
@@ -347,35 +349,23 @@ void path_cost_launch(hipStream_t st, DevBuf<unsigned char> &tmp, const Eval &ev
 
 // Both variants of the call on a map's stream, as path_clearance_run.
 template <class Eval>
-void path_cost_run(hipStream_t st, DevBuf<unsigned char> &in, DevBuf<unsigned char> &tmp, DevBuf<unsigned char> &out, const Eval &ev,
-                   const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-                   const fiesta_hip_path_cost_result &r, bool dev) {
-  if (dev) {
-    path_cost_launch(st, tmp, ev, w, n_wp, off, n_paths, step, margin, true, r);
+void path_cost_run(hipStream_t st, PlannerScratch &S, const Eval &ev, const PathCostArgs &a) {
+  const fiesta_hip_path_cost_result &r = *a.res;
+  if (a.dev) {
+    path_cost_launch(st, S.tmp, ev, a.w, a.n_wp, a.off, a.n_paths, a.step, a.margin, true, r);
     return;
   }
-  const size_t bw = (size_t)n_wp * 3 * sizeof(double), bo = (size_t)(n_paths + 1) * sizeof(int64_t);
-  in.ensure(bw + bo, st);
-  if (bw) FIESTA_HIP_CHECK(hipMemcpyAsync(in.p, w, bw, hipMemcpyHostToDevice, st));
-  FIESTA_HIP_CHECK(hipMemcpyAsync(in.p + bw, off, bo, hipMemcpyHostToDevice, st));
-  const size_t n = (size_t)n_paths, nw3 = (size_t)n_wp * 3;
-  out.ensure((4 * n + nw3) * 8, st);
-  double *o = (double *)out.p;
-  fiesta_hip_path_cost_result d{};
-  if (r.cost) d.cost = o;
-  if (r.length) d.length = o + n;
-  if (r.n_below) d.n_below = (int64_t *)(o + 2 * n);
-  if (r.n_samples) d.n_samples = (int64_t *)(o + 3 * n);
-  if (r.grad) d.grad = o + 4 * n;
-  path_cost_launch(st, tmp, ev, (const double *)in.p, n_wp, (const int64_t *)(in.p + bw), n_paths, step, margin, false, d);
-  auto back = [&](void *dst, const void *src, size_t words) {
-    if (dst && words) FIESTA_HIP_CHECK(hipMemcpyAsync(dst, src, words * 8, hipMemcpyDeviceToHost, st));
-  };
-  back(r.cost, d.cost, n);
-  back(r.length, d.length, n);
-  back(r.n_below, d.n_below, n);
-  back(r.n_samples, d.n_samples, n);
-  back(r.grad, d.grad, nw3);
+  const size_t n = (size_t)a.n_paths, nw3 = (size_t)a.n_wp * 3;
+  Staging in{S.in, st}, out{S.out, st};
+  const auto w = in.add(a.w, nw3);
+  const auto off = in.add(a.off, n + 1);
+  in.alloc(), in.up(w, nw3), in.up(off, n + 1);
+  const auto cost = out.add(r.cost, n), length = out.add(r.length, n), grad = out.add(r.grad, nw3);
+  const auto n_below = out.add(r.n_below, n), n_samples = out.add(r.n_samples, n);
+  out.alloc();
+  const fiesta_hip_path_cost_result d{out.dev(cost), out.dev(grad), out.dev(length), out.dev(n_below), out.dev(n_samples)};
+  path_cost_launch(st, S.tmp, ev, in.dev(w), a.n_wp, in.dev(off), a.n_paths, a.step, a.margin, false, d);
+  out.back(cost, n), out.back(length, n), out.back(n_below, n), out.back(n_samples, n), out.back(grad, nw3);
   FIESTA_HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -33,6 +33,20 @@
 #include "dense_map.hpp"
 
 namespace fiesta {
+// the arguments as fiesta_hip_path_clearance[_dev] and fiesta_hip_path_cost[_dev] take them (R: the call's result struct),
+// already checked
+template <typename R>
+struct PathArgs {
+  const double *w;
+  int64_t n_wp;
+  const int64_t *off;
+  int64_t n_paths;
+  double step, margin;
+  const R *res;
+  bool dev;
+};
+using PathClearanceArgs = PathArgs<fiesta_hip_path_result>;
+
 namespace {  // (this header is included by two translation units)
 
 constexpr long long kPathPiece = 1024;        // samples per piece at least (16 per lane of the wave that evaluates it)
@@ -362,42 +376,29 @@ void path_launch(hipStream_t st, DevBuf<unsigned char> &tmp, const Eval &ev, con
   FIESTA_HIP_CHECK(hipGetLastError());
 }
 
-// Both variants of the call on a map's stream.  Host variant: the inputs are staged into `in`, the requested outputs come back
-// through `out`, then the stream is synchronised.  Device variant: only enqueued.
+// Both variants of the call on a map's stream.  Host variant: the inputs are staged into S.in, the requested outputs come back
+// through S.out, then the stream is synchronised.  Device variant: only enqueued.
 template <class Eval>
-void path_clearance_run(hipStream_t st, DevBuf<unsigned char> &in, DevBuf<unsigned char> &tmp, DevBuf<unsigned char> &out, const Eval &ev,
-                        const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, double step, double margin,
-                        const fiesta_hip_path_result &r, bool dev) {
-  if (dev) {
-    path_launch(st, tmp, ev, w, n_wp, off, n_paths, step, margin, true, r);
+void path_clearance_run(hipStream_t st, PlannerScratch &S, const Eval &ev, const PathClearanceArgs &a) {
+  const fiesta_hip_path_result &r = *a.res;
+  if (a.dev) {
+    path_launch(st, S.tmp, ev, a.w, a.n_wp, a.off, a.n_paths, a.step, a.margin, true, r);
     return;
   }
-  const size_t bw = (size_t)n_wp * 3 * sizeof(double), bo = (size_t)(n_paths + 1) * sizeof(int64_t);
-  in.ensure(bw + bo, st);
-  if (bw) FIESTA_HIP_CHECK(hipMemcpyAsync(in.p, w, bw, hipMemcpyHostToDevice, st));
-  FIESTA_HIP_CHECK(hipMemcpyAsync(in.p + bw, off, bo, hipMemcpyHostToDevice, st));
-  const size_t n = (size_t)n_paths;
-  out.ensure(n * 13 * 8, st);  // the 7 fields: 13 words per path
-  double *o = (double *)out.p;
-  fiesta_hip_path_result d{};
-  if (r.min_dist) d.min_dist = o;
-  if (r.min_index) d.min_index = (int64_t *)(o + n);
-  if (r.min_pos) d.min_pos = o + 2 * n;
-  if (r.min_grad) d.min_grad = o + 5 * n;
-  if (r.first_below) d.first_below = (int64_t *)(o + 8 * n);
-  if (r.first_below_pos) d.first_below_pos = o + 9 * n;
-  if (r.n_samples) d.n_samples = (int64_t *)(o + 12 * n);
-  path_launch(st, tmp, ev, (const double *)in.p, n_wp, (const int64_t *)(in.p + bw), n_paths, step, margin, false, d);
-  auto back = [&](void *dst, const void *src, size_t words) {
-    if (dst) FIESTA_HIP_CHECK(hipMemcpyAsync(dst, src, words * 8, hipMemcpyDeviceToHost, st));
-  };
-  back(r.min_dist, d.min_dist, n);
-  back(r.min_index, d.min_index, n);
-  back(r.min_pos, d.min_pos, 3 * n);
-  back(r.min_grad, d.min_grad, 3 * n);
-  back(r.first_below, d.first_below, n);
-  back(r.first_below_pos, d.first_below_pos, 3 * n);
-  back(r.n_samples, d.n_samples, n);
+  const size_t n = (size_t)a.n_paths, nw3 = (size_t)a.n_wp * 3;
+  Staging in{S.in, st}, out{S.out, st};
+  const auto w = in.add(a.w, nw3);
+  const auto off = in.add(a.off, n + 1);
+  in.alloc(), in.up(w, nw3), in.up(off, n + 1);
+  const auto min_dist = out.add(r.min_dist, n), min_pos = out.add(r.min_pos, 3 * n), min_grad = out.add(r.min_grad, 3 * n),
+             first_below_pos = out.add(r.first_below_pos, 3 * n);
+  const auto min_index = out.add(r.min_index, n), first_below = out.add(r.first_below, n), n_samples = out.add(r.n_samples, n);
+  out.alloc();
+  const fiesta_hip_path_result d{out.dev(min_dist),    out.dev(min_index),       out.dev(min_pos),  out.dev(min_grad),
+                                 out.dev(first_below), out.dev(first_below_pos), out.dev(n_samples)};
+  path_launch(st, S.tmp, ev, in.dev(w), a.n_wp, in.dev(off), a.n_paths, a.step, a.margin, false, d);
+  out.back(min_dist, n), out.back(min_index, n), out.back(min_pos, 3 * n), out.back(min_grad, 3 * n);
+  out.back(first_below, n), out.back(first_below_pos, 3 * n), out.back(n_samples, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -22,6 +22,14 @@
 #include "ray_walk.hpp"
 
 namespace fiesta {
+struct RayArgs {  // the call's arguments as fiesta_hip_ray_query[_dev] takes them, already checked
+  const double *start, *end;
+  int64_t n;
+  int stop_mask;
+  const fiesta_hip_ray_result *res;
+  bool dev;
+};
+
 namespace {  // (this header is included by two translation units)
 
 constexpr double kRayMaxCoord = 1073741824.0;  // 2^30: |start / resolution| and |end / resolution| stay below it
@@ -145,40 +153,27 @@ void ray_query_launch(hipStream_t st, const SRC &src, const double *start, const
   FIESTA_HIP_CHECK(hipGetLastError());
 }
 
-// Both variants of the call on a map's stream.  Host variant: the inputs are staged into `in`, the requested outputs come back
-// through `out`, then the stream is synchronised.  Device variant: only enqueued.
+// Both variants of the call on a map's stream.  Host variant: the inputs are staged into S.in, the requested outputs come back
+// through S.out, then the stream is synchronised.  Device variant: only enqueued.
 template <class SRC>
-void ray_query_run(hipStream_t st, DevBuf<unsigned char> &in, DevBuf<unsigned char> &out, const SRC &src, const double *start,
-                   const double *end, int64_t n, int stop_mask, const fiesta_hip_ray_result &r, bool dev) {
-  if (dev) {
-    ray_query_launch(st, src, start, end, n, stop_mask, r);
+void ray_query_run(hipStream_t st, PlannerScratch &S, const SRC &src, const RayArgs &a) {
+  const fiesta_hip_ray_result &r = *a.res;
+  if (a.dev) {
+    ray_query_launch(st, src, a.start, a.end, a.n, a.stop_mask, r);
     return;
   }
-  const size_t cnt = (size_t)n, bp = cnt * 3 * sizeof(double);
-  in.ensure(2 * bp, st);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(in.p, start, bp, hipMemcpyHostToDevice, st));
-  FIESTA_HIP_CHECK(hipMemcpyAsync(in.p + bp, end, bp, hipMemcpyHostToDevice, st));
-  // the six fields, widest first: 8 + 16 + 12 + 4 + 4 + 1 bytes per ray, every section 8-byte aligned
-  const size_t o_dist = 0, o_counts = o_dist + cnt * 8, o_vox = o_counts + cnt * 16, o_nvis = o_vox + (cnt * 12 + 7) / 8 * 8,
-               o_hidx = o_nvis + (cnt * 4 + 7) / 8 * 8, o_cls = o_hidx + (cnt * 4 + 7) / 8 * 8, bytes = o_cls + cnt;
-  out.ensure(bytes, st);
-  fiesta_hip_ray_result d{};
-  if (r.n_visited) d.n_visited = (int32_t *)(out.p + o_nvis);
-  if (r.hit_index) d.hit_index = (int32_t *)(out.p + o_hidx);
-  if (r.hit_class) d.hit_class = (uint8_t *)(out.p + o_cls);
-  if (r.hit_vox) d.hit_vox = (int32_t *)(out.p + o_vox);
-  if (r.hit_dist) d.hit_dist = (double *)(out.p + o_dist);
-  if (r.counts) d.counts = (int32_t *)(out.p + o_counts);
-  ray_query_launch(st, src, (const double *)in.p, (const double *)(in.p + bp), n, stop_mask, d);
-  auto back = [&](void *dst, const void *from, size_t b) {
-    if (dst) FIESTA_HIP_CHECK(hipMemcpyAsync(dst, from, b, hipMemcpyDeviceToHost, st));
-  };
-  back(r.n_visited, d.n_visited, cnt * 4);
-  back(r.hit_index, d.hit_index, cnt * 4);
-  back(r.hit_class, d.hit_class, cnt);
-  back(r.hit_vox, d.hit_vox, cnt * 12);
-  back(r.hit_dist, d.hit_dist, cnt * 8);
-  back(r.counts, d.counts, cnt * 16);
+  const size_t n = (size_t)a.n;
+  Staging in{S.in, st}, out{S.out, st};
+  const auto start = in.add(a.start, 3 * n), end = in.add(a.end, 3 * n);
+  in.alloc(), in.up(start, 3 * n), in.up(end, 3 * n);
+  const auto n_visited = out.add(r.n_visited, n), hit_index = out.add(r.hit_index, n), hit_vox = out.add(r.hit_vox, 3 * n),
+             counts = out.add(r.counts, 4 * n);
+  const auto hit_class = out.add(r.hit_class, n);
+  const auto hit_dist = out.add(r.hit_dist, n);
+  out.alloc();
+  const fiesta_hip_ray_result d{out.dev(n_visited), out.dev(hit_index), out.dev(hit_class), out.dev(hit_vox), out.dev(hit_dist), out.dev(counts)};
+  ray_query_launch(st, src, in.dev(start), in.dev(end), a.n, a.stop_mask, d);
+  out.back(n_visited, n), out.back(hit_index, n), out.back(hit_class, n), out.back(hit_vox, 3 * n), out.back(hit_dist, n), out.back(counts, 4 * n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -28,6 +28,19 @@
 #include "relax_kernels.hpp"
 
 namespace fiesta {
+struct ReachArgs {  // the call's arguments as fiesta_hip_reach_field[_dev] takes them, already checked
+  const int32_t *lo, *hi;  // the caller's box (both null: the whole array)
+  const int32_t *seeds;
+  int64_t n_seeds;
+  const int32_t *targets;
+  int64_t n_targets;
+  double min_clearance;
+  int connectivity, flags;
+  const fiesta_hip_reach_result *res;
+  fiesta_hip_reach_info *info;
+  bool dev;
+};
+
 namespace {  // (this header is included by two translation units)
 
 constexpr int64_t kReachMaxVoxels = 1ll << 28;  // of the clipped box: keeps every cost below 2^31 (5 * 2^28) and bounds the scratch
@@ -220,25 +233,14 @@ __global__ void k_reach_fill(int32_t *out, int64_t n, int32_t v) {
   if (i < n) out[i] = v;
 }
 
-struct ReachArgs {  // the call's arguments as fiesta_hip_reach_field[_dev] takes them, already checked
-  const int32_t *seeds;
-  int64_t n_seeds;
-  const int32_t *targets;
-  int64_t n_targets;
-  double min_clearance;
-  int connectivity, flags;
-  const fiesta_hip_reach_result *res;
-  fiesta_hip_reach_info *info;
-  bool dev;
-};
-
 inline int reach_blocks(int64_t n, int per, int cap) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, cap)); }
 
 // Both variants of the call on a map's stream.  lo / hi: the clipped box in SRC's coordinates (lo[c] > hi[c]: empty); off: what
 // turns them into map voxel coordinates.  Both variants synchronise: the number of rounds depends on the data.
 template <class SRC>
-void reach_run(hipStream_t st, ReachScratch &S, DevBuf<unsigned char> &in, DevBuf<unsigned char> &out, const SRC &src, const int64_t lo[3],
-               const int64_t hi[3], const int off[3], const ReachArgs &a) {
+void reach_run(hipStream_t st, PlannerScratch &P, const SRC &src, const int64_t lo[3], const int64_t hi[3], const int off[3], const ReachArgs &a) {
+  ReachScratch &S = P.reach;
+  DevBuf<unsigned char> &in = P.in, &out = P.out;  // the staged seeds and targets; the staged target costs
   const fiesta_hip_reach_result &res = *a.res;
   S.field_valid = false;  // (fiesta_hip_reach_paths' retained field: only a call that finishes with its costs in S.cost leaves one)
   if (a.info) *a.info = fiesta_hip_reach_info{};

@@ -28,6 +28,17 @@
 #include "ray_walk.hpp"
 
 namespace fiesta {
+struct ReachPathArgs {  // the call's arguments as fiesta_hip_reach_paths[_dev] takes them, already checked
+  const int32_t *cost;  // null: the retained field
+  const int32_t *box_lo, *box_hi;
+  const int32_t *targets;
+  int64_t n_targets;
+  int connectivity, flags, max_span;
+  int64_t capacity;
+  const fiesta_hip_reach_paths_result *res;
+  bool dev;
+};
+
 namespace {  // (this header is included by two translation units)
 
 constexpr int64_t kReachPathMaxVoxels = 1ll << 28;  // of an explicit box (reach_field's bound)
@@ -268,17 +279,6 @@ __global__ __launch_bounds__(kReachPathBlock) void k_reach_path_write(ReachPathF
   }
 }
 
-struct ReachPathArgs {  // the call's arguments as fiesta_hip_reach_paths[_dev] takes them, already checked
-  const int32_t *cost;  // null: the retained field
-  const int32_t *box_lo, *box_hi;
-  const int32_t *targets;
-  int64_t n_targets;
-  int connectivity, flags, max_span;
-  int64_t capacity;
-  const fiesta_hip_reach_paths_result *res;
-  bool dev;
-};
-
 template <int CONN, bool SHORTCUT>
 void reach_path_passes(hipStream_t st, const ReachPathField &f, const ReachPathOut &o, const int32_t *targets, int64_t n, int max_span, bool count) {
   const int per = SHORTCUT ? kReachPathBlock / 64 : kReachPathBlock;
@@ -305,11 +305,12 @@ inline void reach_path_launch(hipStream_t st, const ReachPathField &f, const Rea
   }
 }
 
-// Both variants of the call on a map's stream; res / org: the map's resolution and origin.  The device variant only enqueues (count,
-// scan, write).  The host variant stages the targets through `in` and the outputs through `out`, reads the totals back between the
-// count and the write pass -- so that it stages min(total, capacity) waypoints, not the capacity -- and synchronises.
-inline void reach_paths_run(hipStream_t st, ReachScratch &S, DevBuf<unsigned char> &in, DevBuf<unsigned char> &out, double res, const double *org,
-                            const ReachPathArgs &a) {
+// Both variants of the call on a map's stream; res / org: the map's resolution and origin -- nothing else of a map is read, so
+// both stores share this function.  The device variant only enqueues (count, scan, write).  The host variant stages the targets
+// through P.in and the outputs through P.out, reads the totals back between the count and the write pass -- so that it stages
+// min(total, capacity) waypoints, not the capacity -- and synchronises.
+inline void reach_paths_run(hipStream_t st, PlannerScratch &P, double res, const double *org, const ReachPathArgs &a) {
+  ReachScratch &S = P.reach;
   const fiesta_hip_reach_paths_result &r = *a.res;
   ReachPathField f{};
   if (a.cost) {
@@ -353,33 +354,29 @@ inline void reach_paths_run(hipStream_t st, ReachScratch &S, DevBuf<unsigned cha
     return;
   }
   const size_t cnt = (size_t)n;
-  in.ensure(cnt * 3 * sizeof(int32_t), st);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(in.p, a.targets, cnt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  const int32_t *dt = (const int32_t *)in.p;
-  // offsets, then status and n_moves (8-byte aligned sections); the waypoints follow once their number is known
-  const size_t o_off = 0, o_st = (cnt + 1) * 8, o_mv = o_st + (cnt * 4 + 7) / 8 * 8, head = o_mv + (cnt * 4 + 7) / 8 * 8;
-  out.ensure(head, st);
-  ReachPathOut o{(int64_t *)(out.p + o_off), nullptr, nullptr, r.status ? (int32_t *)(out.p + o_st) : nullptr,
-                 r.n_moves ? (int32_t *)(out.p + o_mv) : nullptr, 0};
+  Staging in{P.in, st}, out{P.out, st};
+  const auto targets = in.add(a.targets, 3 * cnt);
+  in.alloc(), in.up(targets, 3 * cnt);
+  const int32_t *dt = in.dev(targets);
+  // offsets, status and n_moves; the waypoints follow once their number is known
+  const auto offsets = out.add(r.offsets, cnt + 1);
+  const auto status = out.add(r.status, cnt), n_moves = out.add(r.n_moves, cnt);
+  const size_t head = out.end;
+  out.alloc();
+  ReachPathOut o{out.dev(offsets), nullptr, nullptr, out.dev(status), out.dev(n_moves), 0};
   reach_path_launch(st, f, o, dt, n, a.connectivity, shortcut, a.max_span, true);
   hipLaunchKernelGGL(k_reach_path_scan, dim3(1), dim3(256), 0, st, o.offsets, n);
   FIESTA_HIP_CHECK(hipGetLastError());
-  FIESTA_HIP_CHECK(hipMemcpyAsync(r.offsets, o.offsets, (cnt + 1) * 8, hipMemcpyDeviceToHost, st));
-  if (r.status) FIESTA_HIP_CHECK(hipMemcpyAsync(r.status, o.status, cnt * 4, hipMemcpyDeviceToHost, st));
-  if (r.n_moves) FIESTA_HIP_CHECK(hipMemcpyAsync(r.n_moves, o.n_moves, cnt * 4, hipMemcpyDeviceToHost, st));
+  out.back(offsets, cnt + 1), out.back(status, cnt), out.back(n_moves, cnt);
   FIESTA_HIP_CHECK(hipStreamSynchronize(st));
   const int64_t w = std::min<int64_t>(r.offsets[n], a.capacity);
   if (w <= 0 || (!r.waypoints_vox && !r.waypoints_pos)) return;
-  const size_t o_pos = head, o_vox = o_pos + (r.waypoints_pos ? (size_t)w * 24 : 0), bytes = o_vox + (r.waypoints_vox ? (size_t)w * 12 : 0);
-  out.ensure(bytes, st, head);  // (the scanned offsets are kept: the write pass reads them)
-  o.offsets = (int64_t *)(out.p + o_off);
-  o.pos = r.waypoints_pos ? (double *)(out.p + o_pos) : nullptr;
-  o.vox = r.waypoints_vox ? (int32_t *)(out.p + o_vox) : nullptr;
-  o.status = o.n_moves = nullptr;
-  o.capacity = w;
+  const auto pos = out.add(r.waypoints_pos, 3 * (size_t)w);
+  const auto vox = out.add(r.waypoints_vox, 3 * (size_t)w);
+  out.alloc(head);  // (the buffer may move; the scanned offsets are kept: the write pass reads them)
+  o = ReachPathOut{out.dev(offsets), out.dev(vox), out.dev(pos), nullptr, nullptr, w};
   reach_path_launch(st, f, o, dt, n, a.connectivity, shortcut, a.max_span, false);
-  if (o.pos) FIESTA_HIP_CHECK(hipMemcpyAsync(r.waypoints_pos, o.pos, (size_t)w * 24, hipMemcpyDeviceToHost, st));
-  if (o.vox) FIESTA_HIP_CHECK(hipMemcpyAsync(r.waypoints_vox, o.vox, (size_t)w * 12, hipMemcpyDeviceToHost, st));
+  out.back(pos, 3 * (size_t)w), out.back(vox, 3 * (size_t)w);
   FIESTA_HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -39,6 +39,20 @@
 #include "ray_walk.hpp"
 
 namespace fiesta {
+struct ViewArgs {  // the call's arguments as fiesta_hip_view_coverage[_dev] takes them, already checked
+  const int32_t *vox;
+  int64_t n;
+  const int64_t *offsets, *members;
+  int64_t n_groups;
+  const int64_t *n_groups_dev;
+  int64_t n_members;
+  const fiesta_hip_view_set *views;
+  const fiesta_hip_view_sensor *sensor;
+  const fiesta_hip_view_result *res;
+  fiesta_hip_view_info *info;
+  bool dev;
+};
+
 namespace {  // (this header is included by two translation units)
 
 constexpr int kViewBlock = 256, kViewMaxBlocks = 2048;
@@ -387,19 +401,6 @@ __global__ __launch_bounds__(kViewBlock) void k_view_groups(ViewWork w, ViewIn i
     info->n_usable = (int64_t)w.ctr[0], info->n_pairs = (int64_t)w.ctr[1], info->n_in_view = (int64_t)w.ctr[2], info->n_visible = (int64_t)w.ctr[3];
 }
 
-struct ViewArgs {  // the call's arguments as fiesta_hip_view_coverage[_dev] takes them, already checked
-  const int32_t *vox;
-  int64_t n;
-  const int64_t *offsets, *members;
-  int64_t n_groups;
-  const int64_t *n_groups_dev;
-  int64_t n_members;
-  const fiesta_hip_view_set *views;
-  const fiesta_hip_view_sensor *sensor;
-  const fiesta_hip_view_result *res;
-  fiesta_hip_view_info *info;
-  bool dev;
-};
 inline int64_t view_count_of(const ViewArgs &a) { return a.views->pos ? a.views->n_views : (a.offsets ? a.n_groups : 1) * a.views->n_ring; }
 
 // enqueue the passes; every pointer of `in` (but centroid / ring: device pointers too), `o` and info is a device pointer
@@ -438,9 +439,10 @@ void view_enqueue(hipStream_t st, ViewScratch &S, const VS &vs, ViewIn in, const
 }
 
 // Both variants of the call on a map's stream.  The device variant only enqueues.  The host variant stages the inputs through
-// `in` and every output through `out`, synchronises and copies back.
+// P.in and every output through P.out, synchronises and copies back.
 template <class VS>
-void view_coverage_run(hipStream_t st, ViewScratch &S, DevBuf<unsigned char> &in, DevBuf<unsigned char> &out, const VS &vs, const ViewArgs &a) {
+void view_coverage_run(hipStream_t st, PlannerScratch &P, const VS &vs, const ViewArgs &a) {
+  ViewScratch &S = P.view;
   const fiesta_hip_view_result none{};
   const fiesta_hip_view_result &r = a.res ? *a.res : none;
   const fiesta_hip_view_set &vw = *a.views;
@@ -451,51 +453,25 @@ void view_coverage_run(hipStream_t st, ViewScratch &S, DevBuf<unsigned char> &in
     return;
   }
   const size_t n = (size_t)a.n, g = (size_t)G, v = (size_t)V, nm = (size_t)NM, ring = vw.pos ? 0 : (size_t)vw.n_ring;
-  const auto up8 = [](size_t b) { return (b + 7) / 8 * 8; };
-  // inputs (8-byte aligned sections): offsets, members, pos | centroid, dir | ring, vox, group
-  const size_t i_off = 0, i_mem = i_off + (a.offsets ? (g + 1) * 8 : 0), i_pos = i_mem + (a.members ? nm * 8 : 0),
-               i_dir = i_pos + (vw.pos ? v * 24 : g * 24), i_vox = i_dir + (vw.pos ? (vw.dir ? v * 16 : 0) : ring * 40), i_grp = i_vox + up8(n * 12),
-               i_end = i_grp + up8(vw.pos && vw.group ? v * 4 : 0);
-  in.ensure(std::max<size_t>(i_end, 8), st);
-  const auto up = [&](size_t off, const void *src, size_t bytes) {
-    if (src && bytes) FIESTA_HIP_CHECK(hipMemcpyAsync(in.p + off, src, bytes, hipMemcpyHostToDevice, st));
-  };
-  up(i_off, a.offsets, (g + 1) * 8), up(i_mem, a.members, nm * 8), up(i_vox, a.vox, n * 12);
-  if (vw.pos)
-    up(i_pos, vw.pos, v * 24), up(i_dir, vw.dir, v * 16), up(i_grp, vw.group, v * 4);
-  else
-    up(i_pos, vw.centroid, g * 24), up(i_dir, vw.ring, ring * 40);
-  const ViewIn vi{(const int32_t *)(in.p + i_vox),
-                  a.offsets ? (const int64_t *)(in.p + i_off) : nullptr,
-                  a.members ? (const int64_t *)(in.p + i_mem) : nullptr,
-                  nullptr,
-                  a.n,
-                  G,
-                  NM,
-                  vw.pos ? (const double *)(in.p + i_pos) : nullptr,
-                  vw.pos && vw.dir ? (const double *)(in.p + i_dir) : nullptr,
-                  vw.pos && vw.group ? (const int32_t *)(in.p + i_grp) : nullptr,
-                  V};
-  // outputs: info, best_view, then the 4-byte arrays, then the bytes
-  const size_t o_info = 0, o_best = up8(sizeof(fiesta_hip_view_info)), o_bcnt = o_best + g * 8, o_nin = o_bcnt + up8(g * 4), o_nvis = o_nin + up8(v * 4),
-               o_cov = o_nvis + up8(v * 4), o_first = o_cov + up8(n * 4), o_cls = o_first + up8(n * 4), o_end = o_cls + up8(v);
-  out.ensure(o_end, st);
-  unsigned char *b = out.p;
-  const fiesta_hip_view_result d{r.view_class ? b + o_cls : nullptr,
-                                 r.n_in_view ? (int32_t *)(b + o_nin) : nullptr,
-                                 r.n_visible ? (int32_t *)(b + o_nvis) : nullptr,
-                                 r.cover_count ? (int32_t *)(b + o_cov) : nullptr,
-                                 r.first_view ? (int32_t *)(b + o_first) : nullptr,
-                                 r.best_view ? (int64_t *)(b + o_best) : nullptr,
-                                 r.best_count ? (int32_t *)(b + o_bcnt) : nullptr};
-  view_enqueue(st, S, vs, vi, vw.pos ? nullptr : (const double *)(in.p + i_pos), (const double *)(in.p + i_dir), vw.n_ring, *a.sensor, d,
-               (fiesta_hip_view_info *)(b + o_info));
-  const auto back = [&](void *dst, size_t off, size_t bytes) {
-    if (dst && bytes) FIESTA_HIP_CHECK(hipMemcpyAsync(dst, b + off, bytes, hipMemcpyDeviceToHost, st));
-  };
-  back(a.info, o_info, sizeof(fiesta_hip_view_info));
-  back(r.view_class, o_cls, v), back(r.n_in_view, o_nin, v * 4), back(r.n_visible, o_nvis, v * 4), back(r.cover_count, o_cov, n * 4);
-  back(r.first_view, o_first, n * 4), back(r.best_view, o_best, g * 8), back(r.best_count, o_bcnt, g * 4);
+  Staging in{P.in, st}, out{P.out, st};
+  // exactly one of pos and centroid is given; dir and group belong to the explicit form, and the other form's ring is empty
+  const auto offsets = in.add(a.offsets, g + 1), members = in.add(a.members, nm);
+  const auto pos = in.add(vw.pos, 3 * v), dir = in.add(vw.pos ? vw.dir : nullptr, 2 * v), centroid = in.add(vw.centroid, 3 * g), rg = in.add(vw.ring, 5 * ring);
+  const auto vox = in.add(a.vox, 3 * n), group = in.add(vw.pos ? vw.group : nullptr, v);
+  in.alloc();
+  in.up(offsets, g + 1), in.up(members, nm), in.up(vox, 3 * n), in.up(pos, 3 * v), in.up(dir, 2 * v), in.up(group, v), in.up(centroid, 3 * g), in.up(rg, 5 * ring);
+  const ViewIn vi{in.dev(vox), in.dev(offsets), in.dev(members), nullptr, a.n, G, NM, in.dev(pos), in.dev(dir), in.dev(group), V};
+  const auto info = out.add(a.info, 1);
+  const auto best_view = out.add(r.best_view, g);
+  const auto best_count = out.add(r.best_count, g), n_in_view = out.add(r.n_in_view, v), n_visible = out.add(r.n_visible, v),
+             cover_count = out.add(r.cover_count, n), first_view = out.add(r.first_view, n);
+  const auto view_class = out.add(r.view_class, v);
+  out.alloc();
+  const fiesta_hip_view_result d{out.dev(view_class), out.dev(n_in_view), out.dev(n_visible), out.dev(cover_count),
+                                 out.dev(first_view), out.dev(best_view), out.dev(best_count)};
+  view_enqueue(st, S, vs, vi, in.dev(centroid), in.dev(rg), vw.n_ring, *a.sensor, d, out.dev(info));
+  out.back(info, 1), out.back(view_class, v), out.back(n_in_view, v), out.back(n_visible, v), out.back(cover_count, n);
+  out.back(first_view, n), out.back(best_view, g), out.back(best_count, g);
   FIESTA_HIP_CHECK(hipStreamSynchronize(st));
 }
 
