@@ -2778,12 +2778,12 @@ void DenseMap::snapshot_save(int slot) {
 }
 
 void DenseMap::snapshot_restore(int slot) {
+  if (slot < 0 || slot >= 4 || !snaps_[slot].valid) throw Error(FIESTA_HIP_ERR_STATE, "no such snapshot");  // (a refused call changes nothing)
   ++field_epoch_;  // (the host-side brick cache of the scalar queries is stale from here on)
   nn_clean_ = false;  // (the counters come back as they were saved)
   nn_valid_ = false;
   mask_obs_count_ = -1;
   use_device();
-  if (slot < 0 || slot >= 4 || !snaps_[slot].valid) throw Error(FIESTA_HIP_ERR_STATE, "no such snapshot");
   Snapshot &s = snaps_[slot];
   const int64_t n = g_.n;
   FIESTA_HIP_CHECK(hipMemcpyAsync(coc_, s.coc.p, n * sizeof(vox_t), hipMemcpyDeviceToDevice, stream_));

@@ -869,13 +869,19 @@ int fiesta_hip_get_slice_marker(fiesta_hip_map *m, int32_t slice, double max_dis
 int fiesta_hip_download_hash(fiesta_hip_map *m, int64_t *n_out, int32_t *vox, int32_t *d2, int32_t *coc,
                              uint8_t *occ);
 
-/* Device-side snapshots of the complete map state (benchmark repetitions, tests). slot in [0,3].
+/* Device-side snapshots of the map's state (benchmark repetitions, tests). slot in [0,3].  A snapshot holds everything an
+ * update reads or writes: the field, log-odds, occupancy, the pending observation counts and the touched list, both queues,
+ * the update range and its predecessor, the gates' bookkeeping.  It does NOT hold the probability parameters (a checkpoint
+ * file does): fiesta_hip_set_prob_params after a save survives the restore.  A call with a slot out of range or never saved
+ * fails and leaves the map as it was.
  * Hash-block maps: slot 0 only, save + count_updated only (one copy of the state words; restore is an error). */
 int fiesta_hip_snapshot_save(fiesta_hip_map *m, int32_t slot);
 int fiesta_hip_snapshot_restore(fiesta_hip_map *m, int32_t slot);
 /* Number of voxels whose (d2, closest obstacle) differs between snapshot `slot` and the current state,
  * counted as SURVEY.md 8d defines an "updated voxel": d2 differs, or the old closest obstacle is no longer
- * occupied. */
+ * occupied.  A voxel that only names another of several equidistant obstacles is not updated; a shard counts the box it
+ * owns, a hash-block map the pages inside its window.  The definition holds for a field that is up to date: a count taken
+ * between UpdateOccupancy and UpdateESDF is outside what this call promises. */
 int fiesta_hip_snapshot_count_updated(fiesta_hip_map *m, int32_t slot, int64_t *updated);
 
 /* ---- multi-GPU: one map = one SHARD of a larger grid; used by the sharded driver ----
