@@ -96,6 +96,17 @@ class ReachInfo(C.Structure):
                 ("n_reached", C.c_int64), ("max_cost", C.c_int64), ("rounds", C.c_int64), ("tile_visits", C.c_int64)]
 
 
+class ReachMatrixResult(C.Structure):
+    """fiesta_hip_reach_matrix_result: one array per output of fiesta_hip_reach_matrix, every pointer nullable"""
+    _fields_ = [("cost", C.c_void_p), ("source_status", C.c_void_p), ("source_reached", C.c_void_p)]
+
+
+class ReachMatrixInfo(C.Structure):
+    """fiesta_hip_reach_matrix_info: the clipped box and the counters of one fiesta_hip_reach_matrix call"""
+    _fields_ = [("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3), ("n_traversable", C.c_int64), ("n_sources_used", C.c_int64),
+                ("fields", C.c_int64), ("batches", C.c_int64), ("rounds", C.c_int64), ("tile_visits", C.c_int64)]
+
+
 class ReachPathsResult(C.Structure):
     """fiesta_hip_reach_paths_result: offsets is required, every other pointer nullable"""
     _fields_ = [("offsets", C.c_void_p), ("waypoints_vox", C.c_void_p), ("waypoints_pos", C.c_void_p), ("status", C.c_void_p),
@@ -240,6 +251,8 @@ def load():
         "fiesta_hip_ray_query_dev": (C.c_int, [vp, vp, vp, i64, i32, vp]),
         "fiesta_hip_reach_field": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, vp, vp]),
         "fiesta_hip_reach_field_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, vp, vp]),
+        "fiesta_hip_reach_matrix": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i32, vp, vp]),
+        "fiesta_hip_reach_matrix_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i32, vp, vp]),
         "fiesta_hip_reach_paths": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
         "fiesta_hip_reach_paths_dev": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
         "fiesta_hip_cluster_voxels": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, i64, vp, vp]),

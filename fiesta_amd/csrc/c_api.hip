@@ -7,13 +7,14 @@
 #include <string>
 
 #include "../../include/fiesta_hip.h"
-#include "cluster_kernels.hpp"  // (the eight planner headers: for the calls' argument aggregates; no kernel is used here)
+#include "cluster_kernels.hpp"  // (the nine planner headers: for the calls' argument aggregates; no kernel is used here)
 #include "dense_map.hpp"
 #include "frontier_kernels.hpp"
 #include "hash_map.hpp"
 #include "path_cost_kernels.hpp"
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
+#include "reach_matrix_kernels.hpp"
 #include "reach_path_kernels.hpp"
 #include "shard_group.hpp"
 #include "view_kernels.hpp"
@@ -118,6 +119,24 @@ void reach_field(fiesta_hip_map *m, const fiesta::ReachArgs &a) {
   need(m != nullptr, "null map handle");
   need(m->dense != nullptr || a.lo != nullptr, "reach_field: a hash-block map has no outside, the box is mandatory");
   on_store(m, [&](auto &s) { s.reach_field(a); });
+}
+// reach_field's list and the matrix's own; none needs a device
+void reach_matrix(fiesta_hip_map *m, const fiesta::ReachMatrixArgs &a) {
+  need(a.res != nullptr, "reach_matrix: result is null");
+  need(!std::isnan(a.min_clearance), "reach_matrix: min_clearance is NaN");
+  need((a.lo == nullptr) == (a.hi == nullptr), "reach_matrix: lo and hi must both be given or both be null");
+  need(a.connectivity == 6 || a.connectivity == 26, "reach_matrix: connectivity must be 6 or 26");
+  need((a.flags & ~FIESTA_HIP_REACH_THROUGH_UNKNOWN) == 0, "reach_matrix: unknown flag bits");
+  need(a.max_fields >= 0, "reach_matrix: max_fields is negative");
+  need(a.n_sources >= 0 && a.n_targets >= 0, "reach_matrix: negative count");
+  need(a.sources != nullptr || a.n_sources == 0, "reach_matrix: sources is null");
+  need(a.targets != nullptr || a.n_targets == 0, "reach_matrix: targets is null");
+  constexpr int64_t cap = 1ll << 28;  // (each factor is tested first: the product of two such factors cannot overflow)
+  const int64_t n_cols = a.targets ? a.n_targets : a.n_sources;
+  need(a.n_sources <= cap && n_cols <= cap && a.n_sources * n_cols <= cap, "reach_matrix: the matrix holds more than 2^28 entries");
+  need(m != nullptr, "null map handle");
+  need(m->dense != nullptr || a.lo != nullptr, "reach_matrix: a hash-block map has no outside, the box is mandatory");
+  on_store(m, [&](auto &s) { s.reach_matrix(a); });
 }
 // none of these errors needs a device, and all but the last are checked before the handle is touched
 void reach_paths(fiesta_hip_map *m, const fiesta::ReachPathArgs &a) {
@@ -532,6 +551,19 @@ int fiesta_hip_reach_field_dev(fiesta_hip_map *m, const int32_t lo[3], const int
                                const int32_t *targets_dev, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
                                const fiesta_hip_reach_result *result, fiesta_hip_reach_info *info) {
   return guarded([&] { reach_field(m, {lo, hi, seeds_dev, n_seeds, targets_dev, n_targets, min_clearance, connectivity, flags, result, info, true}); });
+}
+int fiesta_hip_reach_matrix(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *sources, int64_t n_sources,
+                            const int32_t *targets, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
+                            int32_t max_fields, const fiesta_hip_reach_matrix_result *result, fiesta_hip_reach_matrix_info *info) {
+  return guarded(
+      [&] { reach_matrix(m, {lo, hi, sources, n_sources, targets, n_targets, min_clearance, connectivity, flags, max_fields, result, info, false}); });
+}
+int fiesta_hip_reach_matrix_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *sources_dev, int64_t n_sources,
+                                const int32_t *targets_dev, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
+                                int32_t max_fields, const fiesta_hip_reach_matrix_result *result, fiesta_hip_reach_matrix_info *info) {
+  return guarded([&] {
+    reach_matrix(m, {lo, hi, sources_dev, n_sources, targets_dev, n_targets, min_clearance, connectivity, flags, max_fields, result, info, true});
+  });
 }
 int fiesta_hip_reach_paths(fiesta_hip_map *m, const int32_t *cost, const int32_t box_lo[3], const int32_t box_hi[3], const int32_t *targets,
                            int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span, int64_t capacity,

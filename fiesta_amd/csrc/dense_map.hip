@@ -27,6 +27,7 @@
 #include "frontier_kernels.hpp"
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
+#include "reach_matrix_kernels.hpp"
 #include "reach_path_kernels.hpp"
 #include "cluster_kernels.hpp"
 #include "view_kernels.hpp"
@@ -2631,16 +2632,26 @@ int64_t DenseMap::frontier_voxels(const FrontierArgs &a) {
 
 // fiesta_hip_reach_field[_dev] (reach_kernels.hpp).  The padding bits of a row's last bitmap word lie past the clipped box and are
 // masked there.
-void DenseMap::reach_field(const ReachArgs &a) {
+void DenseMap::reach_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]) {
   use_device();
-  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0};
-  int64_t blo[3], bhi[3];
-  const bool empty = !clip_box(a.lo, a.hi, blo, bhi);
+  const bool empty = !clip_box(lo, hi, blo, bhi);
   if (empty) blo[0] = 1, bhi[0] = 0;
   if (!empty && (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * (bhi[2] - blo[2] + 1) > kReachMaxVoxels)  // (before anything is launched)
-    throw Error(FIESTA_HIP_ERR_INVALID, "reach_field: the clipped box holds more than 2^28 voxels");
+    throw Error(FIESTA_HIP_ERR_INVALID, "reach: the clipped box holds more than 2^28 voxels");
   if (!empty) sync_obsbits();
+}
+void DenseMap::reach_field(const ReachArgs &a) {
+  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0};
+  int64_t blo[3], bhi[3];
+  reach_box(a.lo, a.hi, blo, bhi);
   reach_run(stream_, planner_, DenseReachSource{g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, (const vox_t *)coc_}, blo, bhi, g0, a);
+}
+// fiesta_hip_reach_matrix[_dev] (reach_matrix_kernels.hpp): reach_field's box and source
+void DenseMap::reach_matrix(const ReachMatrixArgs &a) {
+  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0};
+  int64_t blo[3], bhi[3];
+  reach_box(a.lo, a.hi, blo, bhi);
+  reach_matrix_run(stream_, planner_, DenseReachSource{g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, (const vox_t *)coc_}, blo, bhi, g0, a);
 }
 
 // fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin

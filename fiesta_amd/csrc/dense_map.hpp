@@ -62,6 +62,15 @@ struct ReachScratch {
   int field_connectivity = 0;
 };
 
+// scratch of fiesta_hip_reach_matrix (reach_matrix_kernels.hpp), owned by a map: the cost planes of one batch of floods, the flags and
+// lists of their (flood, tile) items for both round parities, the counters, and the per-source status and reached counts; allocated
+// on first use, grown on demand, freed with the map.  (The bitmap is ReachScratch::bits; ReachScratch::cost is never touched.)
+struct ReachMatrixScratch {
+  DevBuf<int32_t> planes, status;
+  DevBuf<uint32_t> flags, lists;
+  DevBuf<unsigned long long> ctr, reached;
+};
+
 // scratch of fiesta_hip_cluster_voxels (cluster_kernels.hpp), owned by a map: the voxel hash table, the per-entry union-find arrays,
 // the per-cluster accumulators and two counters; allocated on first use, grown on demand, freed with the map
 struct ClusterScratch {
@@ -81,10 +90,11 @@ struct ViewScratch {
 };
 
 // what the planner calls (path clearance ... view coverage) keep between calls, one per map: the staged inputs of a host variant,
-// the path calls' plan / piece records, the staged outputs, and the three calls' own scratch
+// the path calls' plan / piece records, the staged outputs, and the four calls' own scratch
 struct PlannerScratch {
   DevBuf<unsigned char> in, tmp, out;
   ReachScratch reach;
+  ReachMatrixScratch reach_matrix;
   ClusterScratch cluster;
   ViewScratch view;
 };
@@ -128,6 +138,7 @@ struct PathArgs;
 struct FrontierArgs;
 struct RayArgs;
 struct ReachArgs;
+struct ReachMatrixArgs;
 struct ReachPathArgs;
 struct ClusterArgs;
 struct ViewArgs;
@@ -238,6 +249,7 @@ class DenseMap {
   int64_t frontier_voxels(const FrontierArgs &a);  // returns the total count (host variant; may exceed the capacity)
   void ray_query(const RayArgs &a);
   void reach_field(const ReachArgs &a);
+  void reach_matrix(const ReachMatrixArgs &a);
   void reach_paths(const ReachPathArgs &a);
   void cluster_voxels(const ClusterArgs &a);
   void view_coverage(const ViewArgs &a);
@@ -320,6 +332,7 @@ class DenseMap {
   void sync_obsbits();
   // a caller's box (null: everything) in local array coordinates, intersected with the array; false: nothing is left
   bool clip_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]) const;
+  void reach_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]);  // the reach calls' clipped box, checked; empty: blo[0] > bhi[0]
 
   Geom g_;
   ProbParams pp_;

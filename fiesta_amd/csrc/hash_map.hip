@@ -22,6 +22,7 @@
 #include "frontier_kernels.hpp"
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
+#include "reach_matrix_kernels.hpp"
 #include "reach_path_kernels.hpp"
 #include "cluster_kernels.hpp"
 #include "view_kernels.hpp"
@@ -1585,20 +1586,31 @@ int64_t HashMap::frontier_voxels(const FrontierArgs &a) {
 
 // fiesta_hip_reach_field[_dev] (reach_kernels.hpp).  The map has no outside: the box is taken as given (clamped like the frontier
 // call's); every page answers, resident or parked, and a tile without a page is unknown.
-void HashMap::reach_field(const ReachArgs &a) {
+void HashMap::reach_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]) {
   use_device();
-  int64_t blo[3], bhi[3];
   bool empty = false;
-  for (int k = 0; k < 3; ++k) blo[k] = clamp30(a.lo[k]), bhi[k] = clamp30(a.hi[k]), empty = empty || blo[k] > bhi[k];
+  for (int k = 0; k < 3; ++k) blo[k] = clamp30(lo[k]), bhi[k] = clamp30(hi[k]), empty = empty || blo[k] > bhi[k];
   if (empty) blo[0] = 1, bhi[0] = 0;
   if (!empty) {  // (before anything is launched; each extent is below 2^32)
     const int64_t ex = bhi[0] - blo[0] + 1, ey = bhi[1] - blo[1] + 1, ez = bhi[2] - blo[2] + 1;
     if (ex > kReachMaxVoxels || ey > kReachMaxVoxels || ex * ey > kReachMaxVoxels || ex * ey * ez > kReachMaxVoxels)
-      throw Error(FIESTA_HIP_ERR_INVALID, "reach_field: the box holds more than 2^28 voxels");
+      throw Error(FIESTA_HIP_ERR_INVALID, "reach: the box holds more than 2^28 voxels");
   }
+}
+void HashMap::reach_field(const ReachArgs &a) {
+  int64_t blo[3], bhi[3];
+  reach_box(a.lo, a.hi, blo, bhi);
   const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
   const int off[3] = {0, 0, 0};
   reach_run(stream_, planner_, HashReachSource{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p}, blo, bhi, off, a);
+}
+// fiesta_hip_reach_matrix[_dev] (reach_matrix_kernels.hpp): reach_field's box and source; the page table is rebuilt once per call
+void HashMap::reach_matrix(const ReachMatrixArgs &a) {
+  int64_t blo[3], bhi[3];
+  reach_box(a.lo, a.hi, blo, bhi);
+  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
+  const int off[3] = {0, 0, 0};
+  reach_matrix_run(stream_, planner_, HashReachSource{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p}, blo, bhi, off, a);
 }
 
 // fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin

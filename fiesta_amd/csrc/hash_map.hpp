@@ -84,6 +84,7 @@ class HashMap {
   int64_t frontier_voxels(const FrontierArgs &a);
   void ray_query(const RayArgs &a);
   void reach_field(const ReachArgs &a);
+  void reach_matrix(const ReachMatrixArgs &a);
   void reach_paths(const ReachPathArgs &a);
   void cluster_voxels(const ClusterArgs &a);
   void view_coverage(const ViewArgs &a);
@@ -110,6 +111,7 @@ class HashMap {
   void run_rounds(fiesta_hip_stats *st, uint32_t first_count);
   bool run_levels(fiesta_hip_stats *st, unsigned long long ni, unsigned long long nd);  // false: the rounds finish
   PageTable page_table();  // the map-wide page table of the query kernels (hash_map.hip)
+  void reach_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]);  // the reach calls' clamped box, checked; empty: blo[0] > bhi[0]
   // scalar queries (n <= kHostQueries positions per call, host pointers): a host-side cache of 16^3-voxel bricks of DISTANCES (f64,
   // as the query kernels compute them) and occupancy bits, keyed by map brick coordinates, fetched on first touch (r06: the dense
   // map's HostBricks for the paged map).  field_epoch_ is bumped by everything that may change the field or what a lookup finds.

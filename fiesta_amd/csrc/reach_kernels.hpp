@@ -129,81 +129,87 @@ __global__ __launch_bounds__(256) void k_reach_seed(ReachBox b, int ox, int oy, 
 // improvement is lost; and since a wake-up for round r + 1 goes to the flags and the list of the other parity, it cannot be erased
 // by the tile clearing its own flag of round r.  The same holds inside LDS between the lanes of one sweep: the loop ends only after
 // a sweep in which, between two barriers, no lane changed anything, i.e. every lane has seen the final values of its neighbours.
+//
+// The visit of one tile by one work-group of 256 lanes, shared by k_reach_relax and the batched floods of reach_matrix_kernels.hpp
+// (k_rmx_relax): `cost` is the field (there: the flood's own plane), `t` the tile, and `item0` what the flags and lists add to a
+// tile index (0 here; there flood * ntiles, so that a lowered outer layer wakes the neighbouring tile OF THE SAME FLOOD).
 template <int CONN>
-__global__ __launch_bounds__(256) void k_reach_relax(ReachBox b, const uint32_t *bits, int32_t *cost, ReachRound r) {
+__device__ __forceinline__ void reach_relax_tile(const ReachBox &b, const uint32_t *bits, int32_t *cost, const ReachRound &r, int t, uint32_t item0) {
   __shared__ int s_c[kReachLds];
   __shared__ int s_wake[27];
   const int tid = threadIdx.x, lx = tid >> 4, ly = tid & 15;
+  const int tz = t % b.nzw, ty = (t / b.nzw) % b.nty, tx = t / (b.nzw * b.nty);
+  if (tid == 0) r.flag_cur[item0 + (uint32_t)t] = 0;
+  if (tid < 27) s_wake[tid] = 0;
+  for (int i = tid; i < kReachLds; i += 256) {
+    const int hz = i % 34, hy = (i / 34) % 18, hx = i / kReachPitchY;
+    const int x = tx * 16 - 1 + hx, y = ty * 16 - 1 + hy, z = tz * 32 - 1 + hz;
+    int v = kReachBig;  // outside the box, not traversable, not reached: nothing to pull from
+    if ((unsigned)x < (unsigned)b.ex && (unsigned)y < (unsigned)b.ey && (unsigned)z < (unsigned)b.ez) {
+      const int c = cost[((int64_t)x * b.ey + y) * b.ez + z];
+      if (c >= 0 && c != INT32_MAX) v = c;
+    }
+    s_c[i] = v;
+  }
+  const int x = tx * 16 + lx, y = ty * 16 + ly;
+  const uint32_t own = (x < b.ex && y < b.ey) ? bits[(x * b.ey + y) * b.nzw + tz] : 0u;  // this lane's column: one word
+  const int base = (lx + 1) * kReachPitchY + (ly + 1) * kReachPitchZ + 1;
+  __syncthreads();
+  uint32_t chg = 0;  // voxels of the column whose cost this visit lowered
+  for (int sweep = 0;; ++sweep) {
+    bool ch = false;
+    for (uint32_t m = own; m;) {  // (a word without traversable voxels is skipped) upwards and downwards in turn
+      const int z = (sweep & 1) ? 31 - __clz((int)m) : __ffs((int)m) - 1;
+      m &= ~(1u << z);
+      const int p = base + z, cur = s_c[p];
+      int best = cur;
+#define FIESTA_REACH_PULL(DX, DY, DZ, W) best = min(best, s_c[p + (DX) * kReachPitchY + (DY) * kReachPitchZ + (DZ)] + (W));
+      FIESTA_REACH_PULL(0, 0, -1, 3) FIESTA_REACH_PULL(0, 0, 1, 3) FIESTA_REACH_PULL(-1, 0, 0, 3) FIESTA_REACH_PULL(1, 0, 0, 3)
+      FIESTA_REACH_PULL(0, -1, 0, 3) FIESTA_REACH_PULL(0, 1, 0, 3)
+      if (CONN == 26) {
+        FIESTA_REACH_PULL(-1, -1, 0, 4) FIESTA_REACH_PULL(-1, 1, 0, 4) FIESTA_REACH_PULL(1, -1, 0, 4) FIESTA_REACH_PULL(1, 1, 0, 4)
+        FIESTA_REACH_PULL(-1, 0, -1, 4) FIESTA_REACH_PULL(-1, 0, 1, 4) FIESTA_REACH_PULL(1, 0, -1, 4) FIESTA_REACH_PULL(1, 0, 1, 4)
+        FIESTA_REACH_PULL(0, -1, -1, 4) FIESTA_REACH_PULL(0, -1, 1, 4) FIESTA_REACH_PULL(0, 1, -1, 4) FIESTA_REACH_PULL(0, 1, 1, 4)
+        FIESTA_REACH_PULL(-1, -1, -1, 5) FIESTA_REACH_PULL(-1, -1, 1, 5) FIESTA_REACH_PULL(-1, 1, -1, 5) FIESTA_REACH_PULL(-1, 1, 1, 5)
+        FIESTA_REACH_PULL(1, -1, -1, 5) FIESTA_REACH_PULL(1, -1, 1, 5) FIESTA_REACH_PULL(1, 1, -1, 5) FIESTA_REACH_PULL(1, 1, 1, 5)
+      }
+#undef FIESTA_REACH_PULL
+      if (best < cur) s_c[p] = best, ch = true, chg |= 1u << z;
+    }
+    if (!__syncthreads_or(ch)) break;
+  }
+  const int64_t gi = ((int64_t)x * b.ey + y) * b.ez + tz * 32;
+  for (uint32_t m = chg; m; m &= m - 1) {
+    const int z = __ffs((int)m) - 1;
+    cost[gi + z] = s_c[base + z];
+  }
+  // a lowered cost in the layer that faces a neighbouring tile (a face, an edge, a corner) is news for that tile
+#pragma unroll
+  for (int d = 0; d < 27; ++d) {
+    const int dx = d / 9 - 1, dy = (d / 3) % 3 - 1, dz = d % 3 - 1;
+    if (d == 13 || (CONN == 6 && (dx != 0) + (dy != 0) + (dz != 0) != 1)) continue;
+    const bool layer = (dx == 0 || lx == (dx < 0 ? 0 : 15)) && (dy == 0 || ly == (dy < 0 ? 0 : 15));
+    const uint32_t zm = dz == 0 ? 0xFFFFFFFFu : (dz < 0 ? 1u : 0x80000000u);
+    if (layer && (chg & zm)) s_wake[d] = 1;
+  }
+  __syncthreads();
+  if (tid < 27 && s_wake[tid]) {
+    const int ux = tx + tid / 9 - 1, uy = ty + (tid / 3) % 3 - 1, uz = tz + tid % 3 - 1;
+    if (ux >= 0 && ux < b.ntx && uy >= 0 && uy < b.nty && uz >= 0 && uz < b.nzw)
+      activate_tile(item0 + (uint32_t)((ux * b.nty + uy) * b.nzw + uz), r.flag_next, r.list_next, &r.ctr[r.next]);
+  }
+  if (tid == 0) atomicAdd(&r.ctr[R_VISITS], 1ull);
+  __syncthreads();  // (the next tile overwrites s_c and s_wake)
+}
+
+template <int CONN>
+__global__ __launch_bounds__(256) void k_reach_relax(ReachBox b, const uint32_t *bits, int32_t *cost, ReachRound r) {
   const unsigned count = (unsigned)r.ctr[r.cur];  // (nothing appends to this round's own list)
-  if (blockIdx.x == 0 && tid == 0) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
     r.ctr[r.clear] = 0;
     if (count) atomicAdd(&r.ctr[R_ROUNDS], 1ull);
   }
-  for (unsigned it = blockIdx.x; it < count; it += gridDim.x) {
-    const int t = (int)r.list_cur[it];
-    const int tz = t % b.nzw, ty = (t / b.nzw) % b.nty, tx = t / (b.nzw * b.nty);
-    if (tid == 0) r.flag_cur[t] = 0;
-    if (tid < 27) s_wake[tid] = 0;
-    for (int i = tid; i < kReachLds; i += 256) {
-      const int hz = i % 34, hy = (i / 34) % 18, hx = i / kReachPitchY;
-      const int x = tx * 16 - 1 + hx, y = ty * 16 - 1 + hy, z = tz * 32 - 1 + hz;
-      int v = kReachBig;  // outside the box, not traversable, not reached: nothing to pull from
-      if ((unsigned)x < (unsigned)b.ex && (unsigned)y < (unsigned)b.ey && (unsigned)z < (unsigned)b.ez) {
-        const int c = cost[((int64_t)x * b.ey + y) * b.ez + z];
-        if (c >= 0 && c != INT32_MAX) v = c;
-      }
-      s_c[i] = v;
-    }
-    const int x = tx * 16 + lx, y = ty * 16 + ly;
-    const uint32_t own = (x < b.ex && y < b.ey) ? bits[(x * b.ey + y) * b.nzw + tz] : 0u;  // this lane's column: one word
-    const int base = (lx + 1) * kReachPitchY + (ly + 1) * kReachPitchZ + 1;
-    __syncthreads();
-    uint32_t chg = 0;  // voxels of the column whose cost this visit lowered
-    for (int sweep = 0;; ++sweep) {
-      bool ch = false;
-      for (uint32_t m = own; m;) {  // (a word without traversable voxels is skipped) upwards and downwards in turn
-        const int z = (sweep & 1) ? 31 - __clz((int)m) : __ffs((int)m) - 1;
-        m &= ~(1u << z);
-        const int p = base + z, cur = s_c[p];
-        int best = cur;
-#define FIESTA_REACH_PULL(DX, DY, DZ, W) best = min(best, s_c[p + (DX) * kReachPitchY + (DY) * kReachPitchZ + (DZ)] + (W));
-        FIESTA_REACH_PULL(0, 0, -1, 3) FIESTA_REACH_PULL(0, 0, 1, 3) FIESTA_REACH_PULL(-1, 0, 0, 3) FIESTA_REACH_PULL(1, 0, 0, 3)
-        FIESTA_REACH_PULL(0, -1, 0, 3) FIESTA_REACH_PULL(0, 1, 0, 3)
-        if (CONN == 26) {
-          FIESTA_REACH_PULL(-1, -1, 0, 4) FIESTA_REACH_PULL(-1, 1, 0, 4) FIESTA_REACH_PULL(1, -1, 0, 4) FIESTA_REACH_PULL(1, 1, 0, 4)
-          FIESTA_REACH_PULL(-1, 0, -1, 4) FIESTA_REACH_PULL(-1, 0, 1, 4) FIESTA_REACH_PULL(1, 0, -1, 4) FIESTA_REACH_PULL(1, 0, 1, 4)
-          FIESTA_REACH_PULL(0, -1, -1, 4) FIESTA_REACH_PULL(0, -1, 1, 4) FIESTA_REACH_PULL(0, 1, -1, 4) FIESTA_REACH_PULL(0, 1, 1, 4)
-          FIESTA_REACH_PULL(-1, -1, -1, 5) FIESTA_REACH_PULL(-1, -1, 1, 5) FIESTA_REACH_PULL(-1, 1, -1, 5) FIESTA_REACH_PULL(-1, 1, 1, 5)
-          FIESTA_REACH_PULL(1, -1, -1, 5) FIESTA_REACH_PULL(1, -1, 1, 5) FIESTA_REACH_PULL(1, 1, -1, 5) FIESTA_REACH_PULL(1, 1, 1, 5)
-        }
-#undef FIESTA_REACH_PULL
-        if (best < cur) s_c[p] = best, ch = true, chg |= 1u << z;
-      }
-      if (!__syncthreads_or(ch)) break;
-    }
-    const int64_t gi = ((int64_t)x * b.ey + y) * b.ez + tz * 32;
-    for (uint32_t m = chg; m; m &= m - 1) {
-      const int z = __ffs((int)m) - 1;
-      cost[gi + z] = s_c[base + z];
-    }
-    // a lowered cost in the layer that faces a neighbouring tile (a face, an edge, a corner) is news for that tile
-#pragma unroll
-    for (int d = 0; d < 27; ++d) {
-      const int dx = d / 9 - 1, dy = (d / 3) % 3 - 1, dz = d % 3 - 1;
-      if (d == 13 || (CONN == 6 && (dx != 0) + (dy != 0) + (dz != 0) != 1)) continue;
-      const bool layer = (dx == 0 || lx == (dx < 0 ? 0 : 15)) && (dy == 0 || ly == (dy < 0 ? 0 : 15));
-      const uint32_t zm = dz == 0 ? 0xFFFFFFFFu : (dz < 0 ? 1u : 0x80000000u);
-      if (layer && (chg & zm)) s_wake[d] = 1;
-    }
-    __syncthreads();
-    if (tid < 27 && s_wake[tid]) {
-      const int ux = tx + tid / 9 - 1, uy = ty + (tid / 3) % 3 - 1, uz = tz + tid % 3 - 1;
-      if (ux >= 0 && ux < b.ntx && uy >= 0 && uy < b.nty && uz >= 0 && uz < b.nzw)
-        activate_tile((uint32_t)((ux * b.nty + uy) * b.nzw + uz), r.flag_next, r.list_next, &r.ctr[r.next]);
-    }
-    if (tid == 0) atomicAdd(&r.ctr[R_VISITS], 1ull);
-    __syncthreads();  // (the next tile overwrites s_c and s_wake)
-  }
+  for (unsigned it = blockIdx.x; it < count; it += gridDim.x) reach_relax_tile<CONN>(b, bits, cost, r, (int)r.list_cur[it], 0u);
 }
 
 __global__ __launch_bounds__(256) void k_reach_targets(ReachBox b, int ox, int oy, int oz, const int32_t *targets, int64_t n, const int32_t *cost,

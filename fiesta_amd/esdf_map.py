@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachPathsResult, ReachResult, Stats, check
+from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, Stats, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -757,6 +757,53 @@ class ESDFMap:
                                                    C.c_void_p(targets_dev_ptr or None), int(n_targets), float(min_clearance),
                                                    int(connectivity), int(flags), C.byref(res), C.byref(info)))
         return self._reach_info(info)
+
+    @staticmethod
+    def _reach_matrix_info(info) -> dict:
+        d = {k: getattr(info, k) for k, _ in ReachMatrixInfo._fields_}
+        d["box_lo"], d["box_hi"] = list(info.box_lo), list(info.box_hi)
+        return d
+
+    def ReachMatrix(self, sources, targets=None, lo=None, hi=None, min_clearance=0.0, connectivity=26, flags=0, max_fields=0) -> dict:
+        """fiesta_hip_reach_matrix: the travel cost from every source ((n, 3) map voxels, each a flood of its own) to every column --
+        `targets` ((m, 3) map voxels), or the sources themselves (None: the square form) -- through the traversable voxels of the box
+        [lo, hi], with ReachField's box, clearance, flags and connectivity; the floods share one traversability bitmap and run side by
+        side, at most max_fields at a time (0: as many as 2^28 cost entries allow).  Returns the fields of fiesta_hip_reach_matrix_info
+        plus cost ((n, n_cols) int32: row s is ReachField([source s], targets=columns)["target_cost"], or all -1 for a source that is
+        not REACH_SITE_OK), source_status ((n,) int32) and source_reached ((n,) int64); fiesta_amd.reach_matrix_model is the definition"""
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        blo = None if lo is None else np.ascontiguousarray(lo, np.int32).reshape(3)
+        bhi = None if hi is None else np.ascontiguousarray(hi, np.int32).reshape(3)
+        s = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1, 3)
+        t = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32).reshape(-1, 3)
+        n, nt = len(s), 0 if t is None else len(t)
+        cost = np.empty((n, n if t is None else nt), np.int32)
+        status, reached = np.empty(n, np.int32), np.empty(n, np.int64)
+        info = ReachMatrixInfo()
+        res = ReachMatrixResult(cost.ctypes.data if cost.size else None, status.ctypes.data if n else None, reached.ctypes.data if n else None)
+        # (an empty `targets` is a matrix without columns, not the square form: the pointer stays non-null)
+        tp = None if t is None else _p(t if nt else np.zeros(3, np.int32))
+        check(self._lib.fiesta_hip_reach_matrix(self._h, _p(blo), _p(bhi), _p(s) if n else None, n, tp, nt, float(min_clearance), int(connectivity),
+                                                int(flags), int(max_fields), C.byref(res), C.byref(info)))
+        out = self._reach_matrix_info(info)
+        out.update(cost=cost, source_status=status, source_reached=reached)
+        return out
+
+    def ReachMatrixDevice(self, sources_dev_ptr: int, n_sources: int, targets_dev_ptr: int = 0, n_targets: int = 0, lo=None, hi=None,
+                          min_clearance=0.0, connectivity=26, flags=0, max_fields=0, cost_dev_ptr: int = 0, source_status_dev_ptr: int = 0,
+                          source_reached_dev_ptr: int = 0) -> dict:
+        """fiesta_hip_reach_matrix_dev: sources, targets (0 with n_targets = 0: the square form), cost (n_sources x n_cols int32),
+        source_status (int32) and source_reached (int64) resident on the device (0: not given / not written); returns the fields of
+        fiesta_hip_reach_matrix_info.  Synchronises with the map's stream, like ReachFieldDevice"""
+        blo = None if lo is None else np.ascontiguousarray(lo, np.int32).reshape(3)
+        bhi = None if hi is None else np.ascontiguousarray(hi, np.int32).reshape(3)
+        info = ReachMatrixInfo()
+        res = ReachMatrixResult(int(cost_dev_ptr) or None, int(source_status_dev_ptr) or None, int(source_reached_dev_ptr) or None)
+        check(self._lib.fiesta_hip_reach_matrix_dev(self._h, _p(blo), _p(bhi), C.c_void_p(sources_dev_ptr or None), int(n_sources),
+                                                    C.c_void_p(targets_dev_ptr or None), int(n_targets), float(min_clearance),
+                                                    int(connectivity), int(flags), int(max_fields), C.byref(res), C.byref(info)))
+        return self._reach_matrix_info(info)
 
     def ReachPaths(self, targets, cost=None, box=None, connectivity=26, shortcut=False, max_span=4096, want_pos=True) -> dict:
         """fiesta_hip_reach_paths: per target ((n, 3) map voxels) the path down a cost-to-go field from the seed it was reached from to

@@ -113,6 +113,45 @@ def reach_model(observed, occupied, seeds, dist=None, lo=None, hi=None, min_clea
     return out
 
 
+# ---- fiesta_hip_reach_matrix: pairwise travel costs, one flood per source ---------------------------------------------------------
+REACH_SITE_OK = 0              # FIESTA_HIP_REACH_SITE_*: the per-source status
+REACH_SITE_OUTSIDE = 1         # the source lies outside the clipped box
+REACH_SITE_BLOCKED = 2         # inside, not traversable
+
+
+def reach_matrix_model(observed, occupied, sources, targets=None, dist=None, lo=None, hi=None, min_clearance=0.0, connectivity=26, flags=0,
+                       origin_vox=(0, 0, 0)):
+    """The definition of fiesta_hip_reach_matrix (include/fiesta_hip.h), plain and slow: one reach_model run per usable source.  The
+    arrays, the box and the traversability arguments are reach_model's; `sources` (n, 3) map voxels, `targets` (m, 3) the columns
+    (None: the sources themselves, the square form).  Row s of a source with status OK is reach_model(seeds=[source s],
+    targets=columns)["target_cost"]; the row of a source outside the clipped box (OUTSIDE) or not traversable (BLOCKED) is all -1.
+    Returns a dict: cost ((n, n_cols) int32), source_status ((n,) int32), source_reached ((n,) int64: n_reached of the source's
+    flood, 0 unless OK), box_lo, box_hi, n_traversable and n_sources_used."""
+    src = np.asarray(sources, dtype=np.int64).reshape(-1, 3)
+    cols = src if targets is None else np.asarray(targets, dtype=np.int64).reshape(-1, 3)
+    kw = dict(dist=dist, lo=lo, hi=hi, min_clearance=min_clearance, connectivity=connectivity, flags=flags, origin_vox=origin_vox)
+    base = reach_model(observed, occupied, np.zeros((0, 3), np.int64), targets=src, **kw)   # no seed: the box and traversable(source)
+    n = len(src)
+    out = {"cost": np.full((n, len(cols)), REACH_BLOCKED, np.int32), "source_status": np.full(n, REACH_SITE_OUTSIDE, np.int32),
+           "source_reached": np.zeros(n, np.int64), "box_lo": base["box_lo"], "box_hi": base["box_hi"],
+           "n_traversable": base["n_traversable"], "n_sources_used": 0}
+    if base["cost"].size == 0:
+        return out
+    blo, bhi = np.array(base["box_lo"], np.int64), np.array(base["box_hi"], np.int64)
+    for s in range(n):
+        if np.any(src[s] < blo) or np.any(src[s] > bhi):
+            continue
+        if base["target_cost"][s] == REACH_BLOCKED:
+            out["source_status"][s] = REACH_SITE_BLOCKED
+            continue
+        r = reach_model(observed, occupied, src[s:s + 1], targets=cols, **kw)
+        out["source_status"][s] = REACH_SITE_OK
+        out["cost"][s] = r["target_cost"]
+        out["source_reached"][s] = r["n_reached"]
+        out["n_sources_used"] += 1
+    return out
+
+
 # ---- fiesta_hip_reach_paths: paths out of a cost field -------------------------------------------------------------------------
 REACH_PATHS_SHORTCUT = 1       # FIESTA_HIP_REACH_PATHS_SHORTCUT
 REACH_PATH_OK = 0              # FIESTA_HIP_REACH_PATH_*: the per-target status

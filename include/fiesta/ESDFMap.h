@@ -323,6 +323,33 @@ class ESDFMap {
                               tv.empty() ? nullptr : tv.data(), (int64_t)targets.size(), min_clearance, connectivity, flags, &r, &info));
     return info;
   }
+  // Reach matrix (fiesta_hip_reach_matrix, include/fiesta_hip.h): the travel cost from every source -- each a flood of its own from
+  // that one voxel, ReachField's box, clearance, flags and connectivity -- to every target; an empty `targets` selects the square
+  // form (the columns are the sources), the cost matrix a tour solver takes.  *cost (nullable) receives sources x columns values,
+  // row-major: ReachField's target cost, or -1 along the whole row of a source that is outside the box or not traversable
+  // (*source_status, nullable: FIESTA_HIP_REACH_SITE_*), so the square form is symmetric.  The floods share one traversability
+  // bitmap and run side by side, at most max_fields at a time (0: as many as fit); the field ReachPaths retains is left alone.
+  fiesta_hip_reach_matrix_info ReachMatrix(const Eigen::Vector3i *lo, const Eigen::Vector3i *hi, const std::vector<Eigen::Vector3i> &sources,
+                                           const std::vector<Eigen::Vector3i> &targets, double min_clearance, int32_t connectivity, int32_t flags,
+                                           std::vector<int32_t> *cost, std::vector<int32_t> *source_status = nullptr, int32_t max_fields = 0) {
+    Flush();
+    if ((lo == nullptr) != (hi == nullptr)) throw std::invalid_argument("ReachMatrix: lo and hi must both be given or both be null");
+    int32_t a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
+    for (int c = 0; c < 3 && lo; ++c) a[c] = (*lo)(c), b[c] = (*hi)(c);
+    std::vector<int32_t> sv, tv;
+    for (const auto &v : sources) sv.insert(sv.end(), {v(0), v(1), v(2)});
+    for (const auto &v : targets) tv.insert(tv.end(), {v(0), v(1), v(2)});
+    const size_t n = sources.size(), n_cols = targets.empty() ? n : targets.size();
+    if (n && n_cols > ((size_t)1 << 28) / n) throw std::invalid_argument("ReachMatrix: the matrix holds more than 2^28 entries");
+    if (cost) cost->assign(n * n_cols, -1);
+    if (source_status) source_status->assign(n, FIESTA_HIP_REACH_SITE_OUTSIDE);
+    const fiesta_hip_reach_matrix_result r{cost && !cost->empty() ? cost->data() : nullptr,
+                                           source_status && n ? source_status->data() : nullptr, nullptr};
+    fiesta_hip_reach_matrix_info info{};
+    ck(fiesta_hip_reach_matrix(h_, lo ? a : nullptr, lo ? b : nullptr, sv.empty() ? nullptr : sv.data(), (int64_t)n,
+                               tv.empty() ? nullptr : tv.data(), (int64_t)targets.size(), min_clearance, connectivity, flags, max_fields, &r, &info));
+    return info;
+  }
   // Reach paths (fiesta_hip_reach_paths, include/fiesta_hip.h): per target voxel the path down a cost-to-go field, from the seed it was
   // reached from to the target.  The field is the one the map retained from the last ReachField call (cost null), or *cost with its
   // inclusive voxel box [box_lo, box_hi] (ReachField's info.box_lo / box_hi) and the connectivity it was flooded with.  shortcut: the

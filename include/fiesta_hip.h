@@ -131,7 +131,8 @@ typedef struct fiesta_hip_stats {
 const char *fiesta_hip_last_error(void);
 /* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev].
  * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev], fiesta_hip_ray_query[_dev], fiesta_hip_reach_field[_dev] and
- * fiesta_hip_reach_paths[_dev] came later without a new number: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_reach_paths[_dev] came later without a new number, and so did fiesta_hip_cluster_voxels[_dev],
+ * fiesta_hip_view_coverage[_dev] and fiesta_hip_reach_matrix[_dev]: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -573,6 +574,72 @@ int fiesta_hip_reach_field(fiesta_hip_map *m, const int32_t lo[3], const int32_t
 int fiesta_hip_reach_field_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds_dev, int64_t n_seeds,
                                const int32_t *targets_dev, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
                                const fiesta_hip_reach_result *result, fiesta_hip_reach_info *info);
+
+/* ---- reach matrix: pairwise travel costs between sites, the floods batched on the device ----
+ * What a tour planner needs after the chain frontier voxels -> clusters -> views -> reachability: the travel cost between every
+ * pair of sites (the robot and one viewpoint per frontier cluster), the cost matrix a tour solver takes.  Row s is the flood of
+ * fiesta_hip_reach_field from source s alone, read at the columns; the floods of one call share ONE traversability bitmap and run
+ * side by side, a launch per round for all of them.  Read-only; no reference counterpart.  fiesta_hip_version() is still 101:
+ * detect these two calls by symbol lookup.
+ * Shared with fiesta_hip_reach_field, word for word: the box (lo / hi HOST pointers in both variants, clipped to a dense map's
+ *   array, mandatory on a hash-block map and clamped there, at most 2^28 voxels after clipping, an empty intersection is no error),
+ *   traversable(v) with min_clearance and FIESTA_HIP_REACH_THROUGH_UNKNOWN, the moves with their weights 3 / 4 / 5, connectivity
+ *   6 or 26.
+ * Sources: n_sources x 3 int32 map voxels; each source is a flood of its own from that single voxel.  source_status:
+ *   FIESTA_HIP_REACH_SITE_OK; _OUTSIDE: the source lies outside the clipped box; _BLOCKED: inside, not traversable.
+ * Columns: targets, n_targets x 3 int32 map voxels; with targets == NULL and n_targets == 0 the columns are the sources themselves
+ *   (the square form, n_cols = n_sources).
+ * cost[s * n_cols + j]: if source s is OK, bit for bit target_cost[j] of fiesta_hip_reach_field with seeds = {source s}: the minimum
+ *   total weight of a move sequence from the source to column voxel j, INT32_MAX if that voxel is traversable and not reached, -1
+ *   if it lies outside the clipped box or is not traversable.  If source s is OUTSIDE or BLOCKED its whole row is -1 and
+ *   source_reached[s] is 0 (reach_field with an unusable seed reports INT32_MAX for traversable targets instead): -1 always means
+ *   "this site is no place to be", and since moves are symmetric and traversability belongs to the voxel, the square form is
+ *   SYMMETRIC.  Every number is an integer and the fixed point is unique: every output has the same bits for any launch shape,
+ *   batch width and scheduling, and the bits of fiesta_amd.reach_matrix_model.
+ * max_fields: an upper bound on the floods run side by side; 0: as many as the budget allows.  The budget: B * (voxels of the
+ *   clipped box) <= 2^28 cost entries (1 GiB of scratch at most), B >= 1 always.  Sources are processed in batches of B consecutive
+ *   entries; a source listed twice may be flooded twice.  The outputs do not depend on max_fields; info->fields and info->batches
+ *   say what happened.
+ * info (a HOST struct in both variants, nullable): the clipped box, the traversable voxels, the sources with status OK (a voxel
+ *   listed twice counts twice), the widest batch, the batches, and over all batches the rounds (launches that found work) and the
+ *   tile visits ((tile, flood) pairs relaxed).  n_sources = 0 is no error: nothing is written, info holds the box and
+ *   n_traversable.  An empty box: every written cost is -1, every status OUTSIDE, info all zero.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): those of fiesta_hip_reach_field (NaN
+ *   clearance, exactly one of lo / hi NULL, both NULL on a hash-block map, a clipped box above 2^28 voxels, connectivity other
+ *   than 6 or 26, unknown flag bits, a negative count, result NULL), max_fields < 0, sources NULL with n_sources > 0, targets NULL
+ *   with n_targets > 0, n_sources * n_cols > 2^28.  The scratch memory (the cost planes of a batch, item flags and lists, the
+ *   bitmap) belongs to the map: grown on demand, freed by fiesta_hip_destroy; a failed allocation is FIESTA_HIP_ERR_NOMEM and leaves
+ *   the map usable.  FIESTA_HIP_ERR_STATE: a batch ran more rounds than there are traversable voxels + 1 (a defect, never expected).
+ * The field that fiesta_hip_reach_paths RETAINS is left alone: this call neither reads nor writes it, so a reach_field /
+ *   reach_paths pair may be interleaved with it.
+ * fiesta_hip_reach_matrix      host arrays; stages, runs, synchronises, copies back.
+ * fiesta_hip_reach_matrix_dev  sources / targets and the arrays the result struct names are device pointers; writes exactly
+ *                              n_sources * n_cols costs and nothing beyond them.  Synchronises with the map's stream like
+ *                              fiesta_hip_reach_field_dev: the number of rounds depends on the data (one small counter read after
+ *                              every eight rounds of a batch). */
+#define FIESTA_HIP_REACH_SITE_OK 0
+#define FIESTA_HIP_REACH_SITE_OUTSIDE 1 /* source outside the clipped box */
+#define FIESTA_HIP_REACH_SITE_BLOCKED 2 /* source inside, not traversable */
+typedef struct fiesta_hip_reach_matrix_result { /* every pointer nullable */
+  int32_t *cost;                                /* n_sources x n_cols, row-major */
+  int32_t *source_status;                       /* per source, FIESTA_HIP_REACH_SITE_* */
+  int64_t *source_reached; /* per source: traversable voxels with a finite cost in its flood; 0 unless OK */
+} fiesta_hip_reach_matrix_result;
+typedef struct fiesta_hip_reach_matrix_info {
+  int32_t box_lo[3], box_hi[3]; /* the clipped box, map voxel coordinates, inclusive */
+  int64_t n_traversable;
+  int64_t n_sources_used; /* sources with status OK; a voxel listed twice counts twice */
+  int64_t fields;         /* floods run side by side (the widest batch) */
+  int64_t batches;
+  int64_t rounds;      /* launches that found work, over all batches */
+  int64_t tile_visits; /* (tile, flood) pairs relaxed, over all rounds */
+} fiesta_hip_reach_matrix_info;
+int fiesta_hip_reach_matrix(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *sources, int64_t n_sources,
+                            const int32_t *targets, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
+                            int32_t max_fields, const fiesta_hip_reach_matrix_result *result, fiesta_hip_reach_matrix_info *info);
+int fiesta_hip_reach_matrix_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *sources_dev, int64_t n_sources,
+                                const int32_t *targets_dev, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
+                                int32_t max_fields, const fiesta_hip_reach_matrix_result *result, fiesta_hip_reach_matrix_info *info);
 
 /* ---- reach paths: the paths themselves, extracted from the cost-to-go field on the device ----
  * The last step of the chain frontier voxels -> reachability -> paths -> path cost: fiesta_hip_reach_field says which targets the
