@@ -1142,12 +1142,10 @@ void DenseMap::observe_vox(const int32_t *vox, const int32_t *occ, int64_t n, in
   const Geom &g = g_;
   const int32_t *dv = vox, *docc_in = occ;
   if (!dev) {
-    stage_a_.ensure(n * 3 * sizeof(int32_t), stream_);
-    stage_b_.ensure(n * sizeof(int32_t), stream_);
-    FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, vox, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    FIESTA_HIP_CHECK(hipMemcpyAsync(stage_b_.p, occ, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    dv = (const int32_t *)stage_a_.p;
-    docc_in = (const int32_t *)stage_b_.p;
+    Staging in{planner_.in, stream_};
+    const auto v = in.add(vox, 3 * n), o = in.add(occ, n);
+    in.alloc(), in.up(v, 3 * n), in.up(o, n);
+    dv = in.dev(v), docc_in = in.dev(o);
   }
   ensure_touched_capacity(n);
   hipLaunchKernelGGL(k_observe_vox, dim3(grid_for(n, 256)), dim3(256), 0, stream_, g, dv, docc_in, n, cnt_, touched_.p,
@@ -1158,7 +1156,7 @@ void DenseMap::observe_vox(const int32_t *vox, const int32_t *occ, int64_t n, in
     for (int64_t i = 0; i < n; ++i)
       ret[i] = (vox[3 * i] - g.gx0) * (gny * gnz) + (vox[3 * i + 1] - g.gy0) * gnz + (vox[3 * i + 2] - g.gz0);
   }
-  if (!dev) FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));  // staging buffers are reused
+  if (!dev) FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));  // the staging buffer is reused
 }
 
 void DenseMap::observe_box(const int32_t *lo, const int32_t *hi, int occ) {
@@ -1176,13 +1174,13 @@ void DenseMap::observe_pos(const double *pos, const int32_t *occ, int64_t n, int
   use_device();
   if (n <= 0) return;
   const Geom &g = g_;
-  stage_a_.ensure(n * 3 * sizeof(double), stream_);
-  stage_b_.ensure(n * sizeof(int32_t), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, pos, n * 3 * sizeof(double), hipMemcpyHostToDevice, stream_));
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_b_.p, occ, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  Staging in{planner_.in, stream_};
+  const auto dp = in.add(pos, 3 * n);
+  const auto docc = in.add(occ, n);
+  in.alloc(), in.up(dp, 3 * n), in.up(docc, n);
   ensure_touched_capacity(n);
-  hipLaunchKernelGGL(k_observe_pos, dim3(grid_for(n)), dim3(256), 0, stream_, g, (const double *)stage_a_.p,
-                     (const int32_t *)stage_b_.p, n, cnt_, touched_.p, counters_);
+  hipLaunchKernelGGL(k_observe_pos, dim3(grid_for(n)), dim3(256), 0, stream_, g, in.dev(dp), in.dev(docc), n, cnt_, touched_.p,
+                     counters_);
   FIESTA_HIP_CHECK(hipGetLastError());
   if (ret) {  // SetOccupancy(Vector3d,int) return value (:401-415)
     for (int64_t i = 0; i < n; ++i) {
@@ -2406,12 +2404,12 @@ void DenseMap::get_distance_vox(const int32_t *vox, int64_t n, double *out) {
     return;
   }
   use_device();
-  stage_a_.ensure(n * 3 * sizeof(int32_t), stream_);
-  stage_c_.ensure(n * sizeof(double), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, vox, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_query_dist_vox, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const vox_t *)coc_,
-                     (const int32_t *)stage_a_.p, n, (double *)stage_c_.p);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(out, stage_c_.p, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  Staging in{planner_.in, stream_}, res{planner_.out, stream_};
+  const auto q = in.add(vox, 3 * n);
+  const auto d = res.add(out, n);
+  in.alloc(), in.up(q, 3 * n), res.alloc();
+  hipLaunchKernelGGL(k_query_dist_vox, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, in.dev(q), n, res.dev(d));
+  res.back(d, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 void DenseMap::get_distance_pos(const double *pos, int64_t n, double *out) {
@@ -2422,12 +2420,12 @@ void DenseMap::get_distance_pos(const double *pos, int64_t n, double *out) {
     return;
   }
   use_device();
-  stage_a_.ensure(n * 3 * sizeof(double), stream_);
-  stage_c_.ensure(n * sizeof(double), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, pos, n * 3 * sizeof(double), hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_query_dist_pos, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const vox_t *)coc_,
-                     (const double *)stage_a_.p, n, (double *)stage_c_.p);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(out, stage_c_.p, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  Staging in{planner_.in, stream_}, res{planner_.out, stream_};
+  const auto q = in.add(pos, 3 * n);
+  const auto d = res.add(out, n);
+  in.alloc(), in.up(q, 3 * n), res.alloc();
+  hipLaunchKernelGGL(k_query_dist_pos, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, in.dev(q), n, res.dev(d));
+  res.back(d, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 void DenseMap::get_dist_grad(const double *pos, int64_t n, double *dist, double *grad, bool dev) {
@@ -2444,37 +2442,42 @@ void DenseMap::get_dist_grad(const double *pos, int64_t n, double *dist, double 
     FIESTA_HIP_CHECK(hipGetLastError());
     return;
   }
-  stage_a_.ensure(n * 3 * sizeof(double), stream_);
-  stage_b_.ensure(n * 3 * sizeof(double), stream_);
-  stage_c_.ensure(n * sizeof(double), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, pos, n * 3 * sizeof(double), hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_query_trilinear, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const vox_t *)coc_,
-                     (const double *)stage_a_.p, n, (double *)stage_c_.p, (double *)stage_b_.p);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(dist, stage_c_.p, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
-  if (grad) FIESTA_HIP_CHECK(hipMemcpyAsync(grad, stage_b_.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  Staging in{planner_.in, stream_}, res{planner_.out, stream_};
+  const auto q = in.add(pos, 3 * n);
+  const auto d = res.add(dist, n), gr = res.add(grad, 3 * n);  // (a null grad: the kernel gets null, as from the device variant)
+  in.alloc(), in.up(q, 3 * n), res.alloc();
+  hipLaunchKernelGGL(k_query_trilinear, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, in.dev(q), n, res.dev(d),
+                     res.dev(gr));
+  res.back(d, n), res.back(gr, 3 * n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+// what the planner kernels read of this map (each type next to its kernels), and the path calls' evaluator on the host brick cache
+auto DenseMap::ray_source() const { return DenseRaySource(g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_); }
+auto DenseMap::reach_source() const { return DenseReachSource{g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, (const vox_t *)coc_}; }
+auto DenseMap::path_eval() const { return DensePathEval{g_, (const vox_t *)coc_}; }
+auto DenseMap::frontier_dist() const { return DenseFrontierDist{g_, (const vox_t *)coc_}; }
+auto DenseMap::host_path_eval() {
+  return [this, wd = HostWords{this}](const double *p, double *grad) mutable { return query_trilinear(g_, wd, p, grad); };
 }
 void DenseMap::path_clearance(const PathClearanceArgs &a) {
   if (a.n_paths <= 0) return;
   if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
-    HostWords wd{this};
-    auto ev = [&](const double *p, double *grad) { return query_trilinear(g_, wd, p, grad); };
+    auto ev = host_path_eval();
     path_host(ev, a.w, a.off, a.n_paths, a.step, a.margin, *a.res);
     return;
   }
   use_device();
-  path_clearance_run(stream_, planner_, DensePathEval{g_, (const vox_t *)coc_}, a);
+  path_clearance_run(stream_, planner_, path_eval(), a);
 }
 void DenseMap::path_cost(const PathCostArgs &a) {
   if (a.n_paths <= 0) return;
   if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
-    HostWords wd{this};
-    auto ev = [&](const double *p, double *grad) { return query_trilinear(g_, wd, p, grad); };
+    auto ev = host_path_eval();
     path_cost_host(ev, a.w, a.n_wp, a.off, a.n_paths, a.step, a.margin, *a.res);
     return;
   }
   use_device();
-  path_cost_run(stream_, planner_, DensePathEval{g_, (const vox_t *)coc_}, a);
+  path_cost_run(stream_, planner_, path_eval(), a);
 }
 void DenseMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n <= 0) return;
@@ -2486,12 +2489,12 @@ void DenseMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
     return;
   }
   use_device();
-  stage_a_.ensure(n * 3 * sizeof(int32_t), stream_);
-  stage_c_.ensure(n * sizeof(int32_t), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, vox, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_query_occ_vox, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const uint32_t *)occbits_,
-                     (const int32_t *)stage_a_.p, n, (int32_t *)stage_c_.p);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(out, stage_c_.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  Staging in{planner_.in, stream_}, res{planner_.out, stream_};
+  const auto q = in.add(vox, 3 * n);
+  const auto o = res.add(out, n);
+  in.alloc(), in.up(q, 3 * n), res.alloc();
+  hipLaunchKernelGGL(k_query_occ_vox, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const uint32_t *)occbits_, in.dev(q), n, res.dev(o));
+  res.back(o, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 void DenseMap::get_occupancy_pos(const double *pos, int64_t n, int32_t *out) {
@@ -2510,40 +2513,28 @@ void DenseMap::get_occupancy_pos(const double *pos, int64_t n, int32_t *out) {
     return;
   }
   use_device();
-  stage_a_.ensure(n * 3 * sizeof(double), stream_);
-  stage_c_.ensure(n * sizeof(int32_t), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, pos, n * 3 * sizeof(double), hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_query_occ_pos, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const uint32_t *)occbits_,
-                     (const double *)stage_a_.p, n, (int32_t *)stage_c_.p);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(out, stage_c_.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  Staging in{planner_.in, stream_}, res{planner_.out, stream_};
+  const auto q = in.add(pos, 3 * n);
+  const auto o = res.add(out, n);
+  in.alloc(), in.up(q, 3 * n), res.alloc();
+  hipLaunchKernelGGL(k_query_occ_pos, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const uint32_t *)occbits_, in.dev(q), n, res.dev(o));
+  res.back(o, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
 void DenseMap::download_field(int32_t *d2, int32_t *coc, uint8_t *occ, double *logodds) {
   use_device();
   const int64_t n = g_.n;
-  int32_t *dd2 = nullptr, *dc = nullptr;
-  uint8_t *docc = nullptr;
-  if (d2) {
-    stage_a_.ensure(n * sizeof(int32_t), stream_);
-    dd2 = (int32_t *)stage_a_.p;
-  }
-  if (coc) {
-    stage_b_.ensure(n * 3 * sizeof(int32_t), stream_);
-    dc = (int32_t *)stage_b_.p;
-  }
-  if (occ) {
-    stage_c_.ensure(n, stream_);
-    docc = (uint8_t *)stage_c_.p;
-  }
   if (d2 || coc || occ) {
+    Staging res{planner_.out, stream_};  // (whole-map arrays: one that is not requested takes no room either)
+    const auto dd2 = res.add(d2, d2 ? n : 0), dc = res.add(coc, coc ? 3 * n : 0);
+    const auto docc = res.add(occ, occ ? n : 0);
+    res.alloc();
     hipLaunchKernelGGL(k_export, dim3(grid_for(n, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_,
-                       (const uint32_t *)occbits_, dd2, dc, docc);
+                       (const uint32_t *)occbits_, res.dev(dd2), res.dev(dc), res.dev(docc));
     FIESTA_HIP_CHECK(hipGetLastError());
+    res.back(dd2, n), res.back(dc, 3 * n), res.back(docc, n);
   }
-  if (d2) FIESTA_HIP_CHECK(hipMemcpyAsync(d2, dd2, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  if (coc) FIESTA_HIP_CHECK(hipMemcpyAsync(coc, dc, n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  if (occ) FIESTA_HIP_CHECK(hipMemcpyAsync(occ, docc, n, hipMemcpyDeviceToHost, stream_));
   if (logodds) FIESTA_HIP_CHECK(hipMemcpyAsync(logodds, logodds_, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
@@ -2563,16 +2554,15 @@ int64_t DenseMap::occupied_voxels(int32_t *vox, int64_t cap) {
   use_device();
   zero_counter(C_SCRATCH);
   const int64_t nwords = nbitwords_;
-  int32_t *dout = nullptr;
-  if (vox && cap > 0) {
-    stage_a_.ensure((size_t)cap * 3 * sizeof(int32_t), stream_);
-    dout = (int32_t *)stage_a_.p;
-  }
+  if (!vox) cap = 0;
+  Staging res{planner_.out, stream_};
+  const auto list = res.add(vox, 3 * cap);
+  res.alloc();
   hipLaunchKernelGGL(k_occupied_list, dim3(grid_for(nwords, 256, 8192)), dim3(256), 0, stream_, g_, (const uint32_t *)occbits_,
-                     dout, (unsigned long long)(dout ? cap : 0), &counters_[C_SCRATCH]);
+                     res.dev(list), (unsigned long long)cap, &counters_[C_SCRATCH]);
   FIESTA_HIP_CHECK(hipGetLastError());
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
-  if (dout && n) FIESTA_HIP_CHECK(hipMemcpyAsync(vox, dout, (size_t)std::min(n, cap) * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  res.back(list, 3 * std::min(n, cap));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }
@@ -2606,26 +2596,24 @@ int64_t DenseMap::frontier_voxels(const FrontierArgs &a) {
   int64_t blo[3], bhi[3];
   const int64_t nvox = clip_box(a.lo, a.hi, blo, bhi) ? (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * (bhi[2] - blo[2] + 1) : 0;
   const int64_t cap = std::min(a.capacity, nvox);
-  int32_t *dvox = a.dev ? a.vox : nullptr;
-  uint8_t *dmask = a.dev ? a.mask : nullptr;
-  if (!a.dev && cap > 0) {
-    if (a.vox) stage_a_.ensure((size_t)cap * 3 * sizeof(int32_t), stream_), dvox = (int32_t *)stage_a_.p;
-    if (a.mask) stage_b_.ensure((size_t)cap, stream_), dmask = (uint8_t *)stage_b_.p;
-  }
+  Staging res{planner_.out, stream_};  // (the host variant's)
+  const auto vox = res.add(a.vox, 3 * cap);
+  const auto mask = res.add(a.mask, cap);
+  if (!a.dev) res.alloc();
+  int32_t *dvox = a.dev ? a.vox : res.dev(vox);
+  uint8_t *dmask = a.dev ? a.mask : res.dev(mask);
   if (nvox > 0) {
     sync_obsbits();
     const FrontierBox b{(int)blo[0], (int)blo[1], (int)blo[2], (int)bhi[0], (int)bhi[1], (int)bhi[2]};
     const int64_t nwords = (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * ((bhi[2] >> 5) - (blo[2] >> 5) + 1);
     hipLaunchKernelGGL(k_frontier_dense<DenseFrontierDist>, dim3(grid_for(nwords, 256, 8192)), dim3(256), 0, stream_, g_,
-                       (const uint32_t *)obsbits_, (const uint32_t *)occbits_, b, DenseFrontierDist{g_, (const vox_t *)coc_}, a.min_clearance,
+                       (const uint32_t *)obsbits_, (const uint32_t *)occbits_, b, frontier_dist(), a.min_clearance,
                        FrontierOut{dvox, dmask, (unsigned long long)cap, count});
     FIESTA_HIP_CHECK(hipGetLastError());
   }
   if (a.dev) return 0;
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
-  const size_t k = (size_t)std::min(n, cap);
-  if (dvox && k) FIESTA_HIP_CHECK(hipMemcpyAsync(a.vox, dvox, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(a.mask, dmask, k, hipMemcpyDeviceToHost, stream_));
+  res.back(vox, 3 * std::min(n, cap)), res.back(mask, std::min(n, cap));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }
@@ -2644,14 +2632,14 @@ void DenseMap::reach_field(const ReachArgs &a) {
   const int g0[3] = {g_.gx0, g_.gy0, g_.gz0};
   int64_t blo[3], bhi[3];
   reach_box(a.lo, a.hi, blo, bhi);
-  reach_run(stream_, planner_, DenseReachSource{g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, (const vox_t *)coc_}, blo, bhi, g0, a);
+  reach_run(stream_, planner_, reach_source(), blo, bhi, g0, a);
 }
 // fiesta_hip_reach_matrix[_dev] (reach_matrix_kernels.hpp): reach_field's box and source
 void DenseMap::reach_matrix(const ReachMatrixArgs &a) {
   const int g0[3] = {g_.gx0, g_.gy0, g_.gz0};
   int64_t blo[3], bhi[3];
   reach_box(a.lo, a.hi, blo, bhi);
-  reach_matrix_run(stream_, planner_, DenseReachSource{g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, (const vox_t *)coc_}, blo, bhi, g0, a);
+  reach_matrix_run(stream_, planner_, reach_source(), blo, bhi, g0, a);
 }
 
 // fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin
@@ -2663,8 +2651,7 @@ void DenseMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxe
 void DenseMap::view_coverage(const ViewArgs &a) {
   use_device();
   sync_obsbits();
-  const ViewSource<DenseRaySource, DenseFrontierDist> vs{DenseRaySource(g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_),
-                                                         DenseFrontierDist{g_, (const vox_t *)coc_}, {g_.gx0, g_.gy0, g_.gz0}};
+  const ViewSource<DenseRaySource, DenseFrontierDist> vs{ray_source(), frontier_dist(), {g_.gx0, g_.gy0, g_.gz0}};
   view_coverage_run(stream_, planner_, vs, a);
 }
 
@@ -2673,22 +2660,21 @@ void DenseMap::ray_query(const RayArgs &a) {
   if (a.n <= 0) return;
   use_device();
   sync_obsbits();
-  ray_query_run(stream_, planner_, DenseRaySource(g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_), a);
+  ray_query_run(stream_, planner_, ray_source(), a);
 }
 
 int64_t DenseMap::point_cloud(int vis_lower_bound, int vis_upper_bound, float *xyz, int64_t cap) {
   use_device();
   zero_counter(C_SCRATCH);
-  float *dout = nullptr;
-  if (xyz && cap > 0) {
-    stage_a_.ensure((size_t)cap * 3 * sizeof(float), stream_);
-    dout = (float *)stage_a_.p;
-  }
+  if (!xyz) cap = 0;
+  Staging res{planner_.out, stream_};
+  const auto pts = res.add(xyz, 3 * cap);
+  res.alloc();
   hipLaunchKernelGGL(k_point_cloud, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const uint32_t *)occbits_,
-                     vis_lower_bound, vis_upper_bound, dout, (unsigned long long)(dout ? cap : 0), &counters_[C_SCRATCH]);
+                     vis_lower_bound, vis_upper_bound, res.dev(pts), (unsigned long long)cap, &counters_[C_SCRATCH]);
   FIESTA_HIP_CHECK(hipGetLastError());
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
-  if (dout && n) FIESTA_HIP_CHECK(hipMemcpyAsync(xyz, dout, (size_t)std::min(n, cap) * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  res.back(pts, 3 * std::min(n, cap));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }
@@ -2698,23 +2684,17 @@ int64_t DenseMap::slice_marker(int slice, double max_dist, double *xyz, float *r
   const int z = slice - g_.gz0;
   if (z < 0 || z >= g_.nz) throw Error(FIESTA_HIP_ERR_INVALID, "slice outside the grid");
   zero_counter(C_SCRATCH);
-  double *dx = nullptr;
-  float *dc = nullptr;
-  if (xyz && rgba && cap > 0) {
-    stage_a_.ensure((size_t)cap * 3 * sizeof(double), stream_);
-    stage_b_.ensure((size_t)cap * 4 * sizeof(float), stream_);
-    dx = (double *)stage_a_.p, dc = (float *)stage_b_.p;
-  }
+  if (!xyz || !rgba) cap = 0;  // (both or nothing)
+  Staging res{planner_.out, stream_};
+  const auto dx = res.add(xyz, 3 * cap);
+  const auto dc = res.add(rgba, 4 * cap);
+  res.alloc();
   const int64_t cells = (int64_t)g_.nx * g_.ny;
-  hipLaunchKernelGGL(k_slice_marker, dim3(grid_for(cells, 256, 4096)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, z, max_dist, dx,
-                     dc, (unsigned long long)(dx ? cap : 0), &counters_[C_SCRATCH]);
+  hipLaunchKernelGGL(k_slice_marker, dim3(grid_for(cells, 256, 4096)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, z, max_dist,
+                     res.dev(dx), res.dev(dc), (unsigned long long)cap, &counters_[C_SCRATCH]);
   FIESTA_HIP_CHECK(hipGetLastError());
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
-  if (dx && n) {
-    const size_t k = (size_t)std::min(n, cap);
-    FIESTA_HIP_CHECK(hipMemcpyAsync(xyz, dx, k * 3 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    FIESTA_HIP_CHECK(hipMemcpyAsync(rgba, dc, k * 4 * sizeof(float), hipMemcpyDeviceToHost, stream_));
-  }
+  res.back(dx, 3 * std::min(n, cap)), res.back(dc, 4 * std::min(n, cap));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }
@@ -2724,10 +2704,12 @@ void DenseMap::slice_distances(int z_vox, double *out) {
   const int z = z_vox - g_.gz0;
   if (z < 0 || z >= g_.nz) throw Error(FIESTA_HIP_ERR_INVALID, "slice outside the grid");
   const int64_t n = (int64_t)g_.nx * g_.ny;
-  stage_c_.ensure((size_t)n * sizeof(double), stream_);
-  hipLaunchKernelGGL(k_slice, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, z, (double *)stage_c_.p);
+  Staging res{planner_.out, stream_};
+  const auto d = res.add(out, n);
+  res.alloc();
+  hipLaunchKernelGGL(k_slice, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, z, res.dev(d));
   FIESTA_HIP_CHECK(hipGetLastError());
-  FIESTA_HIP_CHECK(hipMemcpyAsync(out, stage_c_.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  res.back(d, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 

@@ -89,8 +89,8 @@ struct ViewScratch {
   DevBuf<unsigned char> call;  // one ViewCall
 };
 
-// what the planner calls (path clearance ... view coverage) keep between calls, one per map: the staged inputs of a host variant,
-// the path calls' plan / piece records, the staged outputs, and the four calls' own scratch
+// what a map keeps between calls for them, one per map: the staged inputs of a host variant (every host-pointer call of the ABI
+// stages here), the path calls' plan / piece records, the staged outputs, and the four planner calls' own scratch
 struct PlannerScratch {
   DevBuf<unsigned char> in, tmp, out;
   ReachScratch reach;
@@ -99,8 +99,9 @@ struct PlannerScratch {
   ViewScratch view;
 };
 
-// A host variant's staged sections in one of PlannerScratch's buffers: add() every section (8-byte aligned, in order), alloc(),
-// then dev() / up() / back().  A section whose host pointer is null has no device pointer and is never copied.
+// A host variant's staged sections in one of PlannerScratch's buffers (in: what goes up, out: what comes back): add() every
+// section (8-byte aligned, in order), alloc(), then dev() / up() / back().  A section whose host pointer is null has no device
+// pointer and is never copied.  Every call synchronises before it returns, so the next call finds both buffers free.
 struct Staging {
   template <typename T>
   struct Sec {
@@ -276,11 +277,12 @@ class DenseMap {
   void apply_transitions(const uint32_t *ent_dev, int64_t n);
 
   void synchronize();
-  // staging helpers for the host-buffer forms of the shard calls
+  // staging helpers for the host-buffer forms of the shard calls (c_api.hip): the host variants' output buffer, valid until
+  // the next call that stages -- halo_pack / halo_apply / export_transitions / apply_transitions, which consume it, do not
   uint32_t *scratch_u32(int64_t n) {
     use_device();
-    stage_c_.ensure((size_t)n * sizeof(uint32_t), stream_);
-    return (uint32_t *)stage_c_.p;
+    planner_.out.ensure((size_t)n * sizeof(uint32_t), stream_);
+    return (uint32_t *)planner_.out.p;
   }
   void copy_to_host(void *dst, const void *src_dev, size_t bytes) {
     use_device();
@@ -333,6 +335,12 @@ class DenseMap {
   // a caller's box (null: everything) in local array coordinates, intersected with the array; false: nothing is left
   bool clip_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]) const;
   void reach_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]);  // the reach calls' clipped box, checked; empty: blo[0] > bhi[0]
+  // what the planner kernels read of this map; the path calls' evaluator on the host brick cache (dense_map.hip has the types)
+  auto ray_source() const;
+  auto reach_source() const;
+  auto path_eval() const;
+  auto frontier_dist() const;
+  auto host_path_eval();
 
   Geom g_;
   ProbParams pp_;
@@ -436,8 +444,7 @@ class DenseMap {
   unsigned long long *counters_ = nullptr;
   unsigned long long *h_counters_ = nullptr;  // pinned
 
-  // staging
-  DevBuf<unsigned char> stage_a_, stage_b_, stage_c_;
+  // staging of every host variant (Staging over planner_.in / planner_.out) and the planner calls' scratch
   PlannerScratch planner_;
   // raycast front-end state (per-frame stamp arrays = Fiesta::set_occ_/set_free_, include/Fiesta.h:107-110;
   // per-ray traversal lists), lazily allocated by raycast.hip

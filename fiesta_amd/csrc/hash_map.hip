@@ -940,13 +940,13 @@ void HashMap::ensure_window_vox(const int32_t *vox, int64_t n, bool dev) {
     for (int64_t i = 0; i < n; ++i)
       for (int k = 0; k < 3; ++k) lo[k] = std::min<int64_t>(lo[k], vox[3 * i + k]), hi[k] = std::max<int64_t>(hi[k], vox[3 * i + k]);
   } else {
-    stage_c_.ensure(6 * sizeof(int32_t), stream_);
+    bbox_.ensure(6, stream_);
     const int32_t init[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
     int32_t box[6];
-    FIESTA_HIP_CHECK(hipMemcpyAsync(stage_c_.p, init, sizeof(init), hipMemcpyHostToDevice, stream_));
-    hipLaunchKernelGGL(k_h_bbox, dim3(grid_for(n, 1024, 256)), dim3(1024), 0, stream_, vox, n, (int32_t *)stage_c_.p);
+    FIESTA_HIP_CHECK(hipMemcpyAsync(bbox_.p, init, sizeof(init), hipMemcpyHostToDevice, stream_));
+    hipLaunchKernelGGL(k_h_bbox, dim3(grid_for(n, 1024, 256)), dim3(1024), 0, stream_, vox, n, bbox_.p);
     FIESTA_HIP_CHECK(hipGetLastError());
-    FIESTA_HIP_CHECK(hipMemcpyAsync(box, stage_c_.p, sizeof(box), hipMemcpyDeviceToHost, stream_));
+    FIESTA_HIP_CHECK(hipMemcpyAsync(box, bbox_.p, sizeof(box), hipMemcpyDeviceToHost, stream_));
     FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
     for (int k = 0; k < 3; ++k) lo[k] = box[k], hi[k] = box[3 + k];
   }
@@ -956,9 +956,9 @@ void HashMap::ensure_window_vox(const int32_t *vox, int64_t n, bool dev) {
 // Assign pages to every marked tile that has none yet.  Returns the "a voxel was outside the window" flag of the mark
 // kernel (k_h_mark_vox), read in the same round trip as the number of fresh tiles.
 bool HashMap::allocate_marked() {
-  stage_d_.ensure((size_t)kNTiles * sizeof(uint32_t), stream_);
+  fresh_tiles_.ensure(kNTiles, stream_);
   zero_counter(C_SCRATCH);
-  hipLaunchKernelGGL(k_h_collect, dim3(kNTiles / 256), dim3(256), 0, stream_, need_, (const int32_t *)dir_, (uint32_t *)stage_d_.p,
+  hipLaunchKernelGGL(k_h_collect, dim3(kNTiles / 256), dim3(256), 0, stream_, need_, (const int32_t *)dir_, fresh_tiles_.p,
                      &counters_[C_SCRATCH]);
   FIESTA_HIP_CHECK(hipGetLastError());
   static_assert(C_OUTSIDE == C_SCRATCH + 1, "read together");
@@ -968,7 +968,7 @@ bool HashMap::allocate_marked() {
   const bool outside = h_counters_[C_OUTSIDE] != 0;
   if (k == 0) return outside;
   ensure_pages(npages_ + k);
-  hipLaunchKernelGGL(k_h_assign, dim3(grid_for(k)), dim3(256), 0, stream_, g_, (const uint32_t *)stage_d_.p, k, (int32_t)npages_,
+  hipLaunchKernelGGL(k_h_assign, dim3(grid_for(k)), dim3(256), 0, stream_, g_, (const uint32_t *)fresh_tiles_.p, k, (int32_t)npages_,
                      dir_, page_tile_.p, page_gtile_.p);
   FIESTA_HIP_CHECK(hipGetLastError());
   npages_ += k;
@@ -980,12 +980,10 @@ void HashMap::observe_vox(const int32_t *vox, const int32_t *occ, int64_t n, int
   if (n <= 0) return;
   const int32_t *dvox = vox, *docc = occ;
   if (!dev) {
-    stage_a_.ensure(n * 3 * sizeof(int32_t), stream_);
-    stage_b_.ensure(n * sizeof(int32_t), stream_);
-    FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, vox, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    FIESTA_HIP_CHECK(hipMemcpyAsync(stage_b_.p, occ, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    dvox = (const int32_t *)stage_a_.p;
-    docc = (const int32_t *)stage_b_.p;
+    Staging in{planner_.in, stream_};
+    const auto v = in.add(vox, 3 * n), o = in.add(occ, n);
+    in.alloc(), in.up(v, 3 * n), in.up(o, n);
+    dvox = in.dev(v), docc = in.dev(o);
   }
   // host batches: the bounding box decides up front whether the window has to move; device batches: the mark kernel
   // reports a voxel outside the window (no extra round trip when there is none), then the box is reduced on the device
@@ -1081,17 +1079,16 @@ void HashMap::observe_pos(const double *pos, const int32_t *occ, int64_t n, int3
     }
     ensure_window(lo, hi);
   }
-  stage_a_.ensure(n * 3 * sizeof(double), stream_);
-  stage_b_.ensure(n * sizeof(int32_t), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, pos, n * 3 * sizeof(double), hipMemcpyHostToDevice, stream_));
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_b_.p, occ, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_h_mark_pos, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const double *)stage_a_.p,
-                     (const int32_t *)stage_b_.p, n, need_);
+  Staging in{planner_.in, stream_};
+  const auto dp = in.add(pos, 3 * n);
+  const auto docc = in.add(occ, n);
+  in.alloc(), in.up(dp, 3 * n), in.up(docc, n);
+  hipLaunchKernelGGL(k_h_mark_pos, dim3(grid_for(n)), dim3(256), 0, stream_, g_, in.dev(dp), in.dev(docc), n, need_);
   allocate_marked();
   touched_upper_ = std::min<int64_t>(npages_ * kPageVox, touched_upper_ + n);
   touched_.ensure((size_t)touched_upper_, stream_, touched_.cap);
-  hipLaunchKernelGGL(k_h_observe_pos, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const int32_t *)dir_, (const double *)stage_a_.p,
-                     (const int32_t *)stage_b_.p, n, cnt_.p, touched_.p, counters_);
+  hipLaunchKernelGGL(k_h_observe_pos, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const int32_t *)dir_, in.dev(dp), in.dev(docc), n,
+                     cnt_.p, touched_.p, counters_);
   FIESTA_HIP_CHECK(hipGetLastError());
   if (ret) {
     for (int64_t i = 0; i < n; ++i) {
@@ -1411,12 +1408,13 @@ void HashMap::get_distance_vox(const int32_t *vox, int64_t n, double *out) {
   }
   use_device();
   if (n <= 0) return;
-  stage_a_.ensure(n * 3 * sizeof(int32_t), stream_);
-  stage_c_.ensure(n * sizeof(double), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, vox, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  Staging in{planner_.in, stream_}, res{planner_.out, stream_};
+  const auto q = in.add(vox, 3 * n);
+  const auto d = res.add(out, n);
+  in.alloc(), in.up(q, 3 * n), res.alloc();
   hipLaunchKernelGGL(k_h_query_dist, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p,
-                     (const int32_t *)stage_a_.p, (const double *)nullptr, n, (double *)stage_c_.p);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(out, stage_c_.p, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+                     in.dev(q), (const double *)nullptr, n, res.dev(d));
+  res.back(d, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 void HashMap::get_distance_pos(const double *pos, int64_t n, double *out) {
@@ -1428,12 +1426,13 @@ void HashMap::get_distance_pos(const double *pos, int64_t n, double *out) {
   }
   use_device();
   if (n <= 0) return;
-  stage_a_.ensure(n * 3 * sizeof(double), stream_);
-  stage_c_.ensure(n * sizeof(double), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, pos, n * 3 * sizeof(double), hipMemcpyHostToDevice, stream_));
+  Staging in{planner_.in, stream_}, res{planner_.out, stream_};
+  const auto q = in.add(pos, 3 * n);
+  const auto d = res.add(out, n);
+  in.alloc(), in.up(q, 3 * n), res.alloc();
   hipLaunchKernelGGL(k_h_query_dist, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p,
-                     (const int32_t *)nullptr, (const double *)stage_a_.p, n, (double *)stage_c_.p);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(out, stage_c_.p, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+                     (const int32_t *)nullptr, in.dev(q), n, res.dev(d));
+  res.back(d, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 void HashMap::get_dist_grad(const double *pos, int64_t n, double *dist, double *grad) {
@@ -1444,37 +1443,50 @@ void HashMap::get_dist_grad(const double *pos, int64_t n, double *dist, double *
   }
   use_device();
   if (n <= 0) return;
-  stage_a_.ensure(n * 3 * sizeof(double), stream_);
-  stage_b_.ensure(n * 3 * sizeof(double), stream_);
-  stage_c_.ensure(n * sizeof(double), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, pos, n * 3 * sizeof(double), hipMemcpyHostToDevice, stream_));
+  Staging in{planner_.in, stream_}, res{planner_.out, stream_};
+  const auto q = in.add(pos, 3 * n);
+  const auto d = res.add(dist, n), gr = res.add(grad, 3 * n);  // (a null grad: the kernel gets null and computes none)
+  in.alloc(), in.up(q, 3 * n), res.alloc();
   hipLaunchKernelGGL(k_h_query_trilinear, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p,
-                     (const double *)stage_a_.p, n, (double *)stage_c_.p, (double *)stage_b_.p);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(dist, stage_c_.p, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
-  if (grad) FIESTA_HIP_CHECK(hipMemcpyAsync(grad, stage_b_.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+                     in.dev(q), n, res.dev(d), res.dev(gr));
+  res.back(d, n), res.back(gr, 3 * n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+// what the planner kernels read of this map, over a page table already fetched (each type next to its kernels), and the path
+// calls' evaluator on the host brick cache
+auto HashMap::ray_source(const PageTable &tab) const {
+  return HashRaySource{ray_geom(g_), g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p};
+}
+auto HashMap::reach_source(const PageTable &tab) const {
+  return HashReachSource{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p};
+}
+auto HashMap::path_eval(const PageTable &tab) const { return HashPathEval{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}; }
+auto HashMap::frontier_pages(const PageTable &tab) const { return HashFrontierPages{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}; }
+auto HashMap::host_path_eval() {
+  return [this](const double *p, double *grad) {
+    auto corner = [&](int vx, int vy, int vz) { return host_distance(vx, vy, vz); };
+    return h_trilinear(g_, corner, p, grad);
+  };
 }
 void HashMap::path_clearance(const PathClearanceArgs &a) {
   if (a.n_paths <= 0) return;
   if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
-    auto corner = [&](int vx, int vy, int vz) { return host_distance(vx, vy, vz); };
-    auto ev = [&](const double *p, double *grad) { return h_trilinear(g_, corner, p, grad); };
+    auto ev = host_path_eval();
     path_host(ev, a.w, a.off, a.n_paths, a.step, a.margin, *a.res);
     return;
   }
   use_device();
-  path_clearance_run(stream_, planner_, HashPathEval{g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p}, a);
+  path_clearance_run(stream_, planner_, path_eval(page_table()), a);
 }
 void HashMap::path_cost(const PathCostArgs &a) {
   if (a.n_paths <= 0) return;
   if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
-    auto corner = [&](int vx, int vy, int vz) { return host_distance(vx, vy, vz); };
-    auto ev = [&](const double *p, double *grad) { return h_trilinear(g_, corner, p, grad); };
+    auto ev = host_path_eval();
     path_cost_host(ev, a.w, a.n_wp, a.off, a.n_paths, a.step, a.margin, *a.res);
     return;
   }
   use_device();
-  path_cost_run(stream_, planner_, HashPathEval{g_, (const int32_t *)dir_, page_table(), (const vox_t *)coc_.p}, a);
+  path_cost_run(stream_, planner_, path_eval(page_table()), a);
 }
 void HashMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n > 0 && n <= kHostQueries) {
@@ -1483,12 +1495,13 @@ void HashMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   }
   use_device();
   if (n <= 0) return;
-  stage_a_.ensure(n * 3 * sizeof(int32_t), stream_);
-  stage_c_.ensure(n * sizeof(int32_t), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, vox, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  Staging in{planner_.in, stream_}, res{planner_.out, stream_};
+  const auto q = in.add(vox, 3 * n);
+  const auto o = res.add(out, n);
+  in.alloc(), in.up(q, 3 * n), res.alloc();
   hipLaunchKernelGGL(k_h_query_occ, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const int32_t *)dir_, page_table(), (const uint32_t *)occbits_.p,
-                     (const int32_t *)stage_a_.p, (const double *)nullptr, n, (int32_t *)stage_c_.p);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(out, stage_c_.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+                     in.dev(q), (const double *)nullptr, n, res.dev(o));
+  res.back(o, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 void HashMap::get_occupancy_pos(const double *pos, int64_t n, int32_t *out) {
@@ -1500,12 +1513,13 @@ void HashMap::get_occupancy_pos(const double *pos, int64_t n, int32_t *out) {
   }
   use_device();
   if (n <= 0) return;
-  stage_a_.ensure(n * 3 * sizeof(double), stream_);
-  stage_c_.ensure(n * sizeof(int32_t), stream_);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(stage_a_.p, pos, n * 3 * sizeof(double), hipMemcpyHostToDevice, stream_));
+  Staging in{planner_.in, stream_}, res{planner_.out, stream_};
+  const auto q = in.add(pos, 3 * n);
+  const auto o = res.add(out, n);
+  in.alloc(), in.up(q, 3 * n), res.alloc();
   hipLaunchKernelGGL(k_h_query_occ, dim3(grid_for(n)), dim3(256), 0, stream_, g_, (const int32_t *)dir_, page_table(), (const uint32_t *)occbits_.p,
-                     (const int32_t *)nullptr, (const double *)stage_a_.p, n, (int32_t *)stage_c_.p);
-  FIESTA_HIP_CHECK(hipMemcpyAsync(out, stage_c_.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+                     (const int32_t *)nullptr, in.dev(q), n, res.dev(o));
+  res.back(o, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
@@ -1513,19 +1527,14 @@ int64_t HashMap::download(int32_t *vox, int32_t *d2, int32_t *coc, uint8_t *occ)
   use_device();
   const int64_t n = npages_ * kPageVox;
   if (n == 0 || (!vox && !d2 && !coc && !occ)) return n;
-  int32_t *dv = nullptr, *dd = nullptr, *dc = nullptr;
-  uint8_t *doc = nullptr;
-  if (vox) stage_a_.ensure(n * 3 * sizeof(int32_t), stream_), dv = (int32_t *)stage_a_.p;
-  if (coc) stage_b_.ensure(n * 3 * sizeof(int32_t), stream_), dc = (int32_t *)stage_b_.p;
-  if (d2) stage_c_.ensure(n * sizeof(int32_t), stream_), dd = (int32_t *)stage_c_.p;
-  if (occ) stage_d_.ensure(std::max<size_t>((size_t)n, (size_t)kNTiles * 4), stream_), doc = (uint8_t *)stage_d_.p;
+  Staging res{planner_.out, stream_};  // (whole-pool arrays: one that is not requested takes no room either)
+  const auto dv = res.add(vox, vox ? 3 * n : 0), dc = res.add(coc, coc ? 3 * n : 0), dd = res.add(d2, d2 ? n : 0);
+  const auto doc = res.add(occ, occ ? n : 0);
+  res.alloc();
   hipLaunchKernelGGL(k_h_export, dim3(grid_for(n, 256, 8192)), dim3(256), 0, stream_, (const int32_t *)page_gtile_.p, n,
-                     (const vox_t *)coc_.p, (const uint32_t *)occbits_.p, dv, dd, dc, doc);
+                     (const vox_t *)coc_.p, (const uint32_t *)occbits_.p, res.dev(dv), res.dev(dd), res.dev(dc), res.dev(doc));
   FIESTA_HIP_CHECK(hipGetLastError());
-  if (vox) FIESTA_HIP_CHECK(hipMemcpyAsync(vox, dv, n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  if (coc) FIESTA_HIP_CHECK(hipMemcpyAsync(coc, dc, n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  if (d2) FIESTA_HIP_CHECK(hipMemcpyAsync(d2, dd, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  if (occ) FIESTA_HIP_CHECK(hipMemcpyAsync(occ, doc, n, hipMemcpyDeviceToHost, stream_));
+  res.back(dv, 3 * n), res.back(dc, 3 * n), res.back(dd, n), res.back(doc, n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }
@@ -1533,19 +1542,18 @@ int64_t HashMap::download(int32_t *vox, int32_t *d2, int32_t *coc, uint8_t *occ)
 int64_t HashMap::point_cloud(int vis_lower_bound, int vis_upper_bound, float *xyz, int64_t cap) {
   use_device();
   zero_counter(C_SCRATCH);
-  float *dout = nullptr;
-  if (xyz && cap > 0) {
-    stage_a_.ensure((size_t)cap * 3 * sizeof(float), stream_);
-    dout = (float *)stage_a_.p;
-  }
+  if (!xyz) cap = 0;
+  Staging res{planner_.out, stream_};
+  const auto pts = res.add(xyz, 3 * cap);
+  res.alloc();
   const int64_t nrows = npages_ * kPageRows;
   if (nrows)
     hipLaunchKernelGGL(k_h_point_cloud, dim3(grid_for(nrows, 256, 8192)), dim3(256), 0, stream_, g_, (const int32_t *)page_gtile_.p, nrows,
-                       (const uint32_t *)occbits_.p, clamp30(ur_[0]), clamp30(ur_[3]), clamp30(ur_[1]), clamp30(ur_[4]), vis_lower_bound, vis_upper_bound, dout,
-                       (unsigned long long)(dout ? cap : 0), &counters_[C_SCRATCH]);
+                       (const uint32_t *)occbits_.p, clamp30(ur_[0]), clamp30(ur_[3]), clamp30(ur_[1]), clamp30(ur_[4]), vis_lower_bound, vis_upper_bound, res.dev(pts),
+                       (unsigned long long)cap, &counters_[C_SCRATCH]);
   FIESTA_HIP_CHECK(hipGetLastError());
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
-  if (dout && n) FIESTA_HIP_CHECK(hipMemcpyAsync(xyz, dout, (size_t)std::min(n, cap) * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  res.back(pts, 3 * std::min(n, cap));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }
@@ -1562,24 +1570,21 @@ int64_t HashMap::frontier_voxels(const FrontierArgs &a) {
   if (a.lo) b = FrontierBox{clamp30(a.lo[0]), clamp30(a.lo[1]), clamp30(a.lo[2]), clamp30(a.hi[0]), clamp30(a.hi[1]), clamp30(a.hi[2])};
   const bool empty = b.x0 > b.x1 || b.y0 > b.y1 || b.z0 > b.z1 || npages_ == 0;
   const int64_t cap = std::min<int64_t>(a.capacity, npages_ * kPageVox);
-  int32_t *dvox = a.dev ? a.vox : nullptr;
-  uint8_t *dmask = a.dev ? a.mask : nullptr;
-  if (!a.dev && cap > 0) {
-    if (a.vox) stage_a_.ensure((size_t)cap * 3 * sizeof(int32_t), stream_), dvox = (int32_t *)stage_a_.p;
-    if (a.mask) stage_b_.ensure((size_t)cap, stream_), dmask = (uint8_t *)stage_b_.p;
-  }
+  Staging res{planner_.out, stream_};  // (the host variant's)
+  const auto vox = res.add(a.vox, 3 * cap);
+  const auto mask = res.add(a.mask, cap);
+  if (!a.dev) res.alloc();
+  int32_t *dvox = a.dev ? a.vox : res.dev(vox);
+  uint8_t *dmask = a.dev ? a.mask : res.dev(mask);
   if (!empty) {
     hipLaunchKernelGGL(k_frontier_hash<HashFrontierPages>, dim3(grid_for(npages_, 1, 8192)), dim3(256), 0, stream_,
                        (const int32_t *)page_gtile_.p, npages_, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p, b,
-                       HashFrontierPages{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}, a.min_clearance,
-                       FrontierOut{dvox, dmask, (unsigned long long)cap, count});
+                       frontier_pages(tab), a.min_clearance, FrontierOut{dvox, dmask, (unsigned long long)cap, count});
     FIESTA_HIP_CHECK(hipGetLastError());
   }
   if (a.dev) return 0;
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
-  const size_t k = (size_t)std::min(n, cap);
-  if (dvox && k) FIESTA_HIP_CHECK(hipMemcpyAsync(a.vox, dvox, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  if (dmask && k) FIESTA_HIP_CHECK(hipMemcpyAsync(a.mask, dmask, k, hipMemcpyDeviceToHost, stream_));
+  res.back(vox, 3 * std::min(n, cap)), res.back(mask, std::min(n, cap));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }
@@ -1602,7 +1607,7 @@ void HashMap::reach_field(const ReachArgs &a) {
   reach_box(a.lo, a.hi, blo, bhi);
   const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
   const int off[3] = {0, 0, 0};
-  reach_run(stream_, planner_, HashReachSource{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p}, blo, bhi, off, a);
+  reach_run(stream_, planner_, reach_source(tab), blo, bhi, off, a);
 }
 // fiesta_hip_reach_matrix[_dev] (reach_matrix_kernels.hpp): reach_field's box and source; the page table is rebuilt once per call
 void HashMap::reach_matrix(const ReachMatrixArgs &a) {
@@ -1610,7 +1615,7 @@ void HashMap::reach_matrix(const ReachMatrixArgs &a) {
   reach_box(a.lo, a.hi, blo, bhi);
   const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
   const int off[3] = {0, 0, 0};
-  reach_matrix_run(stream_, planner_, HashReachSource{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p}, blo, bhi, off, a);
+  reach_matrix_run(stream_, planner_, reach_source(tab), blo, bhi, off, a);
 }
 
 // fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin
@@ -1622,9 +1627,7 @@ void HashMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxel
 void HashMap::view_coverage(const ViewArgs &a) {
   use_device();
   const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
-  const ViewSource<HashRaySource, HashFrontierPages> vs{
-      HashRaySource{ray_geom(g_), g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p},
-      HashFrontierPages{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}, {0, 0, 0}};
+  const ViewSource<HashRaySource, HashFrontierPages> vs{ray_source(tab), frontier_pages(tab), {0, 0, 0}};
   view_coverage_run(stream_, planner_, vs, a);
 }
 
@@ -1633,30 +1636,24 @@ void HashMap::ray_query(const RayArgs &a) {
   if (a.n <= 0) return;
   use_device();
   const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
-  ray_query_run(stream_, planner_, HashRaySource{ray_geom(g_), g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p}, a);
+  ray_query_run(stream_, planner_, ray_source(tab), a);
 }
 
 int64_t HashMap::slice_marker(int slice, double max_dist, double *xyz, float *rgba, int64_t cap) {
   use_device();
   zero_counter(C_SCRATCH);
-  double *dx = nullptr;
-  float *dc = nullptr;
-  if (xyz && rgba && cap > 0) {
-    stage_a_.ensure((size_t)cap * 3 * sizeof(double), stream_);
-    stage_b_.ensure((size_t)cap * 4 * sizeof(float), stream_);
-    dx = (double *)stage_a_.p, dc = (float *)stage_b_.p;
-  }
+  if (!xyz || !rgba) cap = 0;  // (both or nothing)
+  Staging res{planner_.out, stream_};
+  const auto dx = res.add(xyz, 3 * cap);
+  const auto dc = res.add(rgba, 4 * cap);
+  res.alloc();
   if (npages_)
     hipLaunchKernelGGL(k_h_slice_marker, dim3(grid_for(npages_ * kPageRows, 256, 8192)), dim3(256), 0, stream_, g_,
                        (const int32_t *)page_gtile_.p, npages_, (const vox_t *)coc_.p, clamp30(ur_[0]), clamp30(ur_[3]), clamp30(ur_[1]), clamp30(ur_[4]), slice,
-                       max_dist, dx, dc, (unsigned long long)(dx ? cap : 0), &counters_[C_SCRATCH]);
+                       max_dist, res.dev(dx), res.dev(dc), (unsigned long long)cap, &counters_[C_SCRATCH]);
   FIESTA_HIP_CHECK(hipGetLastError());
   const int64_t n = (int64_t)read_counter(C_SCRATCH);
-  if (dx && n) {
-    const size_t k = (size_t)std::min(n, cap);
-    FIESTA_HIP_CHECK(hipMemcpyAsync(xyz, dx, k * 3 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    FIESTA_HIP_CHECK(hipMemcpyAsync(rgba, dc, k * 4 * sizeof(float), hipMemcpyDeviceToHost, stream_));
-  }
+  res.back(dx, 3 * std::min(n, cap)), res.back(dc, 4 * std::min(n, cap));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
 }

@@ -112,6 +112,12 @@ class HashMap {
   bool run_levels(fiesta_hip_stats *st, unsigned long long ni, unsigned long long nd);  // false: the rounds finish
   PageTable page_table();  // the map-wide page table of the query kernels (hash_map.hip)
   void reach_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]);  // the reach calls' clamped box, checked; empty: blo[0] > bhi[0]
+  // what the planner kernels read of this map, over a page table already fetched; the path calls' evaluator on the host brick cache
+  auto ray_source(const PageTable &tab) const;
+  auto reach_source(const PageTable &tab) const;
+  auto path_eval(const PageTable &tab) const;
+  auto frontier_pages(const PageTable &tab) const;
+  auto host_path_eval();
   // scalar queries (n <= kHostQueries positions per call, host pointers): a host-side cache of 16^3-voxel bricks of DISTANCES (f64,
   // as the query kernels compute them) and occupancy bits, keyed by map brick coordinates, fetched on first touch (r06: the dense
   // map's HostBricks for the paged map).  field_epoch_ is bumped by everything that may change the field or what a lookup finds.
@@ -173,8 +179,9 @@ class HashMap {
   LevelEngine *lv_ = nullptr;  // level_kernels.hpp
   int64_t dropped_host_ = 0;  // voxels of observe_box() requests clipped away by the window (added to C_DROPPED in stats)
   unsigned long long *counters_ = nullptr, *h_counters_ = nullptr;
-  DevBuf<unsigned char> stage_a_, stage_b_, stage_c_, stage_d_;
-  PlannerScratch planner_;
+  DevBuf<int32_t> bbox_;           // ensure_window_vox: a device batch's bounding box, min xyz then max xyz
+  DevBuf<uint32_t> fresh_tiles_;   // allocate_marked: the marked tiles without a page (k_h_collect), kNTiles entries
+  PlannerScratch planner_;         // staging of every host variant (Staging over in / out) and the planner calls' scratch
 };
 
 void raycast_single(const double *start, const double *end, const double *minv, const double *maxv, double *out,
