@@ -10,6 +10,7 @@ from .cluster_model import cluster_model, cluster_stencil  # noqa: F401
 from .view_model import VIEW_OMNI, view_coverage_model, view_ring  # noqa: F401
 from .reach_model import (REACH_PATHS_SHORTCUT, REACH_THROUGH_UNKNOWN, reach_matrix_model, reach_model, reach_moves,  # noqa: F401
                           reach_paths_model, reach_visible, reach_walk)
+from .tour_model import TOUR_CLOSED, best_move, tour_model  # noqa: F401
 
-__all__ = ["ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "reach_model", "reach_matrix_model", "REACH_THROUGH_UNKNOWN", "reach_moves", "reach_paths_model", "reach_visible", "reach_walk", "REACH_PATHS_SHORTCUT", "cluster_model", "cluster_stencil", "view_coverage_model", "view_ring", "VIEW_OMNI", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
+__all__ = ["tour_model", "best_move", "TOUR_CLOSED", "ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "reach_model", "reach_matrix_model", "REACH_THROUGH_UNKNOWN", "reach_moves", "reach_paths_model", "reach_visible", "reach_walk", "REACH_PATHS_SHORTCUT", "cluster_model", "cluster_stencil", "view_coverage_model", "view_ring", "VIEW_OMNI", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
            "D2_INF"]

@@ -107,6 +107,17 @@ class ReachMatrixInfo(C.Structure):
                 ("fields", C.c_int64), ("batches", C.c_int64), ("rounds", C.c_int64), ("tile_visits", C.c_int64)]
 
 
+class TourResult(C.Structure):
+    """fiesta_hip_tour_result: one array per output of fiesta_hip_site_tour, every pointer nullable"""
+    _fields_ = [("order", C.c_void_p), ("site_status", C.c_void_p), ("leg_cost", C.c_void_p), ("restart_length", C.c_void_p)]
+
+
+class TourInfo(C.Structure):
+    """fiesta_hip_tour_info: what one fiesta_hip_site_tour call found"""
+    _fields_ = [("n_visited", C.c_int32), ("best_restart", C.c_int32), ("length", C.c_int64), ("nn_length", C.c_int64), ("moves", C.c_int64),
+                ("capped", C.c_int64)]
+
+
 class ReachPathsResult(C.Structure):
     """fiesta_hip_reach_paths_result: offsets is required, every other pointer nullable"""
     _fields_ = [("offsets", C.c_void_p), ("waypoints_vox", C.c_void_p), ("waypoints_pos", C.c_void_p), ("status", C.c_void_p),
@@ -253,6 +264,8 @@ def load():
         "fiesta_hip_reach_field_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, vp, vp]),
         "fiesta_hip_reach_matrix": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i32, vp, vp]),
         "fiesta_hip_reach_matrix_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i32, vp, vp]),
+        "fiesta_hip_site_tour": (C.c_int, [vp, vp, i32, i64, i32, i32, i32, C.c_uint64, i32, vp, vp]),
+        "fiesta_hip_site_tour_dev": (C.c_int, [vp, vp, i32, i64, i32, i32, i32, C.c_uint64, i32, vp, vp]),
         "fiesta_hip_reach_paths": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
         "fiesta_hip_reach_paths_dev": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
         "fiesta_hip_cluster_voxels": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, i64, vp, vp]),

@@ -17,6 +17,7 @@
 #include "reach_matrix_kernels.hpp"
 #include "reach_path_kernels.hpp"
 #include "shard_group.hpp"
+#include "tour_kernels.hpp"
 #include "view_kernels.hpp"
 
 using fiesta::DenseMap;
@@ -137,6 +138,18 @@ void reach_matrix(fiesta_hip_map *m, const fiesta::ReachMatrixArgs &a) {
   need(m != nullptr, "null map handle");
   need(m->dense != nullptr || a.lo != nullptr, "reach_matrix: a hash-block map has no outside, the box is mandatory");
   on_store(m, [&](auto &s) { s.reach_matrix(a); });
+}
+// none of these errors needs a device; what the matrix itself must satisfy is checked on the device, before any search
+void site_tour(fiesta_hip_map *m, const fiesta::TourArgs &a) {
+  need(a.cost != nullptr, "site_tour: cost is null");
+  need(a.n >= 1 && a.n <= FIESTA_HIP_TOUR_MAX_SITES, "site_tour: n must be 1 .. 512");
+  need(a.start >= 0 && a.start < a.n, "site_tour: start is no site");
+  need(a.ld >= a.n, "site_tour: ld is below n");
+  need(a.restarts >= 1 && a.restarts <= FIESTA_HIP_TOUR_MAX_RESTARTS, "site_tour: restarts must be 1 .. 4096");
+  need((a.flags & ~FIESTA_HIP_TOUR_CLOSED) == 0, "site_tour: unknown flag bits");
+  need(a.max_moves >= 0, "site_tour: max_moves is negative");
+  need(m != nullptr, "null map handle");
+  on_store(m, [&](auto &s) { s.site_tour(a); });
 }
 // none of these errors needs a device, and all but the last are checked before the handle is touched
 void reach_paths(fiesta_hip_map *m, const fiesta::ReachPathArgs &a) {
@@ -564,6 +577,14 @@ int fiesta_hip_reach_matrix_dev(fiesta_hip_map *m, const int32_t lo[3], const in
   return guarded([&] {
     reach_matrix(m, {lo, hi, sources_dev, n_sources, targets_dev, n_targets, min_clearance, connectivity, flags, max_fields, result, info, true});
   });
+}
+int fiesta_hip_site_tour(fiesta_hip_map *m, const int32_t *cost, int32_t n, int64_t ld, int32_t start, int32_t flags, int32_t restarts,
+                         uint64_t seed, int32_t max_moves, const fiesta_hip_tour_result *result, fiesta_hip_tour_info *info) {
+  return guarded([&] { site_tour(m, {cost, n, ld, start, flags, restarts, seed, max_moves, result, info, false}); });
+}
+int fiesta_hip_site_tour_dev(fiesta_hip_map *m, const int32_t *cost_dev, int32_t n, int64_t ld, int32_t start, int32_t flags, int32_t restarts,
+                             uint64_t seed, int32_t max_moves, const fiesta_hip_tour_result *result, fiesta_hip_tour_info *info) {
+  return guarded([&] { site_tour(m, {cost_dev, n, ld, start, flags, restarts, seed, max_moves, result, info, true}); });
 }
 int fiesta_hip_reach_paths(fiesta_hip_map *m, const int32_t *cost, const int32_t box_lo[3], const int32_t box_hi[3], const int32_t *targets,
                            int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span, int64_t capacity,

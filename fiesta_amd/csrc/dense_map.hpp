@@ -71,6 +71,14 @@ struct ReachMatrixScratch {
   DevBuf<unsigned long long> ctr, reached;
 };
 
+// scratch of fiesta_hip_site_tour (tour_kernels.hpp), owned by a map: the call's header words and info, the visited sites and the
+// statuses, the compact m x m matrix, and per restart its final tour, length, moves and capped flag; allocated on first use, grown
+// on demand, freed with the map; no other call touches it
+struct TourScratch {
+  DevBuf<int32_t> head, site, status, mat, tours, stat;
+  DevBuf<long long> len;
+};
+
 // scratch of fiesta_hip_cluster_voxels (cluster_kernels.hpp), owned by a map: the voxel hash table, the per-entry union-find arrays,
 // the per-cluster accumulators and two counters; allocated on first use, grown on demand, freed with the map
 struct ClusterScratch {
@@ -95,6 +103,7 @@ struct PlannerScratch {
   DevBuf<unsigned char> in, tmp, out;
   ReachScratch reach;
   ReachMatrixScratch reach_matrix;
+  TourScratch tour;
   ClusterScratch cluster;
   ViewScratch view;
 };
@@ -141,6 +150,7 @@ struct RayArgs;
 struct ReachArgs;
 struct ReachMatrixArgs;
 struct ReachPathArgs;
+struct TourArgs;
 struct ClusterArgs;
 struct ViewArgs;
 
@@ -251,6 +261,7 @@ class DenseMap {
   void ray_query(const RayArgs &a);
   void reach_field(const ReachArgs &a);
   void reach_matrix(const ReachMatrixArgs &a);
+  void site_tour(const TourArgs &a);
   void reach_paths(const ReachPathArgs &a);
   void cluster_voxels(const ClusterArgs &a);
   void view_coverage(const ViewArgs &a);

@@ -24,6 +24,7 @@
 #include "reach_kernels.hpp"
 #include "reach_matrix_kernels.hpp"
 #include "reach_path_kernels.hpp"
+#include "tour_kernels.hpp"
 #include "cluster_kernels.hpp"
 #include "view_kernels.hpp"
 #include "path_kernels.hpp"
@@ -1621,6 +1622,8 @@ void HashMap::reach_matrix(const ReachMatrixArgs &a) {
 // fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin
 void HashMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
 void HashMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
+// fiesta_hip_site_tour[_dev] (tour_kernels.hpp): no voxel is read
+void HashMap::site_tour(const TourArgs &a) { use_device(), site_tour_run(stream_, planner_, a); }
 
 // fiesta_hip_view_coverage[_dev] (view_kernels.hpp).  The ray query's source, the frontier call's distance (map voxel
 // coordinates).  Every page answers, resident or parked.

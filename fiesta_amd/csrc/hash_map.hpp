@@ -85,6 +85,7 @@ class HashMap {
   void ray_query(const RayArgs &a);
   void reach_field(const ReachArgs &a);
   void reach_matrix(const ReachMatrixArgs &a);
+  void site_tour(const TourArgs &a);
   void reach_paths(const ReachPathArgs &a);
   void cluster_voxels(const ClusterArgs &a);
   void view_coverage(const ViewArgs &a);

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, Stats, check
+from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, Stats, TourInfo, TourResult, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -804,6 +804,38 @@ class ESDFMap:
                                                     C.c_void_p(targets_dev_ptr or None), int(n_targets), float(min_clearance),
                                                     int(connectivity), int(flags), int(max_fields), C.byref(res), C.byref(info)))
         return self._reach_matrix_info(info)
+
+    def SiteTour(self, cost, start=0, closed=False, restarts=64, seed=0, max_moves=0) -> dict:
+        """fiesta_hip_site_tour: the order in which to visit every site the start can reach through the symmetric cost matrix `cost`
+        ((n, ld) int32 with ld >= n: ReachMatrix's square form; -1 and 2^31 - 1 are no connections), as an open path from `start` or
+        a closed tour back to it, minimising the summed leg cost: `restarts` local searches (2-opt and Or-opt, best improvement) run
+        side by side, restart 0 from the nearest-neighbour tour and the others from shuffles seeded by `seed`, each applying at most
+        max_moves moves (0: 8 per visited site).  Returns order, site_status, leg_cost ((n,) int32), restart_length ((restarts,)
+        int64) and the fields of fiesta_hip_tour_info; fiesta_amd.tour_model is the definition"""
+        c = np.ascontiguousarray(cost, dtype=np.int32)
+        if c.ndim != 2:
+            raise ValueError("cost must be a matrix")
+        n, ld = c.shape
+        out = {"order": np.empty(n, np.int32), "site_status": np.empty(n, np.int32), "leg_cost": np.empty(n, np.int32),
+               "restart_length": np.empty(max(int(restarts), 0), np.int64)}
+        res = TourResult(*[a.ctypes.data if a.size else None for a in out.values()])
+        info = TourInfo()
+        check(self._lib.fiesta_hip_site_tour(self._h, _p(c) if c.size else None, n, ld, int(start), 1 if closed else 0, int(restarts),
+                                             int(seed) & (2 ** 64 - 1), int(max_moves), C.byref(res), C.byref(info)))
+        out.update({k: getattr(info, k) for k, _ in TourInfo._fields_})
+        return out
+
+    def SiteTourDevice(self, cost_dev_ptr: int, n: int, ld: int, start=0, closed=False, restarts=64, seed=0, max_moves=0, order_dev_ptr: int = 0,
+                       site_status_dev_ptr: int = 0, leg_cost_dev_ptr: int = 0, restart_length_dev_ptr: int = 0) -> dict:
+        """fiesta_hip_site_tour_dev: the matrix (n x n int32, leading dimension ld: where ReachMatrixDevice left it), order,
+        site_status, leg_cost (n int32 each) and restart_length (restarts int64) resident on the device (0: not written); returns
+        the fields of fiesta_hip_tour_info.  Synchronises with the map's stream"""
+        res = TourResult(int(order_dev_ptr) or None, int(site_status_dev_ptr) or None, int(leg_cost_dev_ptr) or None,
+                         int(restart_length_dev_ptr) or None)
+        info = TourInfo()
+        check(self._lib.fiesta_hip_site_tour_dev(self._h, C.c_void_p(cost_dev_ptr or None), int(n), int(ld), int(start), 1 if closed else 0,
+                                                 int(restarts), int(seed) & (2 ** 64 - 1), int(max_moves), C.byref(res), C.byref(info)))
+        return {k: getattr(info, k) for k, _ in TourInfo._fields_}
 
     def ReachPaths(self, targets, cost=None, box=None, connectivity=26, shortcut=False, max_span=4096, want_pos=True) -> dict:
         """fiesta_hip_reach_paths: per target ((n, 3) map voxels) the path down a cost-to-go field from the seed it was reached from to

@@ -350,6 +350,30 @@ class ESDFMap {
                                tv.empty() ? nullptr : tv.data(), (int64_t)targets.size(), min_clearance, connectivity, flags, max_fields, &r, &info));
     return info;
   }
+  // Site tour (fiesta_hip_site_tour, include/fiesta_hip.h): the order in which to visit every site that `start` can reach through the
+  // symmetric n x n matrix `cost` (ReachMatrix's square form, row-major; ld: its leading dimension, 0 for n), as an open path from
+  // the start or a closed tour back to it: `restarts` local searches side by side (2-opt and Or-opt, best improvement), restart 0 from
+  // the nearest-neighbour tour, the others from shuffles seeded by `seed`, each applying at most max_moves moves (0: 8 per visited
+  // site).  order / leg_cost hold the info.n_visited visited sites, the start first; site_status: FIESTA_HIP_TOUR_SITE_* per site.
+  struct SiteTourResult {
+    std::vector<int32_t> order, leg_cost, site_status;
+    std::vector<int64_t> restart_length;
+    fiesta_hip_tour_info info;
+  };
+  SiteTourResult SiteTour(const std::vector<int32_t> &cost, int32_t n, int32_t start = 0, bool closed = false, int32_t restarts = 64,
+                          uint64_t seed = 0, int32_t max_moves = 0, int64_t ld = 0) {
+    if (ld == 0) ld = n;
+    if (n < 1 || ld < n || cost.size() < (size_t)(n - 1) * (size_t)ld + (size_t)n) throw std::invalid_argument("SiteTour: cost does not hold n rows of ld entries");
+    if (restarts < 1 || restarts > FIESTA_HIP_TOUR_MAX_RESTARTS) throw std::invalid_argument("SiteTour: restarts must be 1 .. 4096");
+    SiteTourResult out;
+    out.order.assign((size_t)n, -1), out.leg_cost.assign((size_t)n, -1), out.site_status.assign((size_t)n, FIESTA_HIP_TOUR_SITE_SKIPPED);
+    out.restart_length.assign((size_t)restarts, 0);
+    out.info = fiesta_hip_tour_info{};
+    const fiesta_hip_tour_result r{out.order.data(), out.site_status.data(), out.leg_cost.data(), out.restart_length.data()};
+    ck(fiesta_hip_site_tour(h_, cost.data(), n, ld, start, closed ? FIESTA_HIP_TOUR_CLOSED : 0, restarts, seed, max_moves, &r, &out.info));
+    out.order.resize((size_t)out.info.n_visited), out.leg_cost.resize((size_t)out.info.n_visited);
+    return out;
+  }
   // Reach paths (fiesta_hip_reach_paths, include/fiesta_hip.h): per target voxel the path down a cost-to-go field, from the seed it was
   // reached from to the target.  The field is the one the map retained from the last ReachField call (cost null), or *cost with its
   // inclusive voxel box [box_lo, box_hi] (ReachField's info.box_lo / box_hi) and the connectivity it was flooded with.  shortcut: the

@@ -132,7 +132,7 @@ const char *fiesta_hip_last_error(void);
 /* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev].
  * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev], fiesta_hip_ray_query[_dev], fiesta_hip_reach_field[_dev] and
  * fiesta_hip_reach_paths[_dev] came later without a new number, and so did fiesta_hip_cluster_voxels[_dev],
- * fiesta_hip_view_coverage[_dev] and fiesta_hip_reach_matrix[_dev]: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev] and fiesta_hip_site_tour[_dev]: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -640,6 +640,76 @@ int fiesta_hip_reach_matrix(fiesta_hip_map *m, const int32_t lo[3], const int32_
 int fiesta_hip_reach_matrix_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *sources_dev, int64_t n_sources,
                                 const int32_t *targets_dev, int64_t n_targets, double min_clearance, int32_t connectivity, int32_t flags,
                                 int32_t max_fields, const fiesta_hip_reach_matrix_result *result, fiesta_hip_reach_matrix_info *info);
+
+/* ---- site tour: the order in which to visit the sites of a cost matrix, a restart-parallel local search on the device ----
+ * What an exploration planner decides after fiesta_hip_reach_matrix: which site to fly to next and in which order to take the
+ * rest.  Given a SYMMETRIC cost matrix and a start site, the call returns the order in which to visit every site the start can
+ * reach, minimising the summed leg cost, as an open path from the start or (FIESTA_HIP_TOUR_CLOSED) a closed tour back to it.
+ * No voxel is read: the call is the same on array-mode and hash-block maps.  No reference counterpart.  fiesta_hip_version() is
+ * still 101: detect these two calls by symbol lookup.  Every number is an integer; fiesta_amd.tour_model is the definition.
+ * Inputs: cost, n x n int32, row-major with leading dimension ld >= n; 1 <= n <= FIESTA_HIP_TOUR_MAX_SITES; start, a site; flags,
+ *   FIESTA_HIP_TOUR_CLOSED or 0; restarts R, 1 <= R <= FIESTA_HIP_TOUR_MAX_RESTARTS; seed; max_moves, the applied moves a restart
+ *   may make (0: 8 * m).
+ * Sites: an entry c is a CONNECTION iff 0 <= c < INT32_MAX (the reach matrix's convention: -1 is an unusable site, INT32_MAX is
+ *   traversable but not reached).  Site j is VISITED iff j == start or cost[start][j] is a connection; every other site is
+ *   SKIPPED.  The m visited sites in ascending site index, with the start moved to the front, are the LOCAL indices 0 .. m - 1.
+ *   Among visited sites every pair must be a connection and cost[a][b] must equal cost[b][a]; the diagonal is ignored.  A
+ *   violation is FIESTA_HIP_ERR_INVALID, found on the device before any search, and nothing is written.  (A square reach matrix
+ *   always meets both: one connected component is mutually reachable, and moves are symmetric.)
+ * Initial tour of restart r, in local indices: r = 0 is nearest neighbour from index 0 (append the unvisited index with the least
+ *   cost from the last one, ties to the lowest index).  r >= 1: t = [0, 1, .., m - 1]; for k = m - 1 down to 2:
+ *   j = 1 + rnd(seed, r, k) % k, swap t[k] and t[j]; rnd(seed, r, k) = mix(mix(seed + r * 0x9E3779B97F4A7C15) + k) in uint64
+ *   arithmetic, mix(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31.
+ * Local search, best improvement, lengths and deltas in int64: an iteration evaluates every move of the current tour and applies
+ *   the one with the most negative delta, ties to the lowest key (type, i, x) compared lexicographically; it stops when no move
+ *   has delta < 0, or -- capped -- when one has and max_moves moves were applied already.  C(a, b): the cost between the sites at
+ *   tour positions a and b; position m is position 0 of a closed tour; in an open tour it does not exist and every term that
+ *   names it is dropped.
+ *   type 0, 2-opt(i, j = x), 1 <= i < j <= m - 1: reverses t[i..j];
+ *     delta = C(i-1, j) - C(i-1, i) + C(i, j+1) - C(j, j+1).
+ *   type L = 1, 2, 3, Or-opt(i, p = x): the segment t[i..e], e = i + L - 1, 1 <= i, e <= m - 1, moves, keeping its orientation, to
+ *     directly after position p of the current tour; p = 0 .. m - 1 but not i - 1 <= p <= e;
+ *     delta = [C(i-1, e+1) - C(i-1, i) - C(e, e+1)] + [C(p, i) + C(e, p+1) - C(p, p+1)].
+ *   The length is an integer and only falls, so the search ends.  The best restart has the least final length, ties to the lowest r.
+ * Outputs (every pointer nullable): order[n], the site indices in tour order, the start first: m entries, then -1; site_status[n]:
+ *   FIESTA_HIP_TOUR_SITE_VISITED / _SKIPPED; leg_cost[n]: the cost of arriving at order[k] -- leg_cost[0] is 0 for an open tour and
+ *   the closing leg for a closed one -- and -1 past the tour; restart_length[R]: every restart's final length.  info (a HOST
+ *   struct in both variants, nullable): n_visited = m, the best restart and its length, nn_length (restart 0 before any move),
+ *   moves (applied, summed over the restarts) and capped (the restarts stopped by max_moves).  With m <= 2 there is no move and
+ *   nothing to search; the call succeeds.  Every output has the same bits for any launch shape, and the bits of
+ *   fiesta_amd.tour_model.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): cost NULL, n outside 1 .. 512, start outside
+ *   0 .. n - 1, ld < n, R outside 1 .. 4096, unknown flag bits, max_moves < 0.  The scratch memory (the compact matrix of the visited
+ *   sites, the restarts' tours and lengths) belongs to the map: grown on demand, freed by fiesta_hip_destroy, touched by no other
+ *   call; the field that fiesta_hip_reach_paths RETAINS is left alone.
+ * fiesta_hip_site_tour      host arrays; stages, runs, synchronises, copies back.
+ * fiesta_hip_site_tour_dev  cost and the arrays the result struct names are device pointers -- the matrix is read where
+ *                           fiesta_hip_reach_matrix_dev left it, no copy goes through the host; writes exactly n entries of order,
+ *                           site_status and leg_cost and R of restart_length.  Synchronises with the map's stream: m and the two
+ *                           error words are read back before the search is launched. */
+#define FIESTA_HIP_TOUR_MAX_SITES 512
+#define FIESTA_HIP_TOUR_MAX_RESTARTS 4096
+#define FIESTA_HIP_TOUR_CLOSED 1
+#define FIESTA_HIP_TOUR_SITE_VISITED 0
+#define FIESTA_HIP_TOUR_SITE_SKIPPED 1
+typedef struct fiesta_hip_tour_result { /* every pointer nullable */
+  int32_t *order;                       /* n: site indices in tour order, then -1 */
+  int32_t *site_status;                 /* n: FIESTA_HIP_TOUR_SITE_* */
+  int32_t *leg_cost;                    /* n: the cost of arriving at order[k], then -1 */
+  int64_t *restart_length;              /* R: the final length of every restart */
+} fiesta_hip_tour_result;
+typedef struct fiesta_hip_tour_info {
+  int32_t n_visited;    /* m */
+  int32_t best_restart; /* least final length, ties to the lowest r */
+  int64_t length;       /* of the returned tour */
+  int64_t nn_length;    /* restart 0 before any move */
+  int64_t moves;        /* applied, over all restarts */
+  int64_t capped;       /* restarts stopped by max_moves */
+} fiesta_hip_tour_info;
+int fiesta_hip_site_tour(fiesta_hip_map *m, const int32_t *cost, int32_t n, int64_t ld, int32_t start, int32_t flags, int32_t restarts,
+                         uint64_t seed, int32_t max_moves, const fiesta_hip_tour_result *result, fiesta_hip_tour_info *info);
+int fiesta_hip_site_tour_dev(fiesta_hip_map *m, const int32_t *cost_dev, int32_t n, int64_t ld, int32_t start, int32_t flags, int32_t restarts,
+                             uint64_t seed, int32_t max_moves, const fiesta_hip_tour_result *result, fiesta_hip_tour_info *info);
 
 /* ---- reach paths: the paths themselves, extracted from the cost-to-go field on the device ----
  * The last step of the chain frontier voxels -> reachability -> paths -> path cost: fiesta_hip_reach_field says which targets the

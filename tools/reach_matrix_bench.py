@@ -36,21 +36,11 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 INF = 2 ** 31 - 1
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--grid", type=int, default=512, help="a multiple of 32 (a rehearsal at a small size)")
-    ap.add_argument("--obstacles", type=int, default=50000)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--caps", type=int, nargs="+", default=[32, 64], help="site counts")
-    ap.add_argument("--split", type=int, default=16, help="grid on which large frontier clusters are cut, voxels")
-    ap.add_argument("--out", default=None, help="directory for reach_matrix_partial<grid>.json")
-    args = ap.parse_args()
-    import torch
+def scene_and_sites(G, obstacles, split):
+    """the map, the robot, the box and the sites of the docstring (also tools/tour_bench.py's): (m, robot, lo, hi, frontier voxels,
+    unsplit cluster count, the clusters in order of cost, the sites)"""
     from reach_bench import build_partial
-    dev = torch.device("cuda", 0)
-    G = args.grid
-    m, _ = build_partial(G, int(round(args.obstacles * (G / 512.0) ** 3)))
+    m, _ = build_partial(G, int(round(obstacles * (G / 512.0) ** 3)))
     f = m.download_field(("d2", "occ"))
     obs, occ = (f["d2"] >= 0).reshape(m.grid_size), f["occ"].reshape(m.grid_size) != 0
     c0 = max(G // 2 - 32, 0)                       # (the nearest free voxel lies well inside the central 64^3)
@@ -65,9 +55,26 @@ def main():
     key = m.ReachField(robot, lo, hi, targets=fv, want_cost=False)["target_cost"]
     unsplit = m.ClusterVoxels(fv, connectivity=26, min_size=5)["n_clusters"]
     # (the cluster call sees coordinates only: one voxel of room per grid plane crossed makes the two sides of a plane non-adjacent)
-    cl = m.ClusterVoxels(np.ascontiguousarray(fv + fv // args.split), key=key, connectivity=26, min_size=5)
+    cl = m.ClusterVoxels(np.ascontiguousarray(fv + fv // split), key=key, connectivity=26, min_size=5)
     order = [k for k in np.lexsort((np.arange(len(cl["key_min"])), cl["key_min"])) if cl["key_argmin"][k] >= 0]
     all_sites = np.concatenate([robot, fv[[int(cl["key_argmin"][k]) for k in order]]]).astype(np.int32)
+    return m, robot, lo, hi, fv, unsplit, order, all_sites
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", type=int, default=512, help="a multiple of 32 (a rehearsal at a small size)")
+    ap.add_argument("--obstacles", type=int, default=50000)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--caps", type=int, nargs="+", default=[32, 64], help="site counts")
+    ap.add_argument("--split", type=int, default=16, help="grid on which large frontier clusters are cut, voxels")
+    ap.add_argument("--out", default=None, help="directory for reach_matrix_partial<grid>.json")
+    args = ap.parse_args()
+    import torch
+    dev = torch.device("cuda", 0)
+    G = args.grid
+    m, robot, lo, hi, fv, unsplit, order, all_sites = scene_and_sites(G, args.obstacles, args.split)
 
     def timed_in_turn(fns):
         """p50 per function; inside every repetition each function runs once, in order"""
