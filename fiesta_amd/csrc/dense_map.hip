@@ -1544,34 +1544,17 @@ bool DenseMap::run_bulk(fiesta_hip_stats *st, int margin, bool *exact) {
 // ---- the cell transform (nn_core.hpp / nn_kernels.hpp): the same fixed point for a sparse obstacle set ----------------------
 // Applies to maps, and to the shards of any grid, whose region -- the array, a shard's array plus margin -- stays within
 // nn::kRegionMax voxels per axis (beyond 1024 the sites are stored modulo 1024, as the voxel words of such grids are).  Whether
-// it is worth trying: the obstacle density must be in the range where every cell finds an obstacle within its search window and
-// lists stay short (measured on scatter scenes, profiles/r05h_density_range.json: 8e-5 ... 2.5e-3 of the voxels; config 2's
-// scene is 3.7e-4), it must not have failed at about this obstacle count, and it must not have been slower than the envelope passes.
+// it is worth trying is cells_verdict's to say (engine_choice.hpp); the effects of its answer are here.
 bool DenseMap::cells_wanted() {
   const Geom &g = g_;
-  if (update_engine_ == 4 || g.nx > nn::kRegionMax || g.ny > nn::kRegionMax || g.nz > nn::kRegionMax) return false;
-  if (update_engine_ == 5) return true;
-  const long long nocc = (long long)h_counters_[C_NOCC];
-  // (measured with the cells that get no list served one by one, profiles/r06_density_range.json: 7.5e-5 -- 0.36 against 0.57 ms on
-  //  the envelope passes; 5.2e-5 -- two cells scan every site, 0.89 against 0.56; 2.5e-3 -- 0.74 against 0.98; 3.7e-3 -- 1.14 against 1.04)
-  if (nocc * 15000 < g.n || nocc * 400 > g.n) {
-    notes_ |= FIESTA_HIP_NOTE_DENSITY;
-    return false;
-  }
-  // a failed attempt (a cell without a list: ~0.2 ms lost before the envelope passes take over) is not repeated at once: the
-  // next 8, 16, ... 256 eligible updates go straight to the envelope passes, then it is tried again -- a scene that cannot be
-  // served costs 1 % in the long run, one unlucky cell in a scene that can does not switch the transform off for good
-  if (nn_skip_ > 0) {
-    --nn_skip_;
-    notes_ |= FIESTA_HIP_NOTE_CELLS_BACKOFF;
-    return false;
-  }
-  if (nn_last_ms_ > 0 && ft_last_ms_ > 0 && nn_last_ms_ > ft_last_ms_ && std::llabs(nocc - nn_last_nocc_) * 4 <= nn_last_nocc_) {
-    notes_ |= FIESTA_HIP_NOTE_CELLS_BACKOFF;
-    return false;
-  }
-  return true;
+  const CellsVerdict v = cells_verdict(update_engine_, g.nx <= nn::kRegionMax && g.ny <= nn::kRegionMax && g.nz <= nn::kRegionMax,
+                                       (long long)h_counters_[C_NOCC], g.n, nn_skip_, nn_last_ms_, ft_last_ms_, nn_last_nocc_);
+  if (v == CellsVerdict::kDensity) notes_ |= FIESTA_HIP_NOTE_DENSITY;
+  if (v == CellsVerdict::kSkipCount) --nn_skip_;
+  if (v == CellsVerdict::kSkipCount || v == CellsVerdict::kLastTimings) notes_ |= FIESTA_HIP_NOTE_CELLS_BACKOFF;
+  return v == CellsVerdict::kWanted;
 }
+void DenseMap::cells_back_off() { nn_fail_streak_ = std::min(nn_fail_streak_ + 1, 6), nn_skip_ = 4 << nn_fail_streak_; }
 
 // The cell transform of this map's array.  Unsharded: the region is the array, the bitmap the map's own.  Sharded: the
 // region is the array grown by `margin` (+ what a search window adds to a distance: a cell's window reaches
@@ -1787,7 +1770,7 @@ bool DenseMap::masked_eligible(unsigned long long ni, unsigned long long nd) {
 // sites, the transform into the side buffer, the certificate, a first chain of repair iterations -- and read back ONCE; further
 // chains only if the repair has not settled.  Returns false with the field untouched (the side buffer is simply dropped) if the
 // repair list outgrew its buffer: the caller's frontier rounds then serve the update.
-bool DenseMap::run_masked(fiesta_hip_stats *st, std::chrono::steady_clock::time_point h0) {
+bool DenseMap::run_masked(fiesta_hip_stats *st) {
   const Geom &g = g_;
   const int ncx = (g.nx + 7) / 8, ncy = (g.ny + 7) / 8, ncz = (g.nz + 7) / 8;
   const int64_t ncells = (int64_t)ncx * ncy * ncz, nquads = (int64_t)ncx * ncy * g.nzw;
@@ -1932,7 +1915,7 @@ bool DenseMap::run_masked(fiesta_hip_stats *st, std::chrono::steady_clock::time_
     mask_seg_cap_ *= 2;  // a scene with more walks than the list was sized for: once more, with room
     tr_occ_ = nullptr, tr_out_ = nullptr, tr_cellobs_ = nullptr;
     reset_stats_counters(/*lists=*/true);
-    return run_masked(st, h0);
+    return run_masked(st);
   }
   // the repair: further chains until an iteration changes nothing
   int total_iters = 0;
@@ -1985,30 +1968,18 @@ bool DenseMap::run_masked(fiesta_hip_stats *st, std::chrono::steady_clock::time_
     st->mask_quads = (int64_t)h_mask_ctr_[MC_QUADS];
     st->relax_ms = (double)m1 + m2 + m3 + mc + mr;
     st->relax_launches = 3 + 3 + 2 * total_iters;
-    st->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
   }
   return true;
 }
 
-// The cost half of the engine choice, from the measured crossover (profiles/r03a_delta_sweep.json: C2's map, both scenes,
-// deltas 100 ... 50 k on either engine).  The transform is one fixed sweep, ~6 ps per voxel of the grid; the rounds cost a
-// fixed ~0.8 ms of launches and scans on a 512^3 map plus ~0.3 ns per voxel whose obstacle changes, about
-// delta x (voxels per obstacle) of them.  In voxel units: bulk pays iff  n <= 1.3e8 + 50 x (estimated updated voxels) --
-// on every grid up to 512^3 that is always (measured: 0.80 vs 0.93 ms at a delta of 100), on a 1024^3 shard from a delta of
-// ~2 % of the obstacles.  FIESTA_HIP_BULK_RATIO (a fraction of the occupied voxels) overrides the model.
-bool DenseMap::bulk_pays(double delta, double nocc, double n) const { return bulk_pays_model(delta, nocc, n, ft_last_ms_, bulk_ratio_); }
-// (static: the sharded driver decides from numbers every rank has seen -- the gathered maxima -- never from one rank's own)
-bool DenseMap::bulk_pays_model(double delta, double nocc, double n, double ft_last_ms, double bulk_ratio) {
-  if (bulk_ratio >= 0) return delta >= bulk_ratio * std::max(nocc, 1.0);
-  const double updated = std::min(n, delta * n / std::max(nocc, 1.0));
-  // a scene of deep deques (surfaces: the transform takes twice the sweep's nominal time) and a handful of voxels: the
-  // rounds win by a few percent (measured: 1.38 vs 1.53 ms at a delta of 100, 2.1 vs 1.5 ms at 500)
-  if (delta <= 128 && ft_last_ms > 1.25 * n * 6e-9) return false;
-  return n <= 1.3e8 + 50.0 * updated;
-}
+struct HostMs {  // fiesta_hip_stats.host_ms: the wall clock from here to the end of the scope, whichever way it is left
+  fiesta_hip_stats *st;
+  std::chrono::steady_clock::time_point h0 = std::chrono::steady_clock::now();
+  ~HostMs() { if (st) st->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count(); }
+};
 
 // After a successful bulk transform: the queues are consumed, timings and counters reported.
-void DenseMap::bulk_finish(fiesta_hip_stats *st, std::chrono::steady_clock::time_point h0, bool cells, bool published) {
+void DenseMap::bulk_finish(fiesta_hip_stats *st, bool cells, bool published) {
   static_assert(C_DELETE == C_INSERT + 1, "counter layout");
   nn_clean_ = false;
   if (published) {
@@ -2053,7 +2024,6 @@ void DenseMap::bulk_finish(fiesta_hip_stats *st, std::chrono::steady_clock::time
       st->ft_overflow[0] = (int64_t)h_counters_[C_FT_OVF0], st->ft_overflow[3] = (int64_t)h_counters_[C_FT_OVF0 + 3];
     }
     st->relax_ms = (double)m1 + m2 + m3;
-    st->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
   }
   if (cells && published && !(st && st->nn_incremental)) nn_last_brute_ = (long long)h_counters_[C_NN_BRUTE];
   if (timed) {
@@ -2089,8 +2059,7 @@ bool DenseMap::bulk_try(fiesta_hip_stats *st, int margin, bool *exact) {
       if (st) st->ft_max_d2 = (int64_t)h_counters_[C_FT_MAXD2];
       return true;
     }
-    nn_fail_streak_ = std::min(nn_fail_streak_ + 1, 6);
-    nn_skip_ = 4 << nn_fail_streak_;
+    cells_back_off();
     const int64_t failed = (int64_t)h_counters_[C_NN_FAILED];
     reset_stats_counters();
     if (st) {
@@ -2106,7 +2075,8 @@ void DenseMap::bulk_commit(fiesta_hip_stats *st) {
   // the side buffer BECOMES the field (both hold exactly n words; every user of the field takes the pointer at call time,
   // in stream order behind the transform): a copy would move 4 B per voxel once more
   if (!ft_in_place_) std::swap(coc_, ft_out_.p);
-  bulk_finish(st, std::chrono::steady_clock::now(), tried_cells_);
+  HostMs host_ms{st};
+  bulk_finish(st, tried_cells_);
 }
 void DenseMap::bulk_probe(unsigned long long *ni, unsigned long long *nd, long long *nocc, bool *eligible) {
   use_device();
@@ -2160,13 +2130,82 @@ bool DenseMap::run_levels(fiesta_hip_stats *st, unsigned long long ni, unsigned 
   return true;
 }
 
+// The transforms of a fully observed map: incremental cell transform, cell transform, envelope passes.  true: the update is served.
+bool DenseMap::serve_by_transform(fiesta_hip_stats *st, unsigned long long ni, unsigned long long nd, bool nn_was_clean, bool nn_was_valid) {
+  // (an unsharded map's transform cannot fail to serve the update -- the envelope passes stand behind the cell transform --
+  //  so the two queue lengths go in the same launch as the statistics)
+  // a sparse obstacle set: the cell transform first (nn_kernels.hpp).  A cell without a list fails it -- k_nn_fill then
+  // wrote nothing -- and the envelope passes below serve the update; the obstacle count is remembered and not retried.
+  const bool want_cells = cells_wanted();
+  // (the last update was a cell transform that cleaned up behind itself and nothing has touched the counters since: no
+  //  reset launch ahead of this one -- its fill will clear the queue lengths at its end)
+  const bool lean = want_cells && nn_was_clean;
+  if (lean) {
+    queues_zeroed_ = false;
+    ft_counters_clean_ = true;
+  } else {
+    queues_zeroed_ = !g_.sharded && g_.nx <= 2048 && g_.ny <= 2048 && g_.nz <= 2048;
+    reset_stats_counters(/*lists=*/true, queues_zeroed_);
+  }
+  // the lists of the last update are still valid and little has changed: only the cells a changed voxel can reach are redone
+  // (a voxel dirties the ~(2 x reach + 1)^3 cells around it: worth it while that is a fraction of the map)
+  const int64_t ncells8 = (int64_t)((g_.nx + 7) / 8) * ((g_.ny + 7) / 8) * ((g_.nz + 7) / 8);
+  if (want_cells && nn_was_valid && !g_.wrap && (int64_t)(ni + nd) * 180 <= ncells8 / 2 && run_cells(st, 0, /*publish=*/true, /*incremental=*/true, ni, nd)) {
+    bulk_finish(st, /*cells=*/true, /*published=*/true);
+    if (h_counters_[C_NN_FAILED] == 0) {
+      nn_fail_streak_ = 0;
+      nn_valid_ = true;
+      return true;
+    }
+    // more dirty cells than the list holds, or a cell that lost its last obstacle in reach: the full transform, from scratch
+    notes_ |= FIESTA_HIP_NOTE_INCREMENTAL_REDONE;
+    FIESTA_HIP_CHECK(hipMemsetAsync(nn_dirty_flag_.p, 0, nn_dirty_flag_.cap * sizeof(uint32_t), stream_));
+    if (st) memset(&st->cells, 0, sizeof(st->cells)), st->nn_incremental = 0;
+    restart_attempt();
+  }
+  if (want_cells && run_cells(st, 0, /*publish=*/true)) {
+    bulk_finish(st, /*cells=*/true, /*published=*/true);
+    if (h_counters_[C_NN_FAILED] == 0) {
+      nn_fail_streak_ = 0;
+      // A cell served against every site (nothing within its widest window) records a reach its winners lie beyond: a
+      // change out there would not dirty it.  The lists are trusted by the next update only if no such cell stands.
+      nn_valid_ = !g_.sharded && h_counters_[C_NN_SPARSE] == 0;
+      return true;
+    }
+    cells_back_off();
+    notes_ |= FIESTA_HIP_NOTE_CELLS_FAILED;
+    const int64_t failed = (int64_t)h_counters_[C_NN_FAILED];
+    if (st) {
+      memset(&st->cells, 0, sizeof(st->cells));
+      st->nn_failed = failed;
+    }
+    restart_attempt();
+  }
+  bool exact = true;
+  if (run_bulk(st, 0, &exact)) {
+    bulk_finish(st);
+    return true;
+  }
+  if (queues_zeroed_) {  // (cannot happen: see above -- but the engines below read the queue lengths on the device)
+    h_counters_[C_INSERT] = ni, h_counters_[C_DELETE] = nd;
+    FIESTA_HIP_CHECK(hipMemcpyAsync(&counters_[C_INSERT], &h_counters_[C_INSERT], 2 * sizeof(unsigned long long), hipMemcpyHostToDevice, stream_));
+    queues_zeroed_ = false;
+  }
+  return false;
+}
+
+void DenseMap::restart_attempt() {  // an engine gave the update back: the next one starts the update's clock and statistics over
+  FIESTA_HIP_CHECK(hipEventRecord(ev0_, stream_));
+  reset_stats_counters(/*lists=*/true);
+}
+
 void DenseMap::update_esdf(fiesta_hip_stats *st, bool seed_only) {  // UpdateESDF (src/ESDFMap.cpp:273-398)
   use_device();
   notes_ = 0;
   const bool nn_was_clean = nn_clean_;  // (only a cell transform that reports for itself sets it again: bulk_finish)
   nn_clean_ = false;
   const bool nn_was_valid = nn_valid_;  // (set again by a cell transform that succeeds on the map's own field)
-  const auto h0 = std::chrono::steady_clock::now();
+  HostMs host_ms{st};
   if (host_counts_valid_) {  // (what UpdateOccupancy read last: nothing else changes these four)
     for (int k = 0; k < 4; ++k) h_counters_[C_INSERT + k] = host_counts_[k];
   } else {
@@ -2184,134 +2223,46 @@ void DenseMap::update_esdf(fiesta_hip_stats *st, bool seed_only) {  // UpdateESD
     st->observed_voxels = (int64_t)h_counters_[C_OBSERVED];
     st->occupied_voxels = (int64_t)h_counters_[C_NOCC];
   }
-  if (ni == 0 && nd == 0 && !seed_only) {
-    if (st) st->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
-    return;
-  }
+  if (ni == 0 && nd == 0 && !seed_only) return;
   nn_valid_ = false;
   ++field_epoch_;  // (the host-side brick cache of the scalar queries is stale from here on; an update without work leaves it valid)
   ++epoch_;
   TileGrid tg{tx_, ty_, ntx_, nty_, ntz_};
   FIESTA_HIP_CHECK(hipEventRecord(ev0_, stream_));
-  {  // why this update will take the path it takes (fiesta_hip_stats.path_notes): the standing conditions here, the rest as they bite
-    const long long owned = (long long)(g_.ox1 - g_.ox0 + 1) * (g_.oy1 - g_.oy0 + 1) * (g_.oz1 - g_.oz0 + 1);
-    if ((long long)h_counters_[C_OBSERVED] != owned) notes_ |= FIESTA_HIP_NOTE_PARTLY_OBSERVED;
-    if (g_.sharded) notes_ |= FIESTA_HIP_NOTE_SHARDED;
-    if (g_.wrap) notes_ |= FIESTA_HIP_NOTE_ID_WRAP;
-    if (update_engine_ != 0) notes_ |= FIESTA_HIP_NOTE_ENGINE_PINNED;
-  }
   const bool full_window = g_.full_window();
   // (a map that held no obstacle before this update has no history: cleared BEFORE this update's own window is recorded --
   //  the first obstacles inserted under a partial window on an empty map must leave the flag set)
   if (win_dirty_ && !g_.sharded && (long long)h_counters_[C_NOCC] - (long long)ni + (long long)nd <= 0) win_dirty_ = false;
   if (!full_window) win_dirty_ = true, notes_ |= FIESTA_HIP_NOTE_PARTIAL_WINDOW;  // (see bulk_eligible)
   else if (win_dirty_) notes_ |= FIESTA_HIP_NOTE_WINDOW_HISTORY;
-  // Engine choice.  The bulk transform costs one fixed sweep over the grid; the frontier rounds cost in proportion to
-  // the voxels whose closest obstacle changes, roughly (inserts + deletes) x (grid / occupied voxels).  The level engine
-  // (level_kernels.hpp) takes every update of a few thousand voxels -- a sensor frame -- that the transform does not, and,
-  // if asked for (update_engine 3), every update its lists can hold; one that outgrows them is finished by the rounds.
-  bool levels_fell_back = false;
-  // On a map the transform's gate is open for -- every voxel observed, no history of partial windows -- the reference's
-  // field is the exact transform whatever the order (section 3c): the level engine has nothing to add there, and a delete on
-  // such a map orphans a whole Voronoi cell (10^5 voxels behind a surface), which is the rounds' or the transform's work.
-  const bool gate_open = !seed_only && !g_.sharded && bulk_eligible(ni, nd);
-  // (the inserts ARE level 0: more of them than one work-group carries and the level engine would only hand the update on)
-  const bool try_levels = !seed_only && !g_.sharded && !g_.wrap && update_engine_ != 1 &&
-                          (update_engine_ == 3 || (!gate_open && ni + nd <= (unsigned long long)small_update_ && ni <= (unsigned long long)LevelEngine::kInsertCap));
-  const bool try_bulk = gate_open && (bulk_pinned() || bulk_pays((double)(ni + nd), (double)(long long)h_counters_[C_NOCC], (double)g_.n));
-  if (gate_open && !try_bulk) notes_ |= FIESTA_HIP_NOTE_SMALL_DELTA;
-  if (!gate_open && !seed_only && (long long)h_counters_[C_OBSERVED] < g_.n && !bulk_pinned() &&
-      !bulk_pays((double)(ni + nd), (double)(long long)h_counters_[C_NOCC], (double)g_.n))
-    notes_ |= FIESTA_HIP_NOTE_SMALL_DELTA;
-  bool counters_reset = false;
-  // A partially observed map (every map a sensor builds): a delta too large for the level engine goes to the masked transform
-  // (mask_kernels.hpp) where the map's history allows it -- a fixed sweep like the other transforms -- instead of the rounds.
-  if (!seed_only && !gate_open && !try_bulk && (long long)h_counters_[C_OBSERVED] < g_.n &&
-      (update_engine_ == 6 || (!try_levels && (update_engine_ == 0 || bulk_pinned()) &&
-                               bulk_pays((double)(ni + nd), (double)(long long)h_counters_[C_NOCC], (double)g_.n))) &&
-      masked_eligible(ni, nd)) {
+  // Engine choice (engine_choice.hpp): the facts, the plan, then the engines in the plan's order, each handing on what it cannot serve
+  UpdateFacts f{};
+  f.ni = ni, f.nd = nd, f.nocc = (long long)h_counters_[C_NOCC], f.observed = (long long)h_counters_[C_OBSERVED];
+  f.owned = (long long)(g_.ox1 - g_.ox0 + 1) * (g_.oy1 - g_.oy0 + 1) * (g_.oz1 - g_.oz0 + 1), f.n = g_.n;
+  f.engine = update_engine_, f.seed_only = seed_only, f.sharded = g_.sharded, f.wrap = g_.wrap;
+  f.gate_open = !seed_only && !g_.sharded && bulk_eligible(ni, nd);
+  f.small_update = small_update_, f.insert_cap = LevelEngine::kInsertCap, f.ft_last_ms = ft_last_ms_, f.bulk_ratio = bulk_ratio_;
+  const EnginePlan plan = choose_engines(f);
+  notes_ |= plan.notes;
+  bool counters_reset = false, levels_fell_back = false;
+  if (plan.ask_masked && masked_eligible(ni, nd)) {
     reset_stats_counters(/*lists=*/true);
     counters_reset = true;
-    if (run_masked(st, h0)) return;
+    if (run_masked(st)) return;
     notes_ |= FIESTA_HIP_NOTE_MASKED_GAVE_UP;
     if (st) {
       const fiesta_hip_stats keep = *st;
       memset(st, 0, sizeof(*st));
       st->inserted = keep.inserted, st->deleted = keep.deleted, st->observed_voxels = keep.observed_voxels, st->occupied_voxels = keep.occupied_voxels;
     }
-    FIESTA_HIP_CHECK(hipEventRecord(ev0_, stream_));
-    reset_stats_counters(/*lists=*/true);
+    restart_attempt();
   }
-  if (try_bulk) {
-    // (an unsharded map's transform cannot fail to serve the update -- the envelope passes stand behind the cell transform --
-    //  so the two queue lengths go in the same launch as the statistics)
-    // a sparse obstacle set: the cell transform first (nn_kernels.hpp).  A cell without a list fails it -- k_nn_fill then
-    // wrote nothing -- and the envelope passes below serve the update; the obstacle count is remembered and not retried.
-    const bool want_cells = cells_wanted();
-    // (the last update was a cell transform that cleaned up behind itself and nothing has touched the counters since: no
-    //  reset launch ahead of this one -- its fill will clear the queue lengths at its end)
-    const bool lean = want_cells && nn_was_clean;
-    if (lean) {
-      queues_zeroed_ = false;
-      ft_counters_clean_ = true;
-    } else {
-      queues_zeroed_ = !g_.sharded && g_.nx <= 2048 && g_.ny <= 2048 && g_.nz <= 2048;
-      reset_stats_counters(/*lists=*/true, queues_zeroed_);
-    }
+  if (plan.try_bulk) {
+    if (serve_by_transform(st, ni, nd, nn_was_clean, nn_was_valid)) return;
     counters_reset = true;
-    // the lists of the last update are still valid and little has changed: only the cells a changed voxel can reach are redone
-    // (a voxel dirties the ~(2 x reach + 1)^3 cells around it: worth it while that is a fraction of the map)
-    const int64_t ncells8 = (int64_t)((g_.nx + 7) / 8) * ((g_.ny + 7) / 8) * ((g_.nz + 7) / 8);
-    if (want_cells && nn_was_valid && !g_.wrap && (int64_t)(ni + nd) * 180 <= ncells8 / 2 && run_cells(st, 0, /*publish=*/true, /*incremental=*/true, ni, nd)) {
-      bulk_finish(st, h0, /*cells=*/true, /*published=*/true);
-      if (h_counters_[C_NN_FAILED] == 0) {
-        nn_fail_streak_ = 0;
-        nn_valid_ = true;
-        return;
-      }
-      // more dirty cells than the list holds, or a cell that lost its last obstacle in reach: the full transform, from scratch
-      notes_ |= FIESTA_HIP_NOTE_INCREMENTAL_REDONE;
-      FIESTA_HIP_CHECK(hipMemsetAsync(nn_dirty_flag_.p, 0, nn_dirty_flag_.cap * sizeof(uint32_t), stream_));
-      if (st) memset(&st->cells, 0, sizeof(st->cells)), st->nn_incremental = 0;
-      FIESTA_HIP_CHECK(hipEventRecord(ev0_, stream_));
-      reset_stats_counters(/*lists=*/true);
-    }
-    if (want_cells && run_cells(st, 0, /*publish=*/true)) {
-      bulk_finish(st, h0, /*cells=*/true, /*published=*/true);
-      if (h_counters_[C_NN_FAILED] == 0) {
-        nn_fail_streak_ = 0;
-        // A cell served against every site (nothing within its widest window) records a reach its winners lie beyond: a
-        // change out there would not dirty it.  The lists are trusted by the next update only if no such cell stands.
-        nn_valid_ = !g_.sharded && h_counters_[C_NN_SPARSE] == 0;
-        return;
-      }
-      nn_fail_streak_ = std::min(nn_fail_streak_ + 1, 6);
-      nn_skip_ = 4 << nn_fail_streak_;
-      notes_ |= FIESTA_HIP_NOTE_CELLS_FAILED;
-      const int64_t failed = (int64_t)h_counters_[C_NN_FAILED];
-      if (st) {
-        memset(&st->cells, 0, sizeof(st->cells));
-        st->nn_failed = failed;
-      }
-      FIESTA_HIP_CHECK(hipEventRecord(ev0_, stream_));
-      reset_stats_counters(/*lists=*/true);
-    }
-    bool exact = true;
-    if (run_bulk(st, 0, &exact)) {
-      bulk_finish(st, h0);
-      return;
-    }
-    if (queues_zeroed_) {  // (cannot happen: see above -- but the engines below read the queue lengths on the device)
-      h_counters_[C_INSERT] = ni, h_counters_[C_DELETE] = nd;
-      FIESTA_HIP_CHECK(hipMemcpyAsync(&counters_[C_INSERT], &h_counters_[C_INSERT], 2 * sizeof(unsigned long long), hipMemcpyHostToDevice, stream_));
-      queues_zeroed_ = false;
-    }
   }
-  if (try_levels) {  // (the level engine keeps its statistics in its own control block: no counter reset on its path)
-    if (run_levels(st, ni, nd)) {
-      if (st) st->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
-      return;
-    }
+  if (plan.try_levels) {  // (the level engine keeps its statistics in its own control block: no counter reset on its path)
+    if (run_levels(st, ni, nd)) return;
     levels_fell_back = true;
     notes_ |= FIESTA_HIP_NOTE_LEVELS_GAVE_UP;
     zero_counters(C_INVALIDATED, C_COUNT - C_INVALIDATED);  // (the tile list is set up: its counters stay)
@@ -2343,7 +2294,6 @@ void DenseMap::update_esdf(fiesta_hip_stats *st, bool seed_only) {  // UpdateESD
   if (g_.sharded) zero_counter(C_REMOTE_DEL);
   if (seed_only) {  // sharded driver: ghost exchange comes next, then relax_pending()
     FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
-    if (st) st->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
     return;
   }
   // a small delta (a depth frame): do not even read how many tiles were seeded, the chain of rounds finds out on the device
@@ -2372,7 +2322,6 @@ void DenseMap::update_esdf(fiesta_hip_stats *st, bool seed_only) {  // UpdateESD
     float ms = 0;
     FIESTA_HIP_CHECK(hipEventElapsedTime(&ms, ev0_, end));
     st->device_ms = ms;
-    st->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
   }
 }
 

@@ -7,6 +7,7 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
+#include "engine_choice.hpp"
 
 namespace fiesta {
 
@@ -237,8 +238,6 @@ class DenseMap {
   int level_trace(uint32_t *out48) const;  // fiesta_hip_level_trace
   void level_tuning(int grid_groups, long long spin_limit);  // fiesta_hip_level_tuning
   void set_alone_in_group(bool alone) { alone_in_group_ = alone; }
-  bool bulk_pays(double delta, double nocc, double n) const;  // is the fixed sweep cheaper than the frontier rounds?
-  static bool bulk_pays_model(double delta, double nocc, double n, double ft_last_ms, double bulk_ratio);
   double ft_last_ms() const { return ft_last_ms_; }
   double bulk_ratio() const { return bulk_ratio_; }
   // continue relaxing tiles that are already flagged (after ghost entries were applied)
@@ -331,12 +330,15 @@ class DenseMap {
   bool run_bulk(fiesta_hip_stats *st, int margin, bool *exact);
   // the masked transform (mask_kernels.hpp): large deltas on partially observed maps
   bool masked_eligible(unsigned long long ni, unsigned long long nd);
-  bool run_masked(fiesta_hip_stats *st, std::chrono::steady_clock::time_point h0);  // false: nothing committed, the rounds serve the update
+  bool run_masked(fiesta_hip_stats *st);  // false: nothing committed, the rounds serve the update
   bool cells_wanted();                  // should this update try the cell transform (nn_kernels.hpp) before the envelope passes?
+  void cells_back_off();                // a cell transform failed: the next 8, 16, ... 256 eligible updates skip it (cells_verdict)
+  bool serve_by_transform(fiesta_hip_stats *st, unsigned long long ni, unsigned long long nd, bool nn_was_clean, bool nn_was_valid);
+  void restart_attempt();               // an engine gave the update back
   // false: not applicable to this map (nothing launched).  incremental: only the cells whose search window holds a voxel of the
   // insert / delete queues get a new list and a new fill (the lists of the last transform must still be valid: nn_valid_)
   bool run_cells(fiesta_hip_stats *st, int margin, bool publish, bool incremental = false, unsigned long long ni = 0, unsigned long long nd = 0);
-  void bulk_finish(fiesta_hip_stats *st, std::chrono::steady_clock::time_point h0, bool cells = false, bool published = false);
+  void bulk_finish(fiesta_hip_stats *st, bool cells = false, bool published = false);
   void reset_stats_counters(bool lists = false, bool queues = false);
   void enable_distance_tracking();
   void collect_stats(fiesta_hip_stats *st);

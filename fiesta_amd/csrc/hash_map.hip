@@ -1275,8 +1275,9 @@ void HashMap::update_esdf(fiesta_hip_stats *st) {  // UpdateESDF (src/ESDFMap.cp
     static_assert(C_LIST2 == C_LIST0 + 2 && C_INVALIDATED == C_LIST2 + 1, "counter layout");
     const auto d00 = std::chrono::steady_clock::now();
     bool levels_fell_back = false;
-    // (the inserts ARE level 0: more of them than one work-group carries and the level engine would only hand the update on)
-    if (update_engine_ != 1 && (update_engine_ == 3 || (ni + nd <= (unsigned long long)small_update_ && ni <= (unsigned long long)LevelEngine::kInsertCap))) {
+    UpdateFacts f{};  // (no transform on this store: only try_levels is read, and the facts it does not read stay zero)
+    f.ni = ni, f.nd = nd, f.engine = update_engine_, f.small_update = small_update_, f.insert_cap = LevelEngine::kInsertCap;
+    if (choose_engines(f).try_levels) {
       // (the level engine keeps its statistics in its own control block: no counter reset, no read-back of counters --
       //  dropped observations are reported from the last value the host saw plus what it clipped itself)
       if (run_levels(st, ni, nd)) {

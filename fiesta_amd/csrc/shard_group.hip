@@ -413,8 +413,8 @@ void ShardGroup::update_esdf(fiesta_hip_stats *st, int32_t *sweeps_out, int64_t 
     // (the cost model per shard: its share of the delta and of the obstacles against the LARGEST shard's array and the
     //  SLOWEST shard's last transform -- all from the gathered table, so every rank computes the same answer)
     const bool want = all && (ni + nd) > 0 &&
-                      (force || DenseMap::bulk_pays_model((double)(ni + nd) / world_, (double)nocc / world_, (double)n_max,
-                                                          (double)ft_ns_max * 1e-6, ratio >= 0 ? (double)ratio * 1e-9 : -1.0));
+                      (force || bulk_pays_model((double)(ni + nd) / world_, (double)nocc / world_, (double)n_max, (double)ft_ns_max * 1e-6,
+                                                ratio >= 0 ? (double)ratio * 1e-9 : -1.0));
     for (int m = margin_; want; m *= 2) {
       std::vector<fiesta_hip_stats> ss(locals_.size());
       for (size_t i = 0; i < locals_.size(); ++i) {
