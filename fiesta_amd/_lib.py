@@ -124,6 +124,17 @@ class ReachPathsResult(C.Structure):
                 ("n_moves", C.c_void_p)]
 
 
+class FreeBoxesResult(C.Structure):
+    """fiesta_hip_free_boxes_result: one array per output of fiesta_hip_free_boxes, every pointer nullable"""
+    _fields_ = [("box", C.c_void_p), ("box_pos", C.c_void_p), ("stop", C.c_void_p), ("volume", C.c_void_p), ("status", C.c_void_p)]
+
+
+class CorridorResult(C.Structure):
+    """fiesta_hip_corridor_result: offsets is required, every other pointer nullable"""
+    _fields_ = [("offsets", C.c_void_p), ("boxes", C.c_void_p), ("boxes_pos", C.c_void_p), ("stop", C.c_void_p), ("entry", C.c_void_p),
+                ("status", C.c_void_p), ("n_chain", C.c_void_p), ("blocked_segment", C.c_void_p), ("blocked_vox", C.c_void_p)]
+
+
 class ClusterResult(C.Structure):
     """fiesta_hip_cluster_result: one array per output of fiesta_hip_cluster_voxels, every pointer nullable"""
     _fields_ = [("label", C.c_void_p), ("size", C.c_void_p), ("root", C.c_void_p), ("box_lo", C.c_void_p), ("box_hi", C.c_void_p),
@@ -268,6 +279,10 @@ def load():
         "fiesta_hip_site_tour_dev": (C.c_int, [vp, vp, i32, i64, i32, i32, i32, C.c_uint64, i32, vp, vp]),
         "fiesta_hip_reach_paths": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
         "fiesta_hip_reach_paths_dev": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
+        "fiesta_hip_free_boxes": (C.c_int, [vp, vp, vp, vp, i64, dbl, i32, i32, vp]),
+        "fiesta_hip_free_boxes_dev": (C.c_int, [vp, vp, vp, vp, i64, dbl, i32, i32, vp]),
+        "fiesta_hip_path_corridor": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i64, vp]),
+        "fiesta_hip_path_corridor_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i64, vp]),
         "fiesta_hip_cluster_voxels": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, i64, vp, vp]),
         "fiesta_hip_cluster_voxels_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, i32, i64, i64, vp, vp]),
         "fiesta_hip_view_coverage": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, vp]),

@@ -7,7 +7,8 @@
 #include <string>
 
 #include "../../include/fiesta_hip.h"
-#include "cluster_kernels.hpp"  // (the nine planner headers: for the calls' argument aggregates; no kernel is used here)
+#include "cluster_kernels.hpp"  // (the ten planner headers: for the calls' argument aggregates; no kernel is used here)
+#include "corridor_kernels.hpp"
 #include "dense_map.hpp"
 #include "frontier_kernels.hpp"
 #include "hash_map.hpp"
@@ -173,6 +174,35 @@ void reach_paths(fiesta_hip_map *m, const fiesta::ReachPathArgs &a) {
   }
   need(m != nullptr, "null map handle");
   on_store(m, [&](auto &s) { s.reach_paths(a); });
+}
+// fiesta_hip_free_boxes and fiesta_hip_path_corridor: none of these errors needs a device, and all are checked before the handle
+// is touched (a host batch: the CSR rules as well)
+constexpr const char *kFreeBoxNames[] = {"free_boxes: result is null", "free_boxes: min_clearance is NaN",
+                                         "free_boxes: lo and hi must both be given or both be null", "free_boxes: max_grow must lie in 0 .. 256",
+                                         "free_boxes: unknown flag bits", "free_boxes: negative count", "free_boxes: seeds is null"};
+constexpr const char *kCorridorNames[] = {"path_corridor: result is null", "path_corridor: min_clearance is NaN",
+                                          "path_corridor: lo and hi must both be given or both be null", "path_corridor: max_grow must lie in 0 .. 256",
+                                          "path_corridor: unknown flag bits", "path_corridor: negative count", "path_corridor: waypoints_vox is null"};
+void corridor(fiesta_hip_map *m, const fiesta::CorridorArgs &a) {
+  const char *const *s = a.paths ? kCorridorNames : kFreeBoxNames;
+  need(a.paths ? a.corridor != nullptr : a.boxes != nullptr, s[0]);
+  if (a.paths) need(a.corridor->offsets != nullptr, "path_corridor: result->offsets is null");
+  need(!std::isnan(a.min_clearance), s[1]);
+  need((a.lo == nullptr) == (a.hi == nullptr), s[2]);
+  need(a.max_grow >= 0 && a.max_grow <= FIESTA_HIP_CORRIDOR_MAX_GROW, s[3]);
+  need((a.flags & ~FIESTA_HIP_CORRIDOR_THROUGH_UNKNOWN) == 0, s[4]);
+  need(a.n_vox >= 0 && a.n_paths >= 0, s[5]);
+  need(a.vox != nullptr || a.n_vox == 0, s[6]);
+  if (a.paths) {
+    need(a.capacity >= 0, "path_corridor: negative capacity");
+    need(a.offsets != nullptr, "path_corridor: offsets is null");
+    if (!a.dev) {
+      need(a.offsets[0] >= 0 && a.offsets[a.n_paths] <= a.n_vox, "path_corridor: offsets must lie in 0 .. n_waypoints");
+      for (int64_t p = 0; p < a.n_paths; ++p) need(a.offsets[p] <= a.offsets[p + 1], "path_corridor: offsets must be non-decreasing");
+    }
+  }
+  need(m != nullptr, "null map handle");
+  on_store(m, [&](auto &st) { st.corridor(a); });
 }
 // none of these errors needs a device
 void cluster_voxels(fiesta_hip_map *m, const fiesta::ClusterArgs &a) {
@@ -595,6 +625,28 @@ int fiesta_hip_reach_paths_dev(fiesta_hip_map *m, const int32_t *cost_dev, const
                                const int32_t *targets_dev, int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span,
                                int64_t capacity, const fiesta_hip_reach_paths_result *result) {
   return guarded([&] { reach_paths(m, {cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, result, true}); });
+}
+int fiesta_hip_free_boxes(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds, int64_t n, double min_clearance,
+                          int32_t max_grow, int32_t flags, const fiesta_hip_free_boxes_result *result) {
+  return guarded([&] { corridor(m, {false, lo, hi, seeds, n, nullptr, 0, min_clearance, max_grow, flags, 0, result, nullptr, false}); });
+}
+int fiesta_hip_free_boxes_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds_dev, int64_t n,
+                              double min_clearance, int32_t max_grow, int32_t flags, const fiesta_hip_free_boxes_result *result) {
+  return guarded([&] { corridor(m, {false, lo, hi, seeds_dev, n, nullptr, 0, min_clearance, max_grow, flags, 0, result, nullptr, true}); });
+}
+int fiesta_hip_path_corridor(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *waypoints_vox, int64_t n_waypoints,
+                             const int64_t *offsets, int64_t n_paths, double min_clearance, int32_t max_grow, int32_t flags,
+                             int64_t capacity, const fiesta_hip_corridor_result *result) {
+  return guarded([&] {
+    corridor(m, {true, lo, hi, waypoints_vox, n_waypoints, offsets, n_paths, min_clearance, max_grow, flags, capacity, nullptr, result, false});
+  });
+}
+int fiesta_hip_path_corridor_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *waypoints_vox_dev,
+                                 int64_t n_waypoints, const int64_t *offsets_dev, int64_t n_paths, double min_clearance, int32_t max_grow,
+                                 int32_t flags, int64_t capacity, const fiesta_hip_corridor_result *result) {
+  return guarded([&] {
+    corridor(m, {true, lo, hi, waypoints_vox_dev, n_waypoints, offsets_dev, n_paths, min_clearance, max_grow, flags, capacity, nullptr, result, true});
+  });
 }
 int fiesta_hip_cluster_voxels(fiesta_hip_map *m, const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, int32_t connectivity,
                               int32_t min_size, int64_t cluster_capacity, int64_t member_capacity, const fiesta_hip_cluster_result *result,

@@ -29,6 +29,7 @@
 #include "reach_kernels.hpp"
 #include "reach_matrix_kernels.hpp"
 #include "reach_path_kernels.hpp"
+#include "corridor_kernels.hpp"
 #include "tour_kernels.hpp"
 #include "cluster_kernels.hpp"
 #include "view_kernels.hpp"
@@ -2595,6 +2596,20 @@ void DenseMap::reach_matrix(const ReachMatrixArgs &a) {
 // fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin
 void DenseMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
 void DenseMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
+// fiesta_hip_free_boxes[_dev] and fiesta_hip_path_corridor[_dev] (corridor_kernels.hpp): the window is the caller's box clipped to the
+// array (both null: the whole array), in map voxel coordinates; reach_field's source
+void DenseMap::corridor(const CorridorArgs &a) {
+  use_device();
+  int64_t blo[3], bhi[3];
+  const bool empty = !clip_box(a.lo, a.hi, blo, bhi);
+  if (!empty) sync_obsbits();
+  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0};
+  CorridorWin w{};
+  for (int c = 0; c < 3; ++c) w.lo[c] = (int)(blo[c] + g0[c]), w.hi[c] = (int)(bhi[c] + g0[c]), w.off[c] = g0[c], w.org[c] = g_.org[c];
+  if (empty) w.lo[0] = 1, w.hi[0] = 0;
+  w.res = g_.res;
+  corridor_run(stream_, planner_, reach_source(), w, a);
+}
 // fiesta_hip_site_tour[_dev] (tour_kernels.hpp): no voxel is read
 void DenseMap::site_tour(const TourArgs &a) { use_device(), site_tour_run(stream_, planner_, a); }
 

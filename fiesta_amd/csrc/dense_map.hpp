@@ -151,6 +151,7 @@ struct RayArgs;
 struct ReachArgs;
 struct ReachMatrixArgs;
 struct ReachPathArgs;
+struct CorridorArgs;
 struct TourArgs;
 struct ClusterArgs;
 struct ViewArgs;
@@ -262,6 +263,7 @@ class DenseMap {
   void reach_matrix(const ReachMatrixArgs &a);
   void site_tour(const TourArgs &a);
   void reach_paths(const ReachPathArgs &a);
+  void corridor(const CorridorArgs &a);
   void cluster_voxels(const ClusterArgs &a);
   void view_coverage(const ViewArgs &a);
   int64_t count_no_obstacle();

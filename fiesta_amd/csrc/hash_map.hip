@@ -24,6 +24,7 @@
 #include "reach_kernels.hpp"
 #include "reach_matrix_kernels.hpp"
 #include "reach_path_kernels.hpp"
+#include "corridor_kernels.hpp"
 #include "tour_kernels.hpp"
 #include "cluster_kernels.hpp"
 #include "view_kernels.hpp"
@@ -1623,6 +1624,22 @@ void HashMap::reach_matrix(const ReachMatrixArgs &a) {
 // fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin
 void HashMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
 void HashMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
+// fiesta_hip_free_boxes[_dev] and fiesta_hip_path_corridor[_dev] (corridor_kernels.hpp): the map has no outside -- the window is the
+// caller's box clamped to +-2^30, or all of that range -- every page answers, resident or parked; reach_field's source
+void HashMap::corridor(const CorridorArgs &a) {
+  use_device();
+  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
+  CorridorWin w{};
+  bool empty = false;
+  for (int c = 0; c < 3; ++c) {
+    w.lo[c] = a.lo ? clamp30(a.lo[c]) : clamp30(INT32_MIN), w.hi[c] = a.hi ? clamp30(a.hi[c]) : clamp30(INT32_MAX);
+    w.off[c] = 0, w.org[c] = g_.org[c];
+    empty = empty || w.lo[c] > w.hi[c];
+  }
+  if (empty) w.lo[0] = 1, w.hi[0] = 0;
+  w.res = g_.res;
+  corridor_run(stream_, planner_, reach_source(tab), w, a);
+}
 // fiesta_hip_site_tour[_dev] (tour_kernels.hpp): no voxel is read
 void HashMap::site_tour(const TourArgs &a) { use_device(), site_tour_run(stream_, planner_, a); }
 

@@ -87,6 +87,7 @@ class HashMap {
   void reach_matrix(const ReachMatrixArgs &a);
   void site_tour(const TourArgs &a);
   void reach_paths(const ReachPathArgs &a);
+  void corridor(const CorridorArgs &a);
   void cluster_voxels(const ClusterArgs &a);
   void view_coverage(const ViewArgs &a);
   // every voxel of every allocated page, page order: vox (map voxel coordinates), d2, coc, occ; returns the count

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, Stats, TourInfo, TourResult, check
+from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, CorridorResult, FreeBoxesResult, Stats, TourInfo, TourResult, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -884,6 +884,82 @@ class ESDFMap:
         check(self._lib.fiesta_hip_reach_paths_dev(self._h, C.c_void_p(cost_dev_ptr or None), _p(blo), _p(bhi), C.c_void_p(targets_dev_ptr or None),
                                                    int(n_targets), int(connectivity), 1 if shortcut else 0, int(max_span), int(capacity),
                                                    C.byref(res)))
+
+    @staticmethod
+    def _window(lo, hi):
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        blo = None if lo is None else np.ascontiguousarray(lo, np.int32).reshape(3)
+        bhi = None if hi is None else np.ascontiguousarray(hi, np.int32).reshape(3)
+        return blo, bhi
+
+    def FreeBoxes(self, seeds, lo=None, hi=None, max_grow=16, min_clearance=0.0, flags=0) -> dict:
+        """fiesta_hip_free_boxes: around every seed ((n, 3) map voxels) the axis-aligned box of traversable voxels -- ReachField's
+        traversability, with CORRIDOR_THROUGH_UNKNOWN in `flags` the never-observed voxels too -- grown face by face (-x, +x, -y, +y,
+        -z, +z in turn, at most max_grow <= 256 steps each) inside the inclusive map-voxel window [lo, hi] (both None: a dense map's
+        whole array, everything on a hash-block map).  Returns box ((n, 6) int32: lo xyz, hi xyz), box_pos ((n, 6) f64 metres: the
+        box's two corners), stop ((n, 6) uint8, CORRIDOR_STOP_*), volume ((n,) int64) and status ((n,) int32, FREE_BOX_*);
+        fiesta_amd.free_box_model is the definition"""
+        blo, bhi = self._window(lo, hi)
+        s = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
+        n = len(s)
+        out = {"box": np.empty((n, 6), np.int32), "box_pos": np.empty((n, 6), np.float64), "stop": np.empty((n, 6), np.uint8),
+               "volume": np.empty(n, np.int64), "status": np.empty(n, np.int32)}
+        res = FreeBoxesResult(*[a.ctypes.data if n else None for a in out.values()])
+        check(self._lib.fiesta_hip_free_boxes(self._h, _p(blo), _p(bhi), _p(s) if n else None, n, float(min_clearance), int(max_grow), int(flags),
+                                              C.byref(res)))
+        return out
+
+    def FreeBoxesDevice(self, seeds_dev_ptr: int, n: int, lo=None, hi=None, max_grow=16, min_clearance=0.0, flags=0, box_dev_ptr: int = 0,
+                        box_pos_dev_ptr: int = 0, stop_dev_ptr: int = 0, volume_dev_ptr: int = 0, status_dev_ptr: int = 0):
+        """fiesta_hip_free_boxes_dev: seeds and the outputs resident on the device (0: that array is not written); only enqueued on
+        the map's stream"""
+        blo, bhi = self._window(lo, hi)
+        res = FreeBoxesResult(int(box_dev_ptr) or None, int(box_pos_dev_ptr) or None, int(stop_dev_ptr) or None, int(volume_dev_ptr) or None,
+                              int(status_dev_ptr) or None)
+        check(self._lib.fiesta_hip_free_boxes_dev(self._h, _p(blo), _p(bhi), C.c_void_p(seeds_dev_ptr or None), int(n), float(min_clearance),
+                                                  int(max_grow), int(flags), C.byref(res)))
+
+    def PathCorridor(self, waypoints_vox, offsets, lo=None, hi=None, max_grow=16, min_clearance=0.0, flags=0, want_pos=True) -> dict:
+        """fiesta_hip_path_corridor: for every polyline of the CSR batch (`waypoints_vox` (n, 3) map voxels and `offsets`, as ReachPaths
+        returns them) the safe flight corridor -- overlapping boxes inflated as by FreeBoxes along the path's voxel chain, a new box
+        wherever the chain leaves the last one.  Returns offsets ((n_paths + 1,) int64 CSR over the boxes), boxes ((N, 6) int32),
+        boxes_pos ((N, 6) f64 metres; None without want_pos), stop ((N, 6) uint8), entry ((N,) int32), status ((n_paths,) int32,
+        CORRIDOR_*), n_chain, blocked_segment ((n_paths,) int32) and blocked_vox ((n_paths, 3) int32);
+        fiesta_amd.corridor_model is the definition"""
+        blo, bhi = self._window(lo, hi)
+        w = np.ascontiguousarray(waypoints_vox, dtype=np.int32).reshape(-1, 3)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if len(off) < 1:
+            raise ValueError("offsets must hold n_paths + 1 entries")
+        n = len(off) - 1
+        out = {"offsets": np.zeros(n + 1, np.int64), "status": np.empty(n, np.int32), "n_chain": np.empty(n, np.int32),
+               "blocked_segment": np.empty(n, np.int32), "blocked_vox": np.empty((n, 3), np.int32)}
+        args = (_p(blo), _p(bhi), _p(w) if len(w) else None, len(w), _p(off), n, float(min_clearance), int(max_grow), int(flags))
+        ptr = lambda k: out[k].ctypes.data if out[k] is not None and out[k].size else None  # noqa: E731
+        res = CorridorResult(out["offsets"].ctypes.data, None, None, None, None, ptr("status"), ptr("n_chain"), ptr("blocked_segment"), ptr("blocked_vox"))
+        check(self._lib.fiesta_hip_path_corridor(self._h, *args, 0, C.byref(res)))
+        total = int(out["offsets"][n])
+        out.update(boxes=np.empty((total, 6), np.int32), boxes_pos=np.empty((total, 6), np.float64) if want_pos else None,
+                   stop=np.empty((total, 6), np.uint8), entry=np.empty(total, np.int32))
+        if total:
+            res = CorridorResult(out["offsets"].ctypes.data, ptr("boxes"), ptr("boxes_pos"), ptr("stop"), ptr("entry"), None, None, None, None)
+            check(self._lib.fiesta_hip_path_corridor(self._h, *args, total, C.byref(res)))
+        return out
+
+    def PathCorridorDevice(self, waypoints_vox_dev_ptr: int, n_waypoints: int, path_offsets_dev_ptr: int, n_paths: int, offsets_dev_ptr: int,
+                           lo=None, hi=None, max_grow=16, min_clearance=0.0, flags=0, capacity: int = 0, boxes_dev_ptr: int = 0,
+                           boxes_pos_dev_ptr: int = 0, stop_dev_ptr: int = 0, entry_dev_ptr: int = 0, status_dev_ptr: int = 0,
+                           n_chain_dev_ptr: int = 0, blocked_segment_dev_ptr: int = 0, blocked_vox_dev_ptr: int = 0):
+        """fiesta_hip_path_corridor_dev: the waypoints, their CSR offsets (where ReachPathsDevice left them) and the outputs resident
+        on the device (offsets: n_paths + 1 int64, required; 0: that array is not written); only enqueued on the map's stream.
+        offsets holds the true totals whatever `capacity` is: enqueue with capacity 0 to size the buffers"""
+        blo, bhi = self._window(lo, hi)
+        res = CorridorResult(*[int(v) or None for v in (offsets_dev_ptr, boxes_dev_ptr, boxes_pos_dev_ptr, stop_dev_ptr, entry_dev_ptr, status_dev_ptr,
+                                                        n_chain_dev_ptr, blocked_segment_dev_ptr, blocked_vox_dev_ptr)])
+        check(self._lib.fiesta_hip_path_corridor_dev(self._h, _p(blo), _p(bhi), C.c_void_p(waypoints_vox_dev_ptr or None), int(n_waypoints),
+                                                     C.c_void_p(path_offsets_dev_ptr or None), int(n_paths), float(min_clearance), int(max_grow),
+                                                     int(flags), int(capacity), C.byref(res)))
 
     @staticmethod
     def _cluster_info(info) -> dict:

@@ -425,6 +425,75 @@ class ESDFMap {
     }
     return out;
   }
+  // Free boxes (fiesta_hip_free_boxes, include/fiesta_hip.h): around every seed voxel the axis-aligned box of traversable voxels
+  // (ReachField's traversability; flags: FIESTA_HIP_CORRIDOR_THROUGH_UNKNOWN) grown face by face, at most max_grow <= 256 steps per
+  // face, inside the inclusive voxel window [lo, hi] (both null: a dense map's whole array, everything on a hash-block map).  box:
+  // lo xyz, hi xyz per seed; pos: the box's two corners in metres; stop: FIESTA_HIP_CORRIDOR_STOP_* per face; status:
+  // FIESTA_HIP_FREE_BOX_*.
+  struct FreeBoxSet {
+    std::vector<int32_t> box;  // 6 per seed
+    std::vector<double> pos;   // 6 per seed
+    std::vector<uint8_t> stop;  // 6 per seed
+    std::vector<int64_t> volume;
+    std::vector<int32_t> status;
+  };
+  FreeBoxSet FreeBoxes(const std::vector<Eigen::Vector3i> &seeds, int32_t max_grow = 16, double min_clearance = 0.0, int32_t flags = 0,
+                       const Eigen::Vector3i *lo = nullptr, const Eigen::Vector3i *hi = nullptr) {
+    Flush();
+    if ((lo == nullptr) != (hi == nullptr)) throw std::invalid_argument("FreeBoxes: lo and hi must both be given or both be null");
+    int32_t a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
+    if (lo)
+      for (int c = 0; c < 3; ++c) a[c] = (*lo)(c), b[c] = (*hi)(c);
+    std::vector<int32_t> sv;
+    for (const auto &v : seeds) sv.insert(sv.end(), {v(0), v(1), v(2)});
+    const size_t n = seeds.size();
+    FreeBoxSet out;
+    out.box.assign(6 * n + 1, 0), out.pos.assign(6 * n + 1, 0.0), out.stop.assign(6 * n + 1, 0);  // (one spare entry: never a null pointer)
+    out.volume.assign(n + 1, 0), out.status.assign(n + 1, 0);
+    const fiesta_hip_free_boxes_result r{out.box.data(), out.pos.data(), out.stop.data(), out.volume.data(), out.status.data()};
+    ck(fiesta_hip_free_boxes(h_, lo ? a : nullptr, lo ? b : nullptr, sv.empty() ? nullptr : sv.data(), (int64_t)n, min_clearance, max_grow, flags, &r));
+    out.box.resize(6 * n), out.pos.resize(6 * n), out.stop.resize(6 * n), out.volume.resize(n), out.status.resize(n);
+    return out;
+  }
+  // Path corridors (fiesta_hip_path_corridor, include/fiesta_hip.h): for every voxel polyline of a CSR batch -- ReachPathSet's vox and
+  // offsets as they come -- the safe flight corridor: overlapping boxes inflated as by FreeBoxes along the path's voxel chain, a new
+  // box wherever the chain leaves the last one.  offsets is CSR over the boxes; status: FIESTA_HIP_CORRIDOR_*; a BLOCKED path keeps
+  // the boxes made so far and names the segment and the voxel.
+  struct CorridorSet {
+    std::vector<int64_t> offsets;  // n_paths + 1
+    std::vector<int32_t> boxes;    // 6 per box: lo xyz, hi xyz
+    std::vector<double> pos;       // 6 per box, metres
+    std::vector<uint8_t> stop;     // 6 per box
+    std::vector<int32_t> entry;    // per box: the chain index at which it was made
+    std::vector<int32_t> status, n_chain, blocked_segment, blocked_vox;  // per path (blocked_vox: 3 per path)
+  };
+  CorridorSet PathCorridor(const std::vector<int32_t> &waypoints_vox, const std::vector<int64_t> &offsets, int32_t max_grow = 16,
+                           double min_clearance = 0.0, int32_t flags = 0, const Eigen::Vector3i *lo = nullptr, const Eigen::Vector3i *hi = nullptr) {
+    Flush();
+    if ((lo == nullptr) != (hi == nullptr)) throw std::invalid_argument("PathCorridor: lo and hi must both be given or both be null");
+    if (offsets.empty() || waypoints_vox.size() % 3 != 0) throw std::invalid_argument("PathCorridor: offsets needs n_paths + 1 entries, waypoints 3 each");
+    int32_t a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
+    if (lo)
+      for (int c = 0; c < 3; ++c) a[c] = (*lo)(c), b[c] = (*hi)(c);
+    const size_t n = offsets.size() - 1;
+    const int64_t nw = (int64_t)(waypoints_vox.size() / 3);
+    CorridorSet out;
+    out.offsets.assign(n + 1, 0);
+    out.status.assign(n + 1, 0), out.n_chain.assign(n + 1, 0), out.blocked_segment.assign(n + 1, -1), out.blocked_vox.assign(3 * n + 1, 0);
+    fiesta_hip_corridor_result r{out.offsets.data(), nullptr, nullptr, nullptr, nullptr, out.status.data(), out.n_chain.data(),
+                                 out.blocked_segment.data(), out.blocked_vox.data()};
+    const int32_t *wp = waypoints_vox.empty() ? nullptr : waypoints_vox.data();
+    ck(fiesta_hip_path_corridor(h_, lo ? a : nullptr, lo ? b : nullptr, wp, nw, offsets.data(), (int64_t)n, min_clearance, max_grow, flags, 0, &r));
+    out.status.resize(n), out.n_chain.resize(n), out.blocked_segment.resize(n), out.blocked_vox.resize(3 * n);
+    const int64_t total = out.offsets[n];
+    out.boxes.assign((size_t)total * 6, 0), out.pos.assign((size_t)total * 6, 0.0), out.stop.assign((size_t)total * 6, 0);
+    out.entry.assign((size_t)total, 0);
+    if (total > 0) {
+      r = fiesta_hip_corridor_result{out.offsets.data(), out.boxes.data(), out.pos.data(), out.stop.data(), out.entry.data(), nullptr, nullptr, nullptr, nullptr};
+      ck(fiesta_hip_path_corridor(h_, lo ? a : nullptr, lo ? b : nullptr, wp, nw, offsets.data(), (int64_t)n, min_clearance, max_grow, flags, total, &r));
+    }
+    return out;
+  }
   // Voxel clusters (fiesta_hip_cluster_voxels, include/fiesta_hip.h): the connected groups (connectivity 6, 18 or 26) of a voxel list
   // -- typically GetFrontierVoxels' -- with those below min_size distinct voxels dropped and the rest numbered by their lowest entry
   // index.  mask (nullable): the frontier call's unknown-neighbour bits; key (nullable): one int32 per entry, e.g. ReachField's

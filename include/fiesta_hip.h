@@ -132,7 +132,8 @@ const char *fiesta_hip_last_error(void);
 /* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev].
  * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev], fiesta_hip_ray_query[_dev], fiesta_hip_reach_field[_dev] and
  * fiesta_hip_reach_paths[_dev] came later without a new number, and so did fiesta_hip_cluster_voxels[_dev],
- * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev] and fiesta_hip_site_tour[_dev]: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_site_tour[_dev], fiesta_hip_free_boxes[_dev] and
+ * fiesta_hip_path_corridor[_dev]: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -784,6 +785,126 @@ int fiesta_hip_reach_paths(fiesta_hip_map *m, const int32_t *cost, const int32_t
 int fiesta_hip_reach_paths_dev(fiesta_hip_map *m, const int32_t *cost_dev, const int32_t box_lo[3], const int32_t box_hi[3],
                                const int32_t *targets_dev, int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span,
                                int64_t capacity, const fiesta_hip_reach_paths_result *result);
+
+/* ---- free-space corridors: box inflation around voxels, and a corridor of overlapping boxes along voxel polylines ----
+ * What a trajectory optimiser takes after the chain frontier voxels -> reachability -> reach paths: not a voxel staircase but a
+ * SAFE FLIGHT CORRIDOR, a short sequence of overlapping axis-aligned boxes of traversable space around the path, inside which a
+ * polynomial or B-spline is fitted under linear constraints.  fiesta_hip_free_boxes inflates one box around every seed voxel;
+ * fiesta_hip_path_corridor builds the corridor of every polyline of a CSR batch, in exactly the form fiesta_hip_reach_paths writes
+ * (waypoints_vox and offsets), so the whole chain stays on the device.  Read-only; no reference counterpart.
+ * fiesta_hip_version() is still 101: detect these four calls by symbol lookup.  fiesta_amd.free_box_model and
+ * fiesta_amd.corridor_model are the definition.
+ * Window W: lo / hi are HOST pointers in both variants, an inclusive voxel box in map voxel coordinates; both may be NULL on every
+ *   store.  A dense map or shard intersects the box with its own array; with both NULL, W is the whole array.  A hash-block map has
+ *   no outside: a given box is clamped to +-2^30, and with both NULL W is unbounded (every voxel within +-2^30, as far as
+ *   coordinates go anywhere in this interface).  An empty W, or lo[c] > hi[c], is no error: every seed then reads OUTSIDE and every
+ *   path with a waypoint BLOCKED at its first.
+ * traversable(v), for v in W: exactly fiesta_hip_reach_field's -- free (observed and not Exist) and, only if min_clearance > 0,
+ *   GetDistance(Vector3i v) >= min_clearance with the voxel query's own f64 value; with flags & FIESTA_HIP_CORRIDOR_THROUGH_UNKNOWN
+ *   a never-observed voxel is traversable too (a tile without a page counts as never observed).  Outside W a voxel is not
+ *   traversable.  With min_clearance <= 0 the distance field is not read.  The map is read as it stands.
+ * inflate(lo0, hi0, max_grow): faces f = 0 .. 5 are -x, +x, -y, +y, -z, +z (the bit order of the frontier mask), axis a = f >> 1.
+ *     lo, hi = lo0, hi0;  g[0..5] = 0;  stop[0..5] = 0
+ *     while some stop[f] == 0:
+ *       for f in 0 .. 5 in this order, skipping faces with stop[f] != 0:
+ *         if g[f] == max_grow:                     stop[f] = LIMIT (3);   continue
+ *         c = hi[a] + 1 (odd f)  or  lo[a] - 1 (even f)
+ *         if c lies outside W on axis a:           stop[f] = EDGE (2);    continue
+ *         slab = the voxels with coordinate c on axis a and the CURRENT [lo, hi] on the other two axes (extensions made earlier
+ *                in the same round included)
+ *         if some slab voxel is not traversable:   stop[f] = BLOCKED (1); continue
+ *         extend the box to c on that side;  g[f] += 1
+ *   Each step grows or stops a face: at most 6 * (max_grow + 1) face tests, and the result is unique.  max_grow lies in
+ *   0 .. FIESTA_HIP_CORRIDOR_MAX_GROW.
+ * fiesta_hip_free_boxes, per seed (seeds: n x 3 int32 map voxels); every pointer of the result struct is nullable:
+ *   box      int32 x 6: lo xyz, then hi xyz, inclusive -- inflate([seed, seed])
+ *   box_pos  f64 x 6: (double)lo[c] * resolution + origin[c], then ((double)hi[c] + 1.0) * resolution + origin[c]
+ *   stop     uint8 x 6: the stop code of each face
+ *   volume   int64: the number of voxels in the box
+ *   status   int32: FIESTA_HIP_FREE_BOX_OK; _OUTSIDE: the seed is not in W; _BLOCKED: it is not traversable.  For any status other
+ *            than OK box is INT32_MIN x 6, box_pos NaN, stop 0 and volume 0; the other seeds are unaffected.
+ *   Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable; each is checked before the map handle is
+ *   looked at): min_clearance is NaN, exactly one of lo / hi is NULL, max_grow out of range, unknown flag bits, a negative n, seeds
+ *   NULL with n > 0, result NULL.  n = 0 does nothing.
+ * fiesta_hip_path_corridor: waypoints_vox, n_waypoints x 3 int32, and offsets, int64 x (n_paths + 1) in CSR form.
+ *   Chain: for waypoints p -> q, walk(p, q) is the voxel sequence of the reference traversal from centre to centre
+ *     (fiesta_amd.reach_walk: what visible() of fiesta_hip_reach_paths walks).  Candidate A is walk(p, q) followed by q unless q is
+ *     already its last element; candidate B is the reverse of (walk(q, p) followed by p, with the same exception).  Both are
+ *     6-connected monotone chains of 1 + |p - q|_1 voxels from p to q.  The segment uses A if all its voxels are traversable,
+ *     otherwise B if all of B's are, otherwise the path is BLOCKED there.  (For a diagonal move of a 26-connected path A and B
+ *     are two of the axis orders, so a path may round a wall corner on whichever side is free; for a path shortcut by
+ *     fiesta_hip_reach_paths B is exactly the sequence its visible() tested, because its output runs from the seed to the target.)
+ *   Corridor of a path w[0 .. m - 1]:
+ *     visit(v):  if a box exists and v lies in the LAST box: prev = v; return
+ *                seed box = [v, v] if prev is none, else the bounding box of {prev, v} (two 6-adjacent traversable voxels)
+ *                append inflate(seed box); entry = v's chain index; prev = v
+ *     w[0] outside W or not traversable: BLOCKED at segment -1 with no boxes, blocked_vox = w[0].  Otherwise visit it with chain
+ *     index 0; then for each segment j with w[j] != w[j + 1] choose A or B and visit its voxels after the first in order, the chain
+ *     indices counting on.  A BLOCKED path keeps the boxes made so far and reports blocked_segment = j and blocked_vox = the first
+ *     voxel of A that is not traversable.  A path is INVALID, and yields no box, if a waypoint has a coordinate beyond +-2^30 or a
+ *     segment has |p - q|_1 > 4095 and -- in the _dev variant only -- if offsets[p + 1] < offsets[p] or its range leaves
+ *     [0, n_waypoints]; the host variant refuses such offsets as a whole-call error.  An empty path is OK with no box.
+ *   Outputs, per box: boxes (int32 x 6), boxes_pos (f64 x 6), stop (uint8 x 6) as above, and entry (int32); per path: status
+ *     (FIESTA_HIP_CORRIDOR_OK / _INVALID / _BLOCKED), n_chain (the chain voxels visited), blocked_segment (-1 if none), blocked_vox
+ *     (INT32_MIN x 3 if none); offsets, int64 x (n_paths + 1), REQUIRED: CSR over the boxes, the TRUE totals whatever capacity is
+ *     (n_paths = 0 writes offsets[0] = 0).  Boxes with a global index below `capacity` are written and nothing beyond is touched:
+ *     call with capacity 0 (the per-box arrays may then be NULL) and read offsets[n_paths] to size the buffers.
+ *   Whole-call errors: those of fiesta_hip_free_boxes (with waypoints_vox NULL while n_waypoints > 0, a negative count or capacity),
+ *     offsets NULL, result or result->offsets NULL, and in the host variant offsets that do not start at or above 0, decrease, or
+ *     end above n_waypoints.
+ * Guarantees: (1) every voxel of every box is traversable and lies inside W; (2) consecutive boxes of a path share at least one
+ *   voxel; (3) every visited chain voxel lies in the box that was last when it was visited; (4) every stop code is truthful for the
+ *   final box -- LIMIT: that side grew max_grow, EDGE: the next plane leaves W, BLOCKED: the slab beyond that face over the final
+ *   cross-section holds a voxel that is not traversable; (5) max_grow = 0 returns the seed boxes; (6) all arithmetic is integer
+ *   apart from the traversal, the clearance comparison and *_pos: every output has the same bits for any launch shape and
+ *   scheduling, and the bits of fiesta_amd.free_box_model / fiesta_amd.corridor_model.
+ * fiesta_hip_free_boxes / fiesta_hip_path_corridor          host arrays; stage, run, synchronise, copy back (the corridor call
+ *                                                           copies min(total, capacity) boxes).
+ * fiesta_hip_free_boxes_dev / fiesta_hip_path_corridor_dev  seeds / waypoints, offsets and the result's arrays are device pointers;
+ *                                                           only enqueued on the map's stream (the corridor: count, scan, write;
+ *                                                           no host round trip, no data-dependent allocation).  A hash-block map
+ *                                                           first rebuilds its page table if its page set changed, as every
+ *                                                           query does.  Shards answer for their own array; there is no
+ *                                                           shard-group call. */
+#define FIESTA_HIP_CORRIDOR_THROUGH_UNKNOWN 1
+#define FIESTA_HIP_CORRIDOR_MAX_GROW 256
+#define FIESTA_HIP_CORRIDOR_STOP_BLOCKED 1 /* stop codes of a face */
+#define FIESTA_HIP_CORRIDOR_STOP_EDGE 2
+#define FIESTA_HIP_CORRIDOR_STOP_LIMIT 3
+#define FIESTA_HIP_FREE_BOX_OK 0      /* status values of fiesta_hip_free_boxes */
+#define FIESTA_HIP_FREE_BOX_OUTSIDE 1 /* seed not in W */
+#define FIESTA_HIP_FREE_BOX_BLOCKED 2 /* seed not traversable */
+#define FIESTA_HIP_CORRIDOR_OK 0      /* status values of fiesta_hip_path_corridor */
+#define FIESTA_HIP_CORRIDOR_INVALID 1 /* a segment too long, a coordinate too far, bad offsets (_dev) */
+#define FIESTA_HIP_CORRIDOR_BLOCKED 2 /* the first waypoint, or both chains of a segment, are not traversable */
+typedef struct fiesta_hip_free_boxes_result { /* every pointer nullable */
+  int32_t *box;                               /* n x 6: lo xyz, hi xyz */
+  double *box_pos;                            /* n x 6, metres */
+  uint8_t *stop;                              /* n x 6 */
+  int64_t *volume;                            /* n */
+  int32_t *status;                            /* n */
+} fiesta_hip_free_boxes_result;
+typedef struct fiesta_hip_corridor_result {
+  int64_t *offsets;         /* n_paths + 1; REQUIRED */
+  int32_t *boxes;           /* capacity x 6; nullable */
+  double *boxes_pos;        /* capacity x 6, metres; nullable */
+  uint8_t *stop;            /* capacity x 6; nullable */
+  int32_t *entry;           /* capacity; nullable */
+  int32_t *status;          /* per path; nullable */
+  int32_t *n_chain;         /* per path; nullable */
+  int32_t *blocked_segment; /* per path; nullable */
+  int32_t *blocked_vox;     /* per path x 3; nullable */
+} fiesta_hip_corridor_result;
+int fiesta_hip_free_boxes(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds, int64_t n, double min_clearance,
+                          int32_t max_grow, int32_t flags, const fiesta_hip_free_boxes_result *result);
+int fiesta_hip_free_boxes_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds_dev, int64_t n,
+                              double min_clearance, int32_t max_grow, int32_t flags, const fiesta_hip_free_boxes_result *result);
+int fiesta_hip_path_corridor(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *waypoints_vox, int64_t n_waypoints,
+                             const int64_t *offsets, int64_t n_paths, double min_clearance, int32_t max_grow, int32_t flags,
+                             int64_t capacity, const fiesta_hip_corridor_result *result);
+int fiesta_hip_path_corridor_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *waypoints_vox_dev,
+                                 int64_t n_waypoints, const int64_t *offsets_dev, int64_t n_paths, double min_clearance, int32_t max_grow,
+                                 int32_t flags, int64_t capacity, const fiesta_hip_corridor_result *result);
 
 /* ---- voxel clusters: the connected groups of a voxel list, with per-cluster statistics, on the device ----
  * The step between fiesta_hip_get_frontier_voxels and fiesta_hip_reach_field: a planner does not visit frontier voxels, it visits
