@@ -135,6 +135,18 @@ class CorridorResult(C.Structure):
                 ("status", C.c_void_p), ("n_chain", C.c_void_p), ("blocked_segment", C.c_void_p), ("blocked_vox", C.c_void_p)]
 
 
+class RefineParams(C.Structure):
+    """fiesta_hip_refine_params: the weights, step limits and iteration count of fiesta_hip_path_refine"""
+    _fields_ = [("margin", C.c_double), ("w_obstacle", C.c_double), ("w_smooth", C.c_double), ("alpha", C.c_double),
+                ("max_step", C.c_double), ("tolerance", C.c_double), ("iterations", C.c_int32), ("flags", C.c_int32)]
+
+
+class RefineResult(C.Structure):
+    """fiesta_hip_refine_result: one array per output of fiesta_hip_path_refine, every pointer nullable"""
+    _fields_ = [("waypoints", C.c_void_p), ("cost", C.c_void_p), ("last_move", C.c_void_p), ("iterations", C.c_void_p),
+                ("n_below", C.c_void_p), ("min_dist", C.c_void_p), ("status", C.c_void_p)]
+
+
 class ClusterResult(C.Structure):
     """fiesta_hip_cluster_result: one array per output of fiesta_hip_cluster_voxels, every pointer nullable"""
     _fields_ = [("label", C.c_void_p), ("size", C.c_void_p), ("root", C.c_void_p), ("box_lo", C.c_void_p), ("box_hi", C.c_void_p),
@@ -283,6 +295,8 @@ def load():
         "fiesta_hip_free_boxes_dev": (C.c_int, [vp, vp, vp, vp, i64, dbl, i32, i32, vp]),
         "fiesta_hip_path_corridor": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i64, vp]),
         "fiesta_hip_path_corridor_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i64, vp]),
+        "fiesta_hip_path_refine": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp]),
+        "fiesta_hip_path_refine_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp]),
         "fiesta_hip_cluster_voxels": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, i64, vp, vp]),
         "fiesta_hip_cluster_voxels_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, i32, i64, i64, vp, vp]),
         "fiesta_hip_view_coverage": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, vp]),

@@ -7,7 +7,7 @@
 #include <string>
 
 #include "../../include/fiesta_hip.h"
-#include "cluster_kernels.hpp"  // (the ten planner headers: for the calls' argument aggregates; no kernel is used here)
+#include "cluster_kernels.hpp"  // (the eleven planner headers: for the calls' argument aggregates; no kernel is used here)
 #include "corridor_kernels.hpp"
 #include "dense_map.hpp"
 #include "frontier_kernels.hpp"
@@ -17,6 +17,7 @@
 #include "reach_kernels.hpp"
 #include "reach_matrix_kernels.hpp"
 #include "reach_path_kernels.hpp"
+#include "refine_kernels.hpp"
 #include "shard_group.hpp"
 #include "tour_kernels.hpp"
 #include "view_kernels.hpp"
@@ -203,6 +204,29 @@ void corridor(fiesta_hip_map *m, const fiesta::CorridorArgs &a) {
   }
   need(m != nullptr, "null map handle");
   on_store(m, [&](auto &st) { st.corridor(a); });
+}
+// fiesta_hip_path_refine: none of these errors needs a device, and all are checked before the handle is touched (a host batch: the
+// CSR rules as well)
+void path_refine(fiesta_hip_map *m, const fiesta::PathRefineArgs &a) {
+  constexpr double lim = 1048576.0;  // 2^20
+  need(a.w && a.off && a.par && a.res, "path_refine: waypoints, offsets, params or result is null");
+  need(a.n_wp >= 0 && a.n_paths >= 0, "path_refine: negative count");
+  need(a.n_paths <= (1ll << 30), "path_refine: more than 2^30 paths");
+  const fiesta_hip_refine_params &p = *a.par;
+  need(std::isfinite(p.margin) && std::fabs(p.margin) <= lim, "path_refine: margin must be finite, |margin| <= 2^20");
+  need(p.w_obstacle >= 0 && p.w_obstacle <= lim, "path_refine: w_obstacle must lie in 0 .. 2^20");  // (a NaN fails every comparison)
+  need(p.w_smooth >= 0 && p.w_smooth <= lim, "path_refine: w_smooth must lie in 0 .. 2^20");
+  need(p.alpha > 0 && p.alpha <= lim, "path_refine: alpha must be > 0 and <= 2^20");
+  need(p.max_step > 0 && p.max_step <= lim, "path_refine: max_step must be > 0 and <= 2^20");
+  need(std::isfinite(p.tolerance) && p.tolerance >= 0, "path_refine: tolerance must be finite and >= 0");
+  need(p.iterations >= 0 && p.iterations <= FIESTA_HIP_REFINE_MAX_ITERATIONS, "path_refine: iterations must lie in 0 .. 1024");
+  need(p.flags == 0, "path_refine: flags must be 0");
+  if (!a.dev) {
+    need(a.off[0] == 0 && a.off[a.n_paths] == a.n_wp, "path_refine: offsets[0] must be 0 and offsets[n_paths] = n_waypoints");
+    for (int64_t i = 0; i < a.n_paths; ++i) need(a.off[i] <= a.off[i + 1], "path_refine: offsets must be non-decreasing");
+  }
+  need(m != nullptr, "null map handle");
+  on_store(m, [&](auto &s) { s.path_refine(a); });
 }
 // none of these errors needs a device
 void cluster_voxels(fiesta_hip_map *m, const fiesta::ClusterArgs &a) {
@@ -528,6 +552,14 @@ int fiesta_hip_path_cost(fiesta_hip_map *m, const double *w, int64_t n_wp, const
 int fiesta_hip_path_cost_dev(fiesta_hip_map *m, const double *w_dev, int64_t n_wp, const int64_t *off_dev, int64_t n_paths, double step,
                              double margin, const fiesta_hip_path_cost_result *r) {
   return guarded([&] { path_cost(m, {w_dev, n_wp, off_dev, n_paths, step, margin, r, true}); });
+}
+int fiesta_hip_path_refine(fiesta_hip_map *m, const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths, const double *bounds,
+                           const fiesta_hip_refine_params *par, const fiesta_hip_refine_result *r) {
+  return guarded([&] { path_refine(m, {w, n_wp, off, n_paths, bounds, par, r, false}); });
+}
+int fiesta_hip_path_refine_dev(fiesta_hip_map *m, const double *w_dev, int64_t n_wp, const int64_t *off_dev, int64_t n_paths,
+                               const double *bounds_dev, const fiesta_hip_refine_params *par, const fiesta_hip_refine_result *r) {
+  return guarded([&] { path_refine(m, {w_dev, n_wp, off_dev, n_paths, bounds_dev, par, r, true}); });
 }
 int fiesta_hip_host_cache_fetches(fiesta_hip_map *m, int64_t *fetches) {
   return guarded([&] {

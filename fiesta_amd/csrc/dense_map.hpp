@@ -152,6 +152,7 @@ struct ReachArgs;
 struct ReachMatrixArgs;
 struct ReachPathArgs;
 struct CorridorArgs;
+struct PathRefineArgs;
 struct TourArgs;
 struct ClusterArgs;
 struct ViewArgs;
@@ -252,6 +253,7 @@ class DenseMap {
   // the planner calls: the arguments are checked and packed by the caller (c_api.hip)
   void path_clearance(const PathArgs<fiesta_hip_path_result> &a);
   void path_cost(const PathArgs<fiesta_hip_path_cost_result> &a);
+  void path_refine(const PathRefineArgs &a);
   int64_t host_brick_fetches() const;  // bricks fetched for scalar queries so far (tests, bench)
 
   void download_field(int32_t *d2, int32_t *coc, uint8_t *occ, double *logodds);

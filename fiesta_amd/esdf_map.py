@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, CorridorResult, FreeBoxesResult, Stats, TourInfo, TourResult, check
+from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, Stats, TourInfo, TourResult, check
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -95,6 +95,12 @@ def path_samples(waypoints, offsets, step):
 # fiesta_hip_path_cost_result, in struct order: (name, dtype, one row per "path" or per "waypoint", row shape)
 PATH_COST_FIELDS = (("cost", np.float64, "path", ()), ("grad", np.float64, "waypoint", (3,)), ("length", np.float64, "path", ()),
                     ("n_below", np.int64, "path", ()), ("n_samples", np.int64, "path", ()))
+
+
+# fiesta_hip_refine_result, in struct order: (name, dtype, one row per "path" or per "waypoint", row shape)
+REFINE_FIELDS = (("waypoints", np.float64, "waypoint", (3,)), ("cost", np.float64, "path", (2,)), ("last_move", np.float64, "path", ()),
+                 ("iterations", np.int32, "path", ()), ("n_below", np.int64, "path", ()), ("min_dist", np.float64, "path", ()),
+                 ("status", np.int32, "path", ()))
 
 
 def path_cost_model(query, waypoints, offsets, step, margin):
@@ -612,6 +618,41 @@ class ESDFMap:
         res = PathCostResult(*[int(out.get(name, 0)) or None for name, _, _, _ in PATH_COST_FIELDS])
         check(self._lib.fiesta_hip_path_cost_dev(self._h, C.c_void_p(waypoints_dev_ptr), int(n_waypoints), C.c_void_p(offsets_dev_ptr),
                                                  int(n_paths), float(step), float(margin), C.byref(res)))
+
+    def PathRefine(self, waypoints, offsets, bounds=None, *, margin, w_obstacle, w_smooth, alpha, max_step, tolerance=0.0,
+                   iterations) -> dict:
+        """fiesta_hip_path_refine: every path of the batch (CSR `offsets` over `waypoints`) takes `iterations` projected-gradient
+        steps of size `alpha` (at most `max_step` per component) on w_obstacle * sum (margin - d)^2 + w_smooth * sum |second
+        difference|^2 over its interior waypoints, each clamped to its row of `bounds` ((N, 6): lo xyz, hi xyz; None: free;
+        fiesta_amd.corridor_bounds makes them from a corridor); the ends never move; a path stops once an iteration moved it by at
+        most `tolerance`.  Returns a dict of numpy arrays named as the fields of fiesta_hip_refine_result (waypoints: one row per
+        waypoint; cost: J before, J after); fiesta_amd.path_refine_model is the definition"""
+        w = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if len(off) < 1:
+            raise ValueError("offsets needs n_paths + 1 entries")
+        b = None
+        if bounds is not None:
+            b = np.ascontiguousarray(bounds, dtype=np.float64).reshape(-1, 6)
+            if len(b) != len(w):
+                raise ValueError("bounds needs one row of lo xyz, hi xyz per waypoint")
+        n = len(off) - 1
+        out = {name: np.empty((n if per == "path" else len(w),) + shape, dtype) for name, dtype, per, shape in REFINE_FIELDS}
+        par = RefineParams(float(margin), float(w_obstacle), float(w_smooth), float(alpha), float(max_step), float(tolerance), int(iterations), 0)
+        res = RefineResult(*[out[name].ctypes.data for name, _, _, _ in REFINE_FIELDS])
+        check(self._lib.fiesta_hip_path_refine(self._h, _p(w), len(w), _p(off), n, _p(b), C.byref(par), C.byref(res)))
+        return out
+
+    def PathRefineDevice(self, waypoints_dev_ptr: int, n_waypoints: int, offsets_dev_ptr: int, n_paths: int, bounds_dev_ptr: int = 0, *,
+                         margin, w_obstacle, w_smooth, alpha, max_step, tolerance=0.0, iterations, out=None):
+        """fiesta_hip_path_refine_dev: inputs and outputs resident on the device (bounds 0: every waypoint free; `out` maps field
+        names of fiesta_hip_refine_result to device pointers, missing fields are not written; out["waypoints"] may be the input
+        pointer: in place); only enqueued on the map's stream"""
+        out = out or {}
+        par = RefineParams(float(margin), float(w_obstacle), float(w_smooth), float(alpha), float(max_step), float(tolerance), int(iterations), 0)
+        res = RefineResult(*[int(out.get(name, 0)) or None for name, _, _, _ in REFINE_FIELDS])
+        check(self._lib.fiesta_hip_path_refine_dev(self._h, C.c_void_p(waypoints_dev_ptr), int(n_waypoints), C.c_void_p(offsets_dev_ptr),
+                                                   int(n_paths), C.c_void_p(bounds_dev_ptr or None), C.byref(par), C.byref(res)))
 
     @property
     def host_cache_fetches(self) -> int:

@@ -494,6 +494,42 @@ class ESDFMap {
     }
     return out;
   }
+  // Path refinement (fiesta_hip_path_refine, include/fiesta_hip.h): every path of the CSR batch (waypoints: 3 doubles each, metres,
+  // e.g. ReachPathSet::pos and ::offsets) takes p.iterations projected-gradient steps on p.w_obstacle * sum (margin - d)^2 +
+  // p.w_smooth * sum |second difference|^2 over its interior waypoints, each clamped to its row of `bounds` (6 doubles per waypoint:
+  // lo xyz, hi xyz, e.g. the corridor box it lies in; empty: every waypoint free).  The ends never move; a path stops once an
+  // iteration moved it by at most p.tolerance.  The whole loop runs on the device.
+  struct RefineParams {
+    double margin = 0.5, w_obstacle = 1.0, w_smooth = 1.0, alpha = 0.02, max_step = 0.05, tolerance = 0.0;
+    int32_t iterations = 16;
+  };
+  struct RefineSet {
+    std::vector<double> pos;         // 3 per waypoint: the refined positions
+    std::vector<double> cost;        // 2 per path: J before, J after
+    std::vector<double> last_move;   // per path from here on
+    std::vector<int32_t> iterations;
+    std::vector<int64_t> n_below;
+    std::vector<double> min_dist;
+    std::vector<int32_t> status;     // FIESTA_HIP_REFINE_*
+  };
+  RefineSet RefinePaths(const std::vector<double> &waypoints, const std::vector<int64_t> &offsets, const std::vector<double> &bounds, const RefineParams &p) {
+    Flush();
+    if (offsets.empty() || waypoints.size() % 3 != 0) throw std::invalid_argument("RefinePaths: offsets needs n_paths + 1 entries, waypoints 3 doubles each");
+    if (!bounds.empty() && bounds.size() != 2 * waypoints.size()) throw std::invalid_argument("RefinePaths: bounds needs 6 doubles per waypoint, or none");
+    const size_t n = offsets.size() - 1;
+    RefineSet out;
+    out.pos.assign(waypoints.size() + 1, 0.0), out.cost.assign(2 * n + 1, 0.0), out.last_move.assign(n + 1, 0.0), out.iterations.assign(n + 1, 0);
+    out.n_below.assign(n + 1, 0), out.min_dist.assign(n + 1, 0.0), out.status.assign(n + 1, 0);
+    const fiesta_hip_refine_params par{p.margin, p.w_obstacle, p.w_smooth, p.alpha, p.max_step, p.tolerance, p.iterations, 0};
+    const fiesta_hip_refine_result r{out.pos.data(), out.cost.data(), out.last_move.data(), out.iterations.data(), out.n_below.data(),
+                                     out.min_dist.data(), out.status.data()};
+    const std::vector<double> none(1, 0.0);  // (the call wants a waypoint pointer even for no waypoints)
+    ck(fiesta_hip_path_refine(h_, waypoints.empty() ? none.data() : waypoints.data(), (int64_t)(waypoints.size() / 3), offsets.data(), (int64_t)n,
+                              bounds.empty() ? nullptr : bounds.data(), &par, &r));
+    out.pos.resize(waypoints.size()), out.cost.resize(2 * n), out.last_move.resize(n), out.iterations.resize(n), out.n_below.resize(n);
+    out.min_dist.resize(n), out.status.resize(n);
+    return out;
+  }
   // Voxel clusters (fiesta_hip_cluster_voxels, include/fiesta_hip.h): the connected groups (connectivity 6, 18 or 26) of a voxel list
   // -- typically GetFrontierVoxels' -- with those below min_size distinct voxels dropped and the rest numbered by their lowest entry
   // index.  mask (nullable): the frontier call's unknown-neighbour bits; key (nullable): one int32 per entry, e.g. ReachField's

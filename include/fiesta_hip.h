@@ -132,8 +132,8 @@ const char *fiesta_hip_last_error(void);
 /* 100: the interface up to fiesta_hip_stats ending in path_notes; 101: fiesta_hip_path_clearance[_dev].
  * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev], fiesta_hip_ray_query[_dev], fiesta_hip_reach_field[_dev] and
  * fiesta_hip_reach_paths[_dev] came later without a new number, and so did fiesta_hip_cluster_voxels[_dev],
- * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_site_tour[_dev], fiesta_hip_free_boxes[_dev] and
- * fiesta_hip_path_corridor[_dev]: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_site_tour[_dev], fiesta_hip_free_boxes[_dev],
+ * fiesta_hip_path_corridor[_dev] and fiesta_hip_path_refine[_dev]: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -905,6 +905,96 @@ int fiesta_hip_path_corridor(fiesta_hip_map *m, const int32_t lo[3], const int32
 int fiesta_hip_path_corridor_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *waypoints_vox_dev,
                                  int64_t n_waypoints, const int64_t *offsets_dev, int64_t n_paths, double min_clearance, int32_t max_grow,
                                  int32_t flags, int64_t capacity, const fiesta_hip_corridor_result *result);
+
+/* ---- path refinement: bounded descent of the waypoints of a CSR batch, the whole loop on the device ----
+ * The optimiser's loop that path cost (the evaluator) and the corridors (the constraints) were made for: every path of the batch
+ * takes `iterations` projected-gradient steps on an obstacle cost plus a smoothness cost, every waypoint clamped to a box of its
+ * own -- such as the corridor box it lies in (fiesta_amd.corridor_bounds).  The paths are independent: one launch runs every
+ * path's whole loop, its positions resident on chip; no host round trip, no global synchronisation.  Read-only on the map; no
+ * reference counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.
+ * fiesta_amd.path_refine_model (numpy) is the definition.
+ * Input: waypoints and offsets are path clearance's CSR polylines.  bounds is nullable: n_waypoints x 6 f64, lo xyz then hi xyz,
+ *   metres; +-inf is allowed and means free on that side; bounds NULL means every waypoint is free.  The first and the last
+ *   waypoint of a path never move, and their bounds rows are not read.
+ * The sample: for a waypoint x, (d, g) is fiesta_hip_get_dist_grad at x, bit for bit (dense maps, a single shard, hash-block
+ *   maps; outside a dense map -1 with zero gradient).  phi and gamma[c] are exactly path cost's:
+ *   if d < margin:  e = margin - d;  phi = e * e;  psi = -2.0 * e;  gamma[c] = psi * g[c]      else phi = 0, gamma = 0.
+ * One iteration of a path w[0 .. m-1] is a Jacobi step: everything is computed from the positions of the previous iteration, in
+ *   f64, each operation rounded once (the library is built with -ffp-contract=off), in exactly this order:
+ *     a_j[c] = (w[j-1][c] - 2.0 * w[j][c]) + w[j+1][c]   for 1 <= j <= m-2,   a_0 = a_{m-1} = 0
+ *   and for every interior i (1 <= i <= m-2) and component c:
+ *     s = (a_{i-1}[c] - 2.0 * a_i[c]) + a_{i+1}[c]
+ *     G = w_obstacle * gamma_i[c] + (2.0 * w_smooth) * s
+ *     delta = alpha * G
+ *     if (delta > max_step) delta = max_step;   if (delta < -max_step) delta = -max_step;
+ *     x = w[i][c] - delta
+ *     if (x < lo) x = lo;   if (x > hi) x = hi;
+ *     move = |x - w[i][c]|
+ *   Both clamps are comparisons, not fmin / fmax: the sign of a zero is ruled.  last_move is the maximum of move over the interior
+ *   waypoints and components of the iteration (a maximum of non-negative numbers: no order).  If last_move <= tolerance the path
+ *   stops after this iteration (with tolerance 0: only after an iteration that moved nothing, which changes no later position);
+ *   result.iterations is the number of iterations run.  With iterations = 0, or m <= 2, nothing moves: last_move 0, iterations 0.
+ *   G is the exact derivative with respect to w[i][c] of
+ *     J = sum over i = 1 .. m-2 of e_i,   e_i = w_obstacle * phi_i + w_smooth * ((a_i[0]*a_i[0] + a_i[1]*a_i[1]) + a_i[2]*a_i[2])
+ *   wherever the field's interpolant is differentiable.
+ *   Stability: the smoothness operator (the second difference applied twice) has eigenvalues up to 16, so a caller wants
+ *   alpha * w_smooth < 1/16; max_step bounds the motion per component and iteration whatever the weights are.
+ * Outputs; every pointer of the result is nullable:
+ *   waypoints (x3)  n_waypoints rows, every one written by every call: the rows of a valid path get its final positions, every
+ *                   other row (gaps of a device batch's offsets, INVALID paths) equals the input row.  result.waypoints may be
+ *                   exactly the input pointer (in place) or disjoint from it; any other overlap is the caller's error and is not
+ *                   detected.
+ *   cost (x2)       per path: J at the input positions, J at the final positions.  Every term e_i is bit-identical on the device
+ *                   and in the model; the order of the sum is left free, but it is fixed by the call's arguments (it follows the
+ *                   path's length alone).  Two orders differ by at most (n + 16) * 2^-52 * A, n the number of terms, A the sum of
+ *                   their magnitudes (path cost's bound).  No floating-point atomics: the same call gives the same bits.
+ *   last_move       per path: of the last iteration run
+ *   iterations      per path: iterations actually run
+ *   n_below         per path, over all m final waypoints, ends included: those with d < margin (strictly); exact
+ *   min_dist        per path, over the same waypoints: the minimum d; exact; an empty path gives 0 and +inf
+ *   status          per path: FIESTA_HIP_REFINE_OK, or _INVALID: a non-finite waypoint or a coordinate beyond +-2^40; more than
+ *                   FIESTA_HIP_REFINE_MAX_WAYPOINTS waypoints; an interior bounds row that holds a NaN or has lo > hi; in the _dev
+ *                   variant only, offsets that break path clearance's offset rules.  An INVALID path gives cost NaN, NaN,
+ *                   last_move NaN, iterations -1, n_below -1, min_dist NaN, and its rows equal the input; the other paths are
+ *                   unaffected.
+ *   With the parameter and coordinate limits every intermediate is finite.  Everything except cost has the bits of the model for
+ *   any launch shape and scheduling.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable; each is checked before the map handle is
+ *   looked at): a parameter outside its range, flags != 0, a NULL waypoints, offsets, params or result, negative counts, more
+ *   than 2^30 paths, and in the host variant offsets that break the CSR rules (offsets[0] = 0, non-decreasing, offsets[n_paths] =
+ *   n_waypoints).  n_paths = 0 does nothing.
+ * fiesta_hip_path_refine      host pointers; stages, runs, synchronises (no host route for small batches: always the device).
+ * fiesta_hip_path_refine_dev  waypoints, offsets, bounds and the result's arrays are device pointers (the two structs themselves
+ *                             are host objects); only enqueued on the map's stream: the row copy, the offset check, the kernels.
+ *                             Shards answer for their own array; there is no shard-group call. */
+#define FIESTA_HIP_REFINE_MAX_WAYPOINTS 1024   /* per path */
+#define FIESTA_HIP_REFINE_MAX_ITERATIONS 1024
+#define FIESTA_HIP_REFINE_OK 0
+#define FIESTA_HIP_REFINE_INVALID 1
+typedef struct fiesta_hip_refine_params {
+  double margin;      /* metres; finite, |margin| <= 2^20 */
+  double w_obstacle;  /* finite, 0 .. 2^20 */
+  double w_smooth;    /* finite, 0 .. 2^20 */
+  double alpha;       /* step size; finite, > 0, <= 2^20 */
+  double max_step;    /* metres per component and iteration; finite, > 0, <= 2^20 */
+  double tolerance;   /* metres; finite, >= 0; 0: never stop early */
+  int32_t iterations; /* 0 .. FIESTA_HIP_REFINE_MAX_ITERATIONS */
+  int32_t flags;      /* 0; any other value is an error */
+} fiesta_hip_refine_params;
+typedef struct fiesta_hip_refine_result { /* every pointer nullable */
+  double *waypoints;   /* n_waypoints x 3: the refined positions */
+  double *cost;        /* n_paths x 2: J before, J after */
+  double *last_move;   /* n_paths */
+  int32_t *iterations; /* n_paths: iterations actually run */
+  int64_t *n_below;    /* n_paths */
+  double *min_dist;    /* n_paths */
+  int32_t *status;     /* n_paths */
+} fiesta_hip_refine_result;
+int fiesta_hip_path_refine(fiesta_hip_map *m, const double *waypoints, int64_t n_waypoints, const int64_t *offsets, int64_t n_paths,
+                           const double *bounds, const fiesta_hip_refine_params *params, const fiesta_hip_refine_result *result);
+int fiesta_hip_path_refine_dev(fiesta_hip_map *m, const double *waypoints_dev, int64_t n_waypoints, const int64_t *offsets_dev,
+                               int64_t n_paths, const double *bounds_dev, const fiesta_hip_refine_params *params,
+                               const fiesta_hip_refine_result *result);
 
 /* ---- voxel clusters: the connected groups of a voxel list, with per-cluster statistics, on the device ----
  * The step between fiesta_hip_get_frontier_voxels and fiesta_hip_reach_field: a planner does not visit frontier voxels, it visits
