@@ -13,11 +13,11 @@ from .reach_model import (REACH_PATHS_SHORTCUT, REACH_THROUGH_UNKNOWN, reach_mat
 from .corridor_model import (CORRIDOR_BLOCKED, CORRIDOR_INVALID, CORRIDOR_MAX_GROW, CORRIDOR_OK, CORRIDOR_STOP_BLOCKED,  # noqa: F401
                              CORRIDOR_STOP_EDGE, CORRIDOR_STOP_LIMIT, CORRIDOR_THROUGH_UNKNOWN, FREE_BOX_BLOCKED, FREE_BOX_OK,
                              FREE_BOX_OUTSIDE, corridor_chain, corridor_model, free_box_model)
-from .refine_model import (REFINE_INVALID, REFINE_MAX_ITERATIONS, REFINE_MAX_WAYPOINTS, REFINE_OK, corridor_bounds,  # noqa: F401
-                           path_refine_gradient, path_refine_model)
+from .refine_model import (BOUNDS_VOID_BROKEN, REFINE_INVALID, REFINE_MAX_ITERATIONS, REFINE_MAX_WAYPOINTS, REFINE_OK,  # noqa: F401
+                           corridor_bounds, corridor_bounds_model, path_refine_gradient, path_refine_model)
 from .tour_model import TOUR_CLOSED, best_move, tour_model  # noqa: F401
 
-__all__ = ["path_refine_model", "path_refine_gradient", "corridor_bounds", "REFINE_OK", "REFINE_INVALID", "REFINE_MAX_WAYPOINTS",
+__all__ = ["path_refine_model", "path_refine_gradient", "corridor_bounds", "corridor_bounds_model", "BOUNDS_VOID_BROKEN","REFINE_OK", "REFINE_INVALID", "REFINE_MAX_WAYPOINTS",
            "REFINE_MAX_ITERATIONS", "free_box_model", "corridor_chain", "corridor_model", "CORRIDOR_THROUGH_UNKNOWN", "CORRIDOR_MAX_GROW", "CORRIDOR_STOP_BLOCKED",
            "CORRIDOR_STOP_EDGE", "CORRIDOR_STOP_LIMIT", "FREE_BOX_OK", "FREE_BOX_OUTSIDE", "FREE_BOX_BLOCKED", "CORRIDOR_OK", "CORRIDOR_INVALID",
            "CORRIDOR_BLOCKED", "tour_model", "best_move", "TOUR_CLOSED", "ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "reach_model", "reach_matrix_model", "REACH_THROUGH_UNKNOWN", "reach_moves", "reach_paths_model", "reach_visible", "reach_walk", "REACH_PATHS_SHORTCUT", "cluster_model", "cluster_stencil", "view_coverage_model", "view_ring", "VIEW_OMNI", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",

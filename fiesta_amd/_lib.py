@@ -147,6 +147,11 @@ class RefineResult(C.Structure):
                 ("n_below", C.c_void_p), ("min_dist", C.c_void_p), ("status", C.c_void_p)]
 
 
+class BoundsResult(C.Structure):
+    """fiesta_hip_bounds_result: one array per output of fiesta_hip_corridor_bounds, every pointer nullable"""
+    _fields_ = [("bounds", C.c_void_p), ("ok", C.c_void_p), ("box", C.c_void_p)]
+
+
 class ClusterResult(C.Structure):
     """fiesta_hip_cluster_result: one array per output of fiesta_hip_cluster_voxels, every pointer nullable"""
     _fields_ = [("label", C.c_void_p), ("size", C.c_void_p), ("root", C.c_void_p), ("box_lo", C.c_void_p), ("box_hi", C.c_void_p),
@@ -297,6 +302,8 @@ def load():
         "fiesta_hip_path_corridor_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i64, vp]),
         "fiesta_hip_path_refine": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp]),
         "fiesta_hip_path_refine_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp]),
+        "fiesta_hip_corridor_bounds": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, dbl, i32, vp]),
+        "fiesta_hip_corridor_bounds_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, dbl, i32, vp]),
         "fiesta_hip_cluster_voxels": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, i64, vp, vp]),
         "fiesta_hip_cluster_voxels_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, i32, i64, i64, vp, vp]),
         "fiesta_hip_view_coverage": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, vp]),

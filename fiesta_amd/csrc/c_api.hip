@@ -7,7 +7,8 @@
 #include <string>
 
 #include "../../include/fiesta_hip.h"
-#include "cluster_kernels.hpp"  // (the eleven planner headers: for the calls' argument aggregates; no kernel is used here)
+#include "bounds_kernels.hpp"  // (the twelve planner headers: for the calls' argument aggregates; no kernel is used here)
+#include "cluster_kernels.hpp"
 #include "corridor_kernels.hpp"
 #include "dense_map.hpp"
 #include "frontier_kernels.hpp"
@@ -227,6 +228,28 @@ void path_refine(fiesta_hip_map *m, const fiesta::PathRefineArgs &a) {
   }
   need(m != nullptr, "null map handle");
   on_store(m, [&](auto &s) { s.path_refine(a); });
+}
+// fiesta_hip_corridor_bounds: none of these errors needs a device, and all are checked before the handle is touched (a host batch:
+// the CSR rules of both offset arrays as well)
+void corridor_bounds(fiesta_hip_map *m, const fiesta::CorridorBoundsArgs &a) {
+  need(a.res != nullptr, "corridor_bounds: result is null");
+  need(a.n_wp >= 0 && a.n_paths >= 0 && a.n_boxes >= 0, "corridor_bounds: negative count");
+  need(a.n_paths <= (1ll << 30), "corridor_bounds: more than 2^30 paths");
+  need(a.w != nullptr || a.n_wp == 0, "corridor_bounds: waypoints_vox is null");
+  need((a.off && a.box_off && a.status) || a.n_paths == 0, "corridor_bounds: offsets, box_offsets or status is null");
+  need((a.boxes && a.boxes_pos && a.entry) || a.n_boxes == 0, "corridor_bounds: boxes, boxes_pos or entry is null");
+  need(std::isfinite(a.inset) && a.inset >= 0, "corridor_bounds: inset must be finite and >= 0");
+  need((a.flags & ~FIESTA_HIP_BOUNDS_VOID_BROKEN) == 0, "corridor_bounds: unknown flag bits");
+  if (!a.dev && a.n_paths > 0) {
+    need(a.off[0] == 0 && a.off[a.n_paths] == a.n_wp, "corridor_bounds: offsets[0] must be 0 and offsets[n_paths] = n_waypoints");
+    for (int64_t i = 0; i < a.n_paths; ++i) {
+      need(a.off[i] <= a.off[i + 1], "corridor_bounds: offsets must be non-decreasing");
+      need(a.box_off[i] >= 0 && a.box_off[i] <= a.box_off[i + 1] && a.box_off[i + 1] <= a.n_boxes,
+           "corridor_bounds: a box range decreases, is negative or ends above n_boxes");
+    }
+  }
+  need(m != nullptr, "null map handle");
+  on_store(m, [&](auto &s) { s.corridor_bounds(a); });
 }
 // none of these errors needs a device
 void cluster_voxels(fiesta_hip_map *m, const fiesta::ClusterArgs &a) {
@@ -560,6 +583,18 @@ int fiesta_hip_path_refine(fiesta_hip_map *m, const double *w, int64_t n_wp, con
 int fiesta_hip_path_refine_dev(fiesta_hip_map *m, const double *w_dev, int64_t n_wp, const int64_t *off_dev, int64_t n_paths,
                                const double *bounds_dev, const fiesta_hip_refine_params *par, const fiesta_hip_refine_result *r) {
   return guarded([&] { path_refine(m, {w_dev, n_wp, off_dev, n_paths, bounds_dev, par, r, true}); });
+}
+int fiesta_hip_corridor_bounds(fiesta_hip_map *m, const int32_t *w, int64_t n_wp, const int64_t *off, int64_t n_paths, const int64_t *box_off,
+                               const int32_t *boxes, const double *boxes_pos, const int32_t *entry, const int32_t *status, int64_t n_boxes,
+                               double inset, int32_t flags, const fiesta_hip_bounds_result *r) {
+  return guarded([&] { corridor_bounds(m, {w, n_wp, off, n_paths, box_off, boxes, boxes_pos, entry, status, n_boxes, inset, flags, r, false}); });
+}
+int fiesta_hip_corridor_bounds_dev(fiesta_hip_map *m, const int32_t *w_dev, int64_t n_wp, const int64_t *off_dev, int64_t n_paths,
+                                   const int64_t *box_off_dev, const int32_t *boxes_dev, const double *boxes_pos_dev, const int32_t *entry_dev,
+                                   const int32_t *status_dev, int64_t n_boxes, double inset, int32_t flags, const fiesta_hip_bounds_result *r) {
+  return guarded([&] {
+    corridor_bounds(m, {w_dev, n_wp, off_dev, n_paths, box_off_dev, boxes_dev, boxes_pos_dev, entry_dev, status_dev, n_boxes, inset, flags, r, true});
+  });
 }
 int fiesta_hip_host_cache_fetches(fiesta_hip_map *m, int64_t *fetches) {
   return guarded([&] {

@@ -39,6 +39,7 @@
 #include "level_kernels.hpp"
 #include "path_cost_kernels.hpp"
 #include "refine_kernels.hpp"
+#include "bounds_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
@@ -2602,6 +2603,11 @@ void DenseMap::reach_matrix(const ReachMatrixArgs &a) {
 // fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin
 void DenseMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
 void DenseMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
+// fiesta_hip_corridor_bounds[_dev] (bounds_kernels.hpp): nothing of the map is read at all
+void DenseMap::corridor_bounds(const CorridorBoundsArgs &a) {
+  if (a.n_paths <= 0) return;
+  use_device(), corridor_bounds_run(stream_, planner_, a);
+}
 // fiesta_hip_free_boxes[_dev] and fiesta_hip_path_corridor[_dev] (corridor_kernels.hpp): the window is the caller's box clipped to the
 // array (both null: the whole array), in map voxel coordinates; reach_field's source
 void DenseMap::corridor(const CorridorArgs &a) {

@@ -153,6 +153,7 @@ struct ReachMatrixArgs;
 struct ReachPathArgs;
 struct CorridorArgs;
 struct PathRefineArgs;
+struct CorridorBoundsArgs;
 struct TourArgs;
 struct ClusterArgs;
 struct ViewArgs;
@@ -266,6 +267,7 @@ class DenseMap {
   void site_tour(const TourArgs &a);
   void reach_paths(const ReachPathArgs &a);
   void corridor(const CorridorArgs &a);
+  void corridor_bounds(const CorridorBoundsArgs &a);
   void cluster_voxels(const ClusterArgs &a);
   void view_coverage(const ViewArgs &a);
   int64_t count_no_obstacle();

@@ -20,6 +20,7 @@
 #include "level_kernels.hpp"
 #include "path_cost_kernels.hpp"
 #include "refine_kernels.hpp"
+#include "bounds_kernels.hpp"
 #include "frontier_kernels.hpp"
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
@@ -1630,6 +1631,11 @@ void HashMap::reach_matrix(const ReachMatrixArgs &a) {
 // fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin
 void HashMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
 void HashMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
+// fiesta_hip_corridor_bounds[_dev] (bounds_kernels.hpp): nothing of the map is read at all
+void HashMap::corridor_bounds(const CorridorBoundsArgs &a) {
+  if (a.n_paths <= 0) return;
+  use_device(), corridor_bounds_run(stream_, planner_, a);
+}
 // fiesta_hip_free_boxes[_dev] and fiesta_hip_path_corridor[_dev] (corridor_kernels.hpp): the map has no outside -- the window is the
 // caller's box clamped to +-2^30, or all of that range -- every page answers, resident or parked; reach_field's source
 void HashMap::corridor(const CorridorArgs &a) {

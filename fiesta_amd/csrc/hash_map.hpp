@@ -89,6 +89,7 @@ class HashMap {
   void site_tour(const TourArgs &a);
   void reach_paths(const ReachPathArgs &a);
   void corridor(const CorridorArgs &a);
+  void corridor_bounds(const CorridorBoundsArgs &a);
   void cluster_voxels(const ClusterArgs &a);
   void view_coverage(const ViewArgs &a);
   // every voxel of every allocated page, page order: vox (map voxel coordinates), d2, coc, occ; returns the count

@@ -17,7 +17,8 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, Stats, TourInfo, TourResult, check
+from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, BoundsResult, Stats, TourInfo, TourResult, check
+from .refine_model import BOUNDS_VOID_BROKEN
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
 INFINITY = 10000     # infinity_   (src/ESDFMap.cpp:181)
@@ -1001,6 +1002,47 @@ class ESDFMap:
         check(self._lib.fiesta_hip_path_corridor_dev(self._h, _p(blo), _p(bhi), C.c_void_p(waypoints_vox_dev_ptr or None), int(n_waypoints),
                                                      C.c_void_p(path_offsets_dev_ptr or None), int(n_paths), float(min_clearance), int(max_grow),
                                                      int(flags), int(capacity), C.byref(res)))
+
+    def CorridorBounds(self, waypoints_vox, offsets, corridor, inset=None, void_broken=False) -> dict:
+        """fiesta_hip_corridor_bounds: the `bounds` of PathRefine for the voxel polylines of a CSR batch and their corridor
+        (`corridor`: what PathCorridor returned for the same waypoints_vox and offsets, with boxes_pos) -- each waypoint's corridor
+        box, intersected with the next one where the path changes boxes, `inset` metres taken off every upper face.  inset=None is
+        resolution * 2.0 ** -20 (fiesta_amd.corridor_bounds' own default reads the voxel size off the first box; its bits can differ:
+        pass the same number to both to compare them).  With void_broken the rows of every path that is not ok are NaN, which
+        PathRefine reports INVALID and leaves alone.  Returns bounds ((N, 6) f64: lo xyz, hi xyz), ok ((n_paths,) int32) and box ((N,)
+        int64: the global index of the waypoint's box, -1: none); fiesta_amd.corridor_bounds_model is the definition"""
+        w = np.ascontiguousarray(waypoints_vox, dtype=np.int32).reshape(-1, 3)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        boff = np.ascontiguousarray(corridor["offsets"], dtype=np.int64).reshape(-1)
+        boxes = np.ascontiguousarray(corridor["boxes"], dtype=np.int32).reshape(-1, 6)
+        pos = np.ascontiguousarray(corridor["boxes_pos"], dtype=np.float64).reshape(-1, 6)
+        entry = np.ascontiguousarray(corridor["entry"], dtype=np.int32).reshape(-1)
+        status = np.ascontiguousarray(corridor["status"], dtype=np.int32).reshape(-1)
+        n = len(off) - 1
+        if n < 0 or len(boff) != n + 1 or len(status) != n or not len(boxes) == len(pos) == len(entry):
+            raise ValueError("offsets and corridor do not describe the same batch")
+        inset = self.resolution * 2.0 ** -20 if inset is None else float(inset)
+        out = {"bounds": np.empty((len(w), 6), np.float64), "ok": np.empty(n, np.int32), "box": np.empty(len(w), np.int64)}
+        res = BoundsResult(*[a.ctypes.data if a.size else None for a in out.values()])
+        ptr = lambda a: _p(a) if a.size else None  # noqa: E731
+        check(self._lib.fiesta_hip_corridor_bounds(self._h, ptr(w), len(w), _p(off), n, _p(boff), ptr(boxes), ptr(pos), ptr(entry), ptr(status),
+                                                   len(pos), inset, BOUNDS_VOID_BROKEN if void_broken else 0, C.byref(res)))
+        return out
+
+    def CorridorBoundsDevice(self, waypoints_vox_dev_ptr: int, n_waypoints: int, path_offsets_dev_ptr: int, n_paths: int, box_offsets_dev_ptr: int,
+                             boxes_dev_ptr: int, boxes_pos_dev_ptr: int, entry_dev_ptr: int, status_dev_ptr: int, n_boxes: int, inset=None,
+                             void_broken=False, bounds_dev_ptr: int = 0, ok_dev_ptr: int = 0, box_dev_ptr: int = 0):
+        """fiesta_hip_corridor_bounds_dev: the waypoints, their CSR offsets and the corridor's arrays where ReachPathsDevice and
+        PathCorridorDevice left them, n_boxes = min(the corridor's total, its capacity), and the outputs resident on the device (0:
+        that array is not written); inset=None is resolution * 2.0 ** -20.  Only enqueued on the map's stream: bounds_dev_ptr can be
+        handed to PathRefineDevice at once"""
+        inset = self.resolution * 2.0 ** -20 if inset is None else float(inset)
+        res = BoundsResult(int(bounds_dev_ptr) or None, int(ok_dev_ptr) or None, int(box_dev_ptr) or None)
+        vp = lambda v: C.c_void_p(int(v) or None)  # noqa: E731
+        check(self._lib.fiesta_hip_corridor_bounds_dev(self._h, vp(waypoints_vox_dev_ptr), int(n_waypoints), vp(path_offsets_dev_ptr), int(n_paths),
+                                                       vp(box_offsets_dev_ptr), vp(boxes_dev_ptr), vp(boxes_pos_dev_ptr), vp(entry_dev_ptr),
+                                                       vp(status_dev_ptr), int(n_boxes), inset, BOUNDS_VOID_BROKEN if void_broken else 0,
+                                                       C.byref(res)))
 
     @staticmethod
     def _cluster_info(info) -> dict:

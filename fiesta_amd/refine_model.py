@@ -6,6 +6,8 @@ path_refine_model      the whole call: vectorised over the waypoints of the batc
 path_refine_gradient   G and J of one configuration (the rule test differentiates J numerically and compares)
 corridor_bounds        per waypoint of a voxel polyline the box it may move in: its corridor box, intersected with the next box
                        where the path changes boxes
+corridor_bounds_model  the definition of fiesta_hip_corridor_bounds, the same step on the device: a literal loop, explicit inset,
+                       the per-waypoint box index, VOID_BROKEN, truncated corridors and the device variant's offset rules
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ REFINE_MAX_ITERATIONS = 1024
 REFINE_OK = 0
 REFINE_INVALID = 1
 REFINE_MAX_COORD = 2.0 ** 40
+BOUNDS_VOID_BROKEN = 1
 _LIM = 2.0 ** 20
 
 
@@ -217,3 +220,81 @@ def corridor_bounds(waypoints_vox, offsets, corridor, inset=None):
         inset = (pos[0, 3] - pos[0, 0]) / float(boxes[0, 3] - boxes[0, 0] + 1) * 2.0 ** -20 if len(pos) else 0.0
     bounds[:, 3:] -= float(inset)
     return bounds, ok
+
+
+def _flagged_offsets(off, n_wp):
+    """path clearance's device offset rule: a path is valid iff its start is in range and is the running maximum of the in-range
+    entries before it, and its end lies in [start, n_waypoints]"""
+    o0, o1 = off[:-1], off[1:]
+    run = np.maximum.accumulate(np.where((o0 >= 0) & (o0 <= n_wp), o0, np.iinfo(np.int64).min))
+    return ~((o0 >= 0) & (o0 == run) & (o1 >= o0) & (o1 <= n_wp))
+
+
+def corridor_bounds_model(waypoints_vox, offsets, corridor, inset, void_broken=False, n_boxes=None, device_offsets=False):
+    """The definition of fiesta_hip_corridor_bounds (include/fiesta_hip.h): a literal loop over paths and waypoints.  `corridor` holds
+    the corridor call's offsets, boxes, boxes_pos, entry and status for the batch (waypoints_vox, offsets); n_boxes (None: the rows
+    boxes_pos holds) is the number of box rows present.  `inset` is explicit, in metres: the ABI has no default, the class methods'
+    default is resolution * 2.0 ** -20 -- corridor_bounds' own inset=None divides the first box's width by its voxel count instead,
+    whose bits can differ.  Returns dict(bounds (N, 6) f64, ok (n_paths,) int32, box (N,) int64).
+    device_offsets=False is the host variant: offsets that break the CSR rules, or a box range that decreases, is negative or ends
+    above n_boxes, raise ValueError (the whole-call error).  True is the _dev variant: such a path gets ok = 0, reads nothing, and
+    its rows (as every row no valid path owns) are NaN with box -1.
+    Against corridor_bounds with the same inset: bounds and ok are equal bit for bit wherever that function accepts the input, the
+    arrays hold no negative zero (np.maximum and a comparison choose differently between +0 and -0) and entry[1] of a path is not
+    0 (it tests the path's box 1 where rule 4 says b(0) + 1; the corridor call's entries increase strictly)."""
+    v = np.ascontiguousarray(waypoints_vox, dtype=np.int64).reshape(-1, 3)
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    boff = np.ascontiguousarray(corridor["offsets"], dtype=np.int64).reshape(-1)
+    entry = np.asarray(corridor["entry"], dtype=np.int64).reshape(-1)
+    pos = np.asarray(corridor["boxes_pos"], dtype=np.float64).reshape(-1, 6)
+    boxes = np.asarray(corridor["boxes"], dtype=np.int64).reshape(-1, 6)
+    status = np.asarray(corridor["status"]).reshape(-1)
+    inset = float(inset)
+    if not (np.isfinite(inset) and inset >= 0):
+        raise ValueError("corridor_bounds: inset must be finite and >= 0")
+    n_paths, n_wp = len(off) - 1, len(v)
+    n_boxes = len(pos) if n_boxes is None else int(n_boxes)
+    if n_paths < 0 or len(boff) != n_paths + 1 or len(status) != n_paths or not 0 <= n_boxes <= min(len(pos), len(boxes), len(entry)):
+        raise ValueError("corridor_bounds: offsets and corridor do not describe the same batch")
+    flagged = _flagged_offsets(off, n_wp) if device_offsets else np.zeros(n_paths, bool)
+    bad_box = (boff[:-1] < 0) | (boff[1:] < boff[:-1]) | (boff[1:] > n_boxes)
+    if not device_offsets and n_paths > 0 and (off[0] != 0 or off[-1] != n_wp or np.any(np.diff(off) < 0) or bad_box.any()):
+        raise ValueError("corridor_bounds: offsets break the CSR rules, or a box range decreases, is negative or ends above n_boxes")
+    bounds = np.full((n_wp, 6), np.nan)
+    box = np.full(n_wp, -1, np.int64)
+    ok = np.zeros(n_paths, np.int32)
+    for p in range(n_paths):
+        if flagged[p] or bad_box[p]:
+            continue
+        o0, o1, b0, b1 = int(off[p]), int(off[p + 1]), int(boff[p]), int(boff[p + 1])
+        good = int(status[p]) == 0
+        ok[p] = good
+        m, nb = o1 - o0, b1 - b0
+        if m == 0 or nb == 0:
+            continue
+        c, b = 0, []
+        for i in range(m):
+            if i:
+                c += int(np.abs(v[o0 + i] - v[o0 + i - 1]).sum())
+            k = 0                                            # the last box with entry <= c_i, clamped into the path's range
+            while k + 1 < nb and entry[b0 + k + 1] <= c:
+                k += 1
+            b.append(k)
+        for i in range(m - 1):
+            if b[i + 1] > b[i] + 1:
+                good = False
+        if m > 1 and b[1] == b[0] + 1 and not _inside(v[o0], boxes[b0 + b[0] + 1]):
+            good = False
+        ok[p] = good
+        for i in range(m):
+            row = pos[b0 + b[i]].copy()
+            if good and i + 1 < m and b[i + 1] == b[i] + 1:
+                other = pos[b0 + b[i] + 1]
+                row[:3] = np.where(row[:3] > other[:3], row[:3], other[:3])
+                row[3:] = np.where(row[3:] < other[3:], row[3:], other[3:])
+            row[3:] = row[3:] - inset
+            if void_broken and not good:
+                row[:] = np.nan
+            bounds[o0 + i] = row
+            box[o0 + i] = b0 + b[i]
+    return {"bounds": bounds, "ok": ok, "box": box}

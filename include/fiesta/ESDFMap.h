@@ -494,6 +494,32 @@ class ESDFMap {
     }
     return out;
   }
+  // Corridor bounds (fiesta_hip_corridor_bounds, include/fiesta_hip.h): the `bounds` of RefinePaths for the voxel polylines of a CSR
+  // batch and the CorridorSet PathCorridor returned for them -- per waypoint its corridor box, intersected with the next one where
+  // the path changes boxes, `inset` metres taken off every upper face (negative: resolution * 2^-20, so that a waypoint clamped onto
+  // an upper face stays in the box's last voxel).  ok says per path whether the corridor is whole and no box is skipped: every
+  // refined segment of such a path stays in traversable space.  With void_broken the rows of the other paths are NaN, which
+  // RefinePaths reports INVALID and leaves alone.  box: per waypoint the index of its box in the CorridorSet, -1 if it has none.
+  struct BoundsSet {
+    std::vector<double> bounds;  // 6 per waypoint: lo xyz, hi xyz, metres
+    std::vector<int32_t> ok;     // per path
+    std::vector<int64_t> box;    // per waypoint
+  };
+  BoundsSet CorridorBounds(const std::vector<int32_t> &waypoints_vox, const std::vector<int64_t> &offsets, const CorridorSet &corridor, double inset = -1 /* resolution·2⁻²⁰ */, bool void_broken = false) {
+    Flush();
+    if (offsets.empty() || waypoints_vox.size() % 3 != 0) throw std::invalid_argument("CorridorBounds: offsets needs n_paths + 1 entries, waypoints 3 each");
+    const size_t n = offsets.size() - 1, nw = waypoints_vox.size() / 3, nb = corridor.entry.size();
+    if (corridor.offsets.size() != n + 1 || corridor.status.size() != n || corridor.boxes.size() != 6 * nb || corridor.pos.size() != 6 * nb)
+      throw std::invalid_argument("CorridorBounds: the corridor does not describe this batch");
+    BoundsSet out;
+    out.bounds.assign(6 * nw + 1, 0.0), out.ok.assign(n + 1, 0), out.box.assign(nw + 1, -1);
+    const fiesta_hip_bounds_result r{out.bounds.data(), out.ok.data(), out.box.data()};
+    ck(fiesta_hip_corridor_bounds(h_, nw ? waypoints_vox.data() : nullptr, (int64_t)nw, offsets.data(), (int64_t)n, corridor.offsets.data(),
+                                  nb ? corridor.boxes.data() : nullptr, nb ? corridor.pos.data() : nullptr, nb ? corridor.entry.data() : nullptr,
+                                  corridor.status.data(), (int64_t)nb, inset < 0 ? res_ * 0x1p-20 : inset, void_broken ? FIESTA_HIP_BOUNDS_VOID_BROKEN : 0, &r));
+    out.bounds.resize(6 * nw), out.ok.resize(n), out.box.resize(nw);
+    return out;
+  }
   // Path refinement (fiesta_hip_path_refine, include/fiesta_hip.h): every path of the CSR batch (waypoints: 3 doubles each, metres,
   // e.g. ReachPathSet::pos and ::offsets) takes p.iterations projected-gradient steps on p.w_obstacle * sum (margin - d)^2 +
   // p.w_smooth * sum |second difference|^2 over its interior waypoints, each clamped to its row of `bounds` (6 doubles per waypoint:

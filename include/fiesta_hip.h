@@ -133,7 +133,8 @@ const char *fiesta_hip_last_error(void);
  * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev], fiesta_hip_ray_query[_dev], fiesta_hip_reach_field[_dev] and
  * fiesta_hip_reach_paths[_dev] came later without a new number, and so did fiesta_hip_cluster_voxels[_dev],
  * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_site_tour[_dev], fiesta_hip_free_boxes[_dev],
- * fiesta_hip_path_corridor[_dev] and fiesta_hip_path_refine[_dev]: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_path_corridor[_dev], fiesta_hip_path_refine[_dev] and fiesta_hip_corridor_bounds[_dev]: detect them by symbol lookup
+ * (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -995,6 +996,74 @@ int fiesta_hip_path_refine(fiesta_hip_map *m, const double *waypoints, int64_t n
 int fiesta_hip_path_refine_dev(fiesta_hip_map *m, const double *waypoints_dev, int64_t n_waypoints, const int64_t *offsets_dev,
                                int64_t n_paths, const double *bounds_dev, const fiesta_hip_refine_params *params,
                                const fiesta_hip_refine_result *result);
+
+/* ---- corridor bounds: per waypoint of a voxel polyline the box fiesta_hip_path_refine clamps it to, on the device ----
+ * The link between fiesta_hip_path_corridor and fiesta_hip_path_refine: it turns a corridor into the `bounds` argument of the
+ * refinement, and says per path whether refining inside those bounds is safe.  It reads no voxel: a pure function of the path
+ * batch and the corridor arrays (the map lends its stream and scratch), the same on array and hash maps.  No reference counterpart.
+ * fiesta_hip_version() is still 101: detect these two calls by symbol lookup.  fiesta_amd.corridor_bounds_model (numpy) is the
+ * definition.
+ * Inputs:
+ *   waypoints_vox  int32 x 3 x n_waypoints.
+ *   offsets        int64 x (n_paths + 1): the CSR batch that fiesta_hip_path_corridor took.
+ *   the corridor call's outputs for that batch: box_offsets, int64 x (n_paths + 1); boxes, int32 x 6; boxes_pos, f64 x 6; entry,
+ *                  int32; status, int32 per path.
+ *   n_boxes        the number of box rows actually present in the per-box arrays: min(total, the corridor call's capacity).
+ *   inset          f64, metres, finite and >= 0.
+ *   flags          0 or FIESTA_HIP_BOUNDS_VOID_BROKEN.
+ * Per path p with waypoint range [o0, o1) and box range [b0, b1):
+ *   1. The chain index is c_0 = 0, c_{i+1} = c_i + |w_{i+1} - w_i|_1, accumulated in int64.
+ *   2. b(i) is the last box of the path with entry <= c_i.
+ *   3. ok = (status == FIESTA_HIP_CORRIDOR_OK).  It is cleared if some b(i+1) > b(i) + 1.
+ *   4. ok is also cleared if b(1) = b(0) + 1 and w_0 lies outside the integer box b(0) + 1.
+ *   5. Row i is boxes_pos[b(i)].
+ *   6. On an ok path, where b(i+1) = b(i) + 1, row i is intersected with boxes_pos[b(i) + 1]: lo is the componentwise larger, hi
+ *      the componentwise smaller.  Both are written as comparisons, a > b ? a : b and a < b ? a : b (a: row i, b: the other box),
+ *      so that the result is ruled bit for bit.
+ *   7. Then inset is subtracted from the three upper faces of every row: one f64 subtraction with no contraction.
+ * Special cases:
+ *   A path with waypoints but no box gets NaN rows.  An empty path writes nothing, and its ok follows its status.
+ *   With flags & FIESTA_HIP_BOUNDS_VOID_BROKEN every row of a path that is not ok is NaN: fiesta_hip_path_refine then reports that
+ *   path INVALID and leaves it alone, so the chain stays on the device with no host-side masking.
+ *   The entries of a path are trusted to be non-decreasing and to start at 0, as the corridor call writes them.  Whatever the
+ *   entries hold, every index is clamped into [b0, b1): no read ever leaves the arrays.
+ * Outputs; every pointer of the result is nullable:
+ *   bounds  f64 x 6 per waypoint (lo xyz, hi xyz): exactly the bounds argument of fiesta_hip_path_refine.
+ *   ok      int32 per path.
+ *   box     int64 per waypoint: the global index of b(i), or -1 where there is none (which box constrains which waypoint).
+ * _dev only: no whole-call refusal of offsets is possible on the device.  A path whose waypoint offsets break path clearance's
+ *   offset rule (its start is not the running maximum of the in-range entries before it, or its range is reversed or leaves
+ *   [0, n_waypoints]) gets ok = 0, and so does a path whose box range decreases, is negative, or ends above n_boxes (a truncated
+ *   corridor).  Such a path reads nothing and writes no row.  The call first fills bounds with NaN and box with -1, so rows that
+ *   belong to no valid path are NaN / -1 and deterministic.
+ * Host variant: it refuses such offsets (offsets[0] != 0, decreasing, offsets[n_paths] != n_waypoints; a box range that decreases,
+ *   is negative or ends above n_boxes) as a whole-call error.  It stages, enqueues exactly what _dev enqueues, and synchronises once
+ *   (no host route for small batches: always the device).
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable; each is checked before the map handle is
+ *   looked at): negative counts, more than 2^30 paths; a required input NULL while its count is > 0 (waypoints_vox: n_waypoints;
+ *   offsets, box_offsets, status: n_paths; boxes, boxes_pos, entry: n_boxes); result NULL; inset NaN, negative or infinite; unknown
+ *   flag bits.  n_paths = 0 does nothing.
+ * Guarantees: every output has the model's bits for any launch shape and scheduling (integers, comparisons and one subtraction; no
+ *   atomics).  On inputs that fiesta_amd.corridor_bounds accepts, holding no negative zero, and with the same explicit inset,
+ *   bounds equals its result bit for bit and ok equals it exactly.
+ * fiesta_hip_corridor_bounds      host arrays.
+ * fiesta_hip_corridor_bounds_dev  every array, input and output, is a device pointer (the result struct itself is a host object);
+ *                                 only enqueued on the map's stream: the fill, the offset check, one kernel.  The outputs may
+ *                                 feed fiesta_hip_path_refine_dev on the same map with nothing in between.  There is no shard-group
+ *                                 call. */
+#define FIESTA_HIP_BOUNDS_VOID_BROKEN 1
+typedef struct fiesta_hip_bounds_result { /* every pointer nullable */
+  double *bounds; /* n_waypoints x 6: lo xyz, hi xyz, metres */
+  int32_t *ok;    /* n_paths */
+  int64_t *box;   /* n_waypoints */
+} fiesta_hip_bounds_result;
+int fiesta_hip_corridor_bounds(fiesta_hip_map *m, const int32_t *waypoints_vox, int64_t n_waypoints, const int64_t *offsets, int64_t n_paths,
+                               const int64_t *box_offsets, const int32_t *boxes, const double *boxes_pos, const int32_t *entry,
+                               const int32_t *status, int64_t n_boxes, double inset, int32_t flags, const fiesta_hip_bounds_result *result);
+int fiesta_hip_corridor_bounds_dev(fiesta_hip_map *m, const int32_t *waypoints_vox_dev, int64_t n_waypoints, const int64_t *offsets_dev,
+                                   int64_t n_paths, const int64_t *box_offsets_dev, const int32_t *boxes_dev, const double *boxes_pos_dev,
+                                   const int32_t *entry_dev, const int32_t *status_dev, int64_t n_boxes, double inset, int32_t flags,
+                                   const fiesta_hip_bounds_result *result);
 
 /* ---- voxel clusters: the connected groups of a voxel list, with per-cluster statistics, on the device ----
  * The step between fiesta_hip_get_frontier_voxels and fiesta_hip_reach_field: a planner does not visit frontier voxels, it visits
