@@ -165,6 +165,19 @@ class ClusterInfo(C.Structure):
                 ("n_dropped_clusters", C.c_int64), ("largest", C.c_int64)]
 
 
+class SplitResult(C.Structure):
+    """fiesta_hip_split_result: one array per output of fiesta_hip_split_clusters, every pointer nullable"""
+    _fields_ = [("parent", C.c_void_p), ("depth", C.c_void_p), ("size", C.c_void_p), ("root", C.c_void_p), ("box_lo", C.c_void_p),
+                ("box_hi", C.c_void_p), ("centroid", C.c_void_p), ("mask_or", C.c_void_p), ("key_min", C.c_void_p), ("key_argmin", C.c_void_p),
+                ("offsets", C.c_void_p), ("members", C.c_void_p), ("label", C.c_void_p)]
+
+
+class SplitInfo(C.Structure):
+    """fiesta_hip_split_info: the totals of one fiesta_hip_split_clusters call, whatever the capacity"""
+    _fields_ = [("n_parts", C.c_int64), ("n_members", C.c_int64), ("n_split_clusters", C.c_int64), ("n_oversize", C.c_int64),
+                ("largest", C.c_int64), ("depth", C.c_int64), ("status", C.c_int64)]
+
+
 class ViewSet(C.Structure):
     """fiesta_hip_view_set: the candidate views of fiesta_hip_view_coverage, explicit (pos, dir, group, n_views) or ring (centroid, ring, n_ring)"""
     _fields_ = [("pos", C.c_void_p), ("dir", C.c_void_p), ("group", C.c_void_p), ("n_views", C.c_int64), ("centroid", C.c_void_p),
@@ -306,6 +319,8 @@ def load():
         "fiesta_hip_corridor_bounds_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, dbl, i32, vp]),
         "fiesta_hip_cluster_voxels": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, i64, vp, vp]),
         "fiesta_hip_cluster_voxels_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, i32, i64, i64, vp, vp]),
+        "fiesta_hip_split_clusters": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, i64, i64, i32, i32, i32, i64, vp, vp]),
+        "fiesta_hip_split_clusters_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i64, vp, vp]),
         "fiesta_hip_view_coverage": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, vp]),
         "fiesta_hip_view_coverage_dev": (C.c_int, [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp]),
         "fiesta_hip_get_occupancy_vox": (C.c_int, [vp, vp, i64, vp]),

@@ -7,7 +7,7 @@
 #include <string>
 
 #include "../../include/fiesta_hip.h"
-#include "bounds_kernels.hpp"  // (the twelve planner headers: for the calls' argument aggregates; no kernel is used here)
+#include "bounds_kernels.hpp"  // (the thirteen planner headers: for the calls' argument aggregates; no kernel is used here)
 #include "cluster_kernels.hpp"
 #include "corridor_kernels.hpp"
 #include "dense_map.hpp"
@@ -20,6 +20,7 @@
 #include "reach_path_kernels.hpp"
 #include "refine_kernels.hpp"
 #include "shard_group.hpp"
+#include "split_kernels.hpp"
 #include "tour_kernels.hpp"
 #include "view_kernels.hpp"
 
@@ -261,6 +262,38 @@ void cluster_voxels(fiesta_hip_map *m, const fiesta::ClusterArgs &a) {
   need(a.vox != nullptr || a.n == 0, "cluster_voxels: vox is null");
   need(m != nullptr, "null map handle");
   on_store(m, [&](auto &s) { s.cluster_voxels(a); });
+}
+// fiesta_hip_split_clusters: none of these errors needs a device, and all are checked before the handle is touched (a host batch: the
+// data errors as well -- the _dev variant finds those on the device and reports them in info.status)
+void split_clusters(fiesta_hip_map *m, const fiesta::SplitArgs &a) {
+  constexpr int64_t cap = 1ll << 24;
+  need(a.info != nullptr, "split_clusters: info is null");
+  need(a.n >= 0 && a.n <= cap, "split_clusters: the entry count must lie in 0 .. 2^24");
+  need(a.n_clusters >= 0 && a.n_clusters <= cap, "split_clusters: the cluster count must lie in 0 .. 2^24");
+  need(a.n_members >= 0 && a.n_members <= cap, "split_clusters: the member count must lie in 0 .. 2^24");
+  need(a.max_size >= 0, "split_clusters: max_size must be >= 0");
+  need(a.max_extent >= 0, "split_clusters: max_extent must be >= 0");
+  need(a.max_depth >= 0 && a.max_depth <= FIESTA_HIP_SPLIT_MAX_DEPTH, "split_clusters: max_depth must lie in 0 .. 63");
+  need(a.part_capacity >= 0, "split_clusters: negative capacity");
+  need(a.vox != nullptr || a.n == 0, "split_clusters: vox is null");
+  need(a.offsets != nullptr || a.n_clusters == 0, "split_clusters: offsets is null");
+  need(a.members != nullptr || a.n_members == 0, "split_clusters: members is null");
+  if (!a.dev && a.n_clusters > 0) {
+    const int64_t m0 = a.offsets[0], m1 = a.offsets[a.n_clusters];
+    need(m0 >= 0, "split_clusters: offsets[0] is negative");
+    need(m1 <= a.n_members, "split_clusters: offsets[n_clusters] is above n_members");
+    for (int64_t k = 0; k < a.n_clusters; ++k) need(a.offsets[k] <= a.offsets[k + 1], "split_clusters: offsets must be non-decreasing");
+    constexpr int lim = (1 << 20) - 1;
+    for (int64_t j = m0; j < m1; ++j) {
+      const int64_t i = a.members[j];
+      need(i >= 0 && i < a.n, "split_clusters: a member index lies outside the entry list");
+      const int32_t *v = a.vox + 3 * i;
+      need(v[0] > -lim && v[0] < lim && v[1] > -lim && v[1] < lim && v[2] > -lim && v[2] < lim,
+           "split_clusters: a member's voxel breaks the coordinate limit (|c| < 2^20 - 1)");
+    }
+  }
+  need(m != nullptr, "null map handle");
+  on_store(m, [&](auto &s) { s.split_clusters(a); });
 }
 // none of these errors needs a device
 void view_coverage(fiesta_hip_map *m, const fiesta::ViewArgs &a) {
@@ -713,6 +746,22 @@ int fiesta_hip_path_corridor_dev(fiesta_hip_map *m, const int32_t lo[3], const i
                                  int32_t flags, int64_t capacity, const fiesta_hip_corridor_result *result) {
   return guarded([&] {
     corridor(m, {true, lo, hi, waypoints_vox_dev, n_waypoints, offsets_dev, n_paths, min_clearance, max_grow, flags, capacity, nullptr, result, true});
+  });
+}
+int fiesta_hip_split_clusters(fiesta_hip_map *m, const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const int64_t *offsets,
+                              const int64_t *members, int64_t n_clusters, int64_t n_members, int32_t max_size, int32_t max_extent,
+                              int32_t max_depth, int64_t part_capacity, const fiesta_hip_split_result *result, fiesta_hip_split_info *info) {
+  return guarded([&] {
+    split_clusters(m, {vox, mask, key, n, offsets, members, n_clusters, nullptr, n_members, max_size, max_extent, max_depth, part_capacity, result, info, false});
+  });
+}
+int fiesta_hip_split_clusters_dev(fiesta_hip_map *m, const int32_t *vox_dev, const uint8_t *mask_dev, const int32_t *key_dev, int64_t n,
+                                  const int64_t *offsets_dev, const int64_t *members_dev, int64_t n_clusters, const int64_t *n_clusters_dev,
+                                  int64_t n_members, int32_t max_size, int32_t max_extent, int32_t max_depth, int64_t part_capacity,
+                                  const fiesta_hip_split_result *result, fiesta_hip_split_info *info_dev) {
+  return guarded([&] {
+    split_clusters(m, {vox_dev, mask_dev, key_dev, n, offsets_dev, members_dev, n_clusters, n_clusters_dev, n_members, max_size, max_extent, max_depth,
+                       part_capacity, result, info_dev, true});
   });
 }
 int fiesta_hip_cluster_voxels(fiesta_hip_map *m, const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, int32_t connectivity,

@@ -88,6 +88,14 @@ struct ClusterScratch {
   DevBuf<uint32_t> mor;
 };
 
+// scratch of fiesta_hip_split_clusters (split_kernels.hpp), owned by a map, O(n_members): three pools that one call carves into the two
+// member / part buffer sets, the per-part records, boxes and accumulators, the flag bytes, their scan and the counters
+struct SplitScratch {
+  DevBuf<int32_t> i32;
+  DevBuf<unsigned long long> u64;
+  DevBuf<uint8_t> u8;
+};
+
 // scratch of fiesta_hip_view_coverage (view_kernels.hpp), owned by a map: the ring form's expanded views, the per-view pair counts
 // and their scan, the per-view and per-group accumulators and four counters; O(views + groups), grown on demand, freed with the map
 struct ViewScratch {
@@ -106,6 +114,7 @@ struct PlannerScratch {
   ReachMatrixScratch reach_matrix;
   TourScratch tour;
   ClusterScratch cluster;
+  SplitScratch split;
   ViewScratch view;
 };
 
@@ -156,6 +165,7 @@ struct PathRefineArgs;
 struct CorridorBoundsArgs;
 struct TourArgs;
 struct ClusterArgs;
+struct SplitArgs;
 struct ViewArgs;
 
 // Device-side counters, one 64-bit word each.
@@ -269,6 +279,7 @@ class DenseMap {
   void corridor(const CorridorArgs &a);
   void corridor_bounds(const CorridorBoundsArgs &a);
   void cluster_voxels(const ClusterArgs &a);
+  void split_clusters(const SplitArgs &a);
   void view_coverage(const ViewArgs &a);
   int64_t count_no_obstacle();
   void slice_distances(int z_vox, double *out);        // nx * ny doubles, x-major

@@ -29,6 +29,7 @@
 #include "corridor_kernels.hpp"
 #include "tour_kernels.hpp"
 #include "cluster_kernels.hpp"
+#include "split_kernels.hpp"
 #include "view_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
@@ -1628,9 +1629,10 @@ void HashMap::reach_matrix(const ReachMatrixArgs &a) {
   reach_matrix_run(stream_, planner_, reach_source(tab), blo, bhi, off, a);
 }
 
-// fiesta_hip_reach_paths[_dev] and fiesta_hip_cluster_voxels[_dev]: nothing of the map is read but its resolution and origin
+// fiesta_hip_reach_paths[_dev], fiesta_hip_cluster_voxels[_dev] and fiesta_hip_split_clusters[_dev]: nothing of the map is read but its resolution and origin
 void HashMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
 void HashMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
+void HashMap::split_clusters(const SplitArgs &a) { use_device(), split_clusters_run(stream_, planner_, g_.res, g_.org, a); }
 // fiesta_hip_corridor_bounds[_dev] (bounds_kernels.hpp): nothing of the map is read at all
 void HashMap::corridor_bounds(const CorridorBoundsArgs &a) {
   if (a.n_paths <= 0) return;

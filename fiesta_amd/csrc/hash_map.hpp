@@ -91,6 +91,7 @@ class HashMap {
   void corridor(const CorridorArgs &a);
   void corridor_bounds(const CorridorBoundsArgs &a);
   void cluster_voxels(const ClusterArgs &a);
+  void split_clusters(const SplitArgs &a);
   void view_coverage(const ViewArgs &a);
   // every voxel of every allocated page, page order: vox (map voxel coordinates), d2, coc, occ; returns the count
   int64_t download(int32_t *vox, int32_t *d2, int32_t *coc, uint8_t *occ);

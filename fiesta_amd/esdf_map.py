@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterInfo, ClusterResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, BoundsResult, Stats, TourInfo, TourResult, check
+from ._lib import ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, BoundsResult, Stats, TourInfo, TourResult, check
 from .refine_model import BOUNDS_VOID_BROKEN
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
@@ -45,6 +45,9 @@ PATH_FIELDS = (("min_dist", np.float64, ()), ("min_index", np.int64, ()), ("min_
 # the per-cluster arrays of fiesta_hip_cluster_result, in struct order (label before, offsets and members after them)
 CLUSTER_FIELDS = (("size", np.int32, ()), ("root", np.int64, ()), ("box_lo", np.int32, (3,)), ("box_hi", np.int32, (3,)),
                   ("centroid", np.float64, (3,)), ("mask_or", np.uint8, ()), ("key_min", np.int32, ()), ("key_argmin", np.int64, ()))
+# the per-part arrays of fiesta_hip_split_result, in struct order (offsets, members and label after them)
+SPLIT_FIELDS = (("parent", np.int32, ()), ("depth", np.uint8, ())) + CLUSTER_FIELDS
+SPLIT_INFO_KEYS = ("n_parts", "n_members", "n_split_clusters", "n_oversize", "largest", "deepest", "status")   # fiesta_hip_split_info, as the dicts name it
 # the arrays of fiesta_hip_view_result, in struct order: (name, dtype, which count sizes it)
 VIEW_FIELDS = (("view_class", np.uint8, "views"), ("n_in_view", np.int32, "views"), ("n_visible", np.int32, "views"),
                ("cover_count", np.int32, "entries"), ("first_view", np.int32, "entries"), ("best_view", np.int64, "groups"),
@@ -1093,6 +1096,60 @@ class ESDFMap:
                                                       int(min_size), int(cluster_capacity), int(member_capacity), C.byref(res),
                                                       C.c_void_p(info_dev_ptr or None)))
 
+    def SplitClusters(self, vox, offsets, members, mask=None, key=None, max_size=0, max_extent=0, max_depth=63) -> dict:
+        """fiesta_hip_split_clusters: bisect every oversize part of the clusters (offsets, members: ClusterVoxels' CSR pair over `vox`)
+        at the middle of its box's longest axis until no part holds more than `max_size` members or spans more than `max_extent`
+        voxels (0: criterion off), at most `max_depth` levels deep.  Returns per part parent (its cluster), depth, size, root, box_lo,
+        box_hi, centroid (metres), mask_or, key_min, key_argmin; the CSR pair offsets / members of the parts; label ((n,) int32, -1:
+        listed by no part); and n_parts, n_members, n_split_clusters, n_oversize, largest, deepest (fiesta_hip_split_info.depth) and
+        status.  Parts need not be connected.  fiesta_amd.split_model is the definition"""
+        v = np.ascontiguousarray(vox, dtype=np.int32).reshape(-1, 3)
+        n = len(v)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        mem = np.ascontiguousarray(members, dtype=np.int64).reshape(-1)
+        mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+        ky = None if key is None else np.ascontiguousarray(key, dtype=np.int32).reshape(-1)
+        if (mk is not None and len(mk) != n) or (ky is not None and len(ky) != n):
+            raise ValueError("mask and key need one value per entry")
+        K, M = max(len(off) - 1, 0), len(mem)
+        info = SplitInfo()
+        label = np.empty(n, np.int32)
+        out_members = np.empty(M, np.int64)
+        cap = min(M, max(K, 1 << 12))   # (one call serves unless there are more parts than this, then a second one with the total)
+        while True:
+            out = {name: np.empty((cap,) + shape, dtype) for name, dtype, shape in SPLIT_FIELDS}
+            out["offsets"] = np.zeros(cap + 1, np.int64)
+            res = SplitResult(*[out[name].ctypes.data for name, _, _ in SPLIT_FIELDS], out["offsets"].ctypes.data, out_members.ctypes.data,
+                              label.ctypes.data)
+            check(self._lib.fiesta_hip_split_clusters(self._h, _p(v) if n else None, _p(mk), _p(ky), n, _p(off) if K else None, _p(mem) if M else None,
+                                                      K, M, int(max_size), int(max_extent), int(max_depth), cap, C.byref(res), C.byref(info)))
+            if info.n_parts <= cap:
+                break
+            cap = int(info.n_parts)
+        k = int(info.n_parts)
+        out = {name: a[:k + 1] if name == "offsets" else a[:k] for name, a in out.items()}
+        out["label"], out["members"] = label, out_members[:int(info.n_members)]
+        out.update(self._split_info(info))
+        return out
+
+    @staticmethod
+    def _split_info(info) -> dict:
+        return dict(zip(SPLIT_INFO_KEYS, (int(getattr(info, k)) for k, _ in SplitInfo._fields_)))
+
+    def SplitClustersDevice(self, vox_dev_ptr: int, n: int, offsets_dev_ptr: int, members_dev_ptr: int, n_clusters: int, n_members: int,
+                            info_dev_ptr: int, mask_dev_ptr: int = 0, key_dev_ptr: int = 0, n_clusters_dev_ptr: int = 0, max_size=0, max_extent=0,
+                            max_depth=63, part_capacity: int = 0, out=None):
+        """fiesta_hip_split_clusters_dev: every array resident on the device (`out` maps field names of fiesta_hip_split_result to
+        device pointers, missing fields are not written; info_dev_ptr: a device fiesta_hip_split_info, seven int64).
+        n_clusters_dev_ptr: a device int64, the cluster count is min(n_clusters, that) -- ClusterVoxelsDevice's info.  The outputs
+        must not overlap the inputs.  Only enqueued on the map's stream"""
+        out = out or {}
+        res = SplitResult(*[int(out.get(name, 0)) or None for name, _ in SplitResult._fields_])
+        vp = lambda v: C.c_void_p(int(v) or None)  # noqa: E731
+        check(self._lib.fiesta_hip_split_clusters_dev(self._h, vp(vox_dev_ptr), vp(mask_dev_ptr), vp(key_dev_ptr), int(n), vp(offsets_dev_ptr),
+                                                      vp(members_dev_ptr), int(n_clusters), vp(n_clusters_dev_ptr), int(n_members), int(max_size),
+                                                      int(max_extent), int(max_depth), int(part_capacity), C.byref(res), vp(info_dev_ptr)))
+
     def _frontier_alloc(self) -> dict:
         """the device buffers FrontierClusters and FrontierViews share (torch tensors of self._frontier_capacity entries), made on demand"""
         import torch
@@ -1110,23 +1167,67 @@ class ESDFMap:
             self._frontier_buffers = b
         return b
 
-    def FrontierClusters(self, lo=None, hi=None, min_clearance=0.0, connectivity=26, min_size=1) -> dict:
+    def _split_alloc(self, b) -> dict:
+        """the device buffers of the parts in FrontierClusters / FrontierViews (made with the first call that splits)"""
+        import torch
+        sp = b.get("split")
+        if sp is None:
+            dev = torch.device("cuda", self.device)
+            cap = b["label"].shape[0]
+            sp = {"label": torch.empty(cap, dtype=torch.int32, device=dev), "members": torch.empty(cap, dtype=torch.int64, device=dev),
+                  "offsets": torch.empty(cap + 1, dtype=torch.int64, device=dev), "info": torch.zeros(len(SplitInfo._fields_), dtype=torch.int64, device=dev)}
+            for name, dtype, shape in SPLIT_FIELDS:
+                sp[name] = torch.empty((cap,) + shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
+            torch.cuda.synchronize(dev)   # (the map's stream does not wait for torch's)
+            b["split"] = sp
+        return sp
+
+    def _split_enqueue(self, b, sp, cluster_capacity, part_capacity, max_size, max_extent, max_depth):
+        """SplitClustersDevice on the cluster call's buffers `b` into the part buffers `sp`: the cluster count comes from the device"""
+        cap = b["label"].shape[0]
+        self.SplitClustersDevice(b["vox"].data_ptr(), cap, b["offsets"].data_ptr(), b["members"].data_ptr(), cluster_capacity, cap,
+                                 sp["info"].data_ptr(), mask_dev_ptr=b["mask"].data_ptr(), n_clusters_dev_ptr=b["head"].data_ptr() + 8,
+                                 max_size=max_size, max_extent=max_extent, max_depth=max_depth, part_capacity=part_capacity,
+                                 out={name: sp[name].data_ptr() for name, _ in SplitResult._fields_})
+
+    @staticmethod
+    def _split_results(out, sp, n):
+        """replace the per-cluster entries of `out` by the parts'; returns the number of parts"""
+        info = dict(zip(SPLIT_INFO_KEYS, (int(x) for x in sp["info"].cpu().numpy())))
+        if info["status"] != 0:
+            raise ValueError("the clusters handed to the split were broken (fiesta_hip_split_info.status INVALID)")
+        k = info["n_parts"]
+        for name, _, _ in SPLIT_FIELDS:
+            out[name] = sp[name][:k].cpu().numpy()
+        out["offsets"] = sp["offsets"][:k + 1].cpu().numpy()
+        out["members"] = sp["members"][:info["n_members"]].cpu().numpy()
+        out["label"] = sp["label"][:n].cpu().numpy()
+        out.update(info)
+        return k
+
+    def FrontierClusters(self, lo=None, hi=None, min_clearance=0.0, connectivity=26, min_size=1, max_size=0, max_extent=0, max_depth=63) -> dict:
         """GetFrontierVoxels and ClusterVoxels as one chain on the device: the frontier sweep writes into device buffers this object
         keeps (torch tensors, grown on demand), its device counter feeds the clustering, and the host waits ONCE, at the end, before
         it copies the results back: vox, mask, and everything ClusterVoxels returns for that list.  Only when the buffers turn out too
-        small for the frontier (the first call, a frontier that grew by more than a quarter) is the chain run a second time."""
+        small for the frontier (the first call, a frontier that grew by more than a quarter) is the chain run a second time.
+        With max_size or max_extent above 0 SplitClusters runs between the two, in the same buffers and with the same single wait:
+        the results then describe the PARTS (plus parent, depth and SplitClusters' totals), n_clusters stays the unsplit count."""
         import torch
         if (lo is None) != (hi is None):
             raise ValueError("lo and hi must both be given or both be None")
         dev = torch.device("cuda", self.device)
+        split = max_size > 0 or max_extent > 0
         while True:
             b = self._frontier_alloc()
             cap = b["label"].shape[0]
             head = b["head"].data_ptr()
+            sp = self._split_alloc(b) if split else None
             self.GetFrontierVoxelsDevice(lo, hi, min_clearance, b["vox"].data_ptr(), b["mask"].data_ptr(), cap, head)
             outs = {name: b[name].data_ptr() for name, _ in ClusterResult._fields_}
             self.ClusterVoxelsDevice(b["vox"].data_ptr(), cap, head + 8, mask_dev_ptr=b["mask"].data_ptr(), n_dev_ptr=head,
                                      connectivity=connectivity, min_size=min_size, cluster_capacity=cap, member_capacity=cap, out=outs)
+            if split:
+                self._split_enqueue(b, sp, cap, cap, max_size, max_extent, max_depth)
             self.synchronize()
             h = b["head"].cpu().numpy()
             n = int(h[0])
@@ -1142,6 +1243,8 @@ class ESDFMap:
         out["members"] = b["members"][:info["n_members"]].cpu().numpy()
         out["vox"], out["mask"], out["label"] = b["vox"][:n].cpu().numpy(), b["mask"][:n].cpu().numpy(), b["label"][:n].cpu().numpy()
         out.update(info)
+        if split:
+            self._split_results(out, sp, n)
         return out
 
     @staticmethod
@@ -1219,8 +1322,11 @@ class ESDFMap:
                                                      int(n_members), C.byref(vs), C.byref(sn), C.byref(res), C.c_void_p(info_dev_ptr or None)))
 
     def FrontierViews(self, lo=None, hi=None, min_clearance=0.0, connectivity=26, min_size=1, ring=None, min_range=0.0, max_range=np.inf,
-                      tan_h=np.inf, tan_v=np.inf, block_mask=1, omni=False, view_clearance=0.0, min_visible=1) -> dict:
-        """GetFrontierVoxels, ClusterVoxels and ViewCoverage (ring form: `ring` around every cluster's centroid, against the cluster's
+                      tan_h=np.inf, tan_v=np.inf, block_mask=1, omni=False, view_clearance=0.0, min_visible=1, max_size=0, max_extent=0,
+                      max_depth=63) -> dict:
+        """With max_size or max_extent above 0 SplitClusters runs between clustering and coverage, as in FrontierClusters: the rings
+        then stand around the PARTS' centroids and every per-cluster result describes a part.
+        GetFrontierVoxels, ClusterVoxels and ViewCoverage (ring form: `ring` around every cluster's centroid, against the cluster's
         own members) as one chain on the device, in FrontierClusters' buffers: the frontier counter feeds the clustering, the cluster
         count and the CSR pair feed the coverage, and the host waits ONCE, at the end -- after a wait for torch's stream when a new ring
         was uploaded or buffers were made (the first call with a ring), and unless the buffers turn out too small for the
@@ -1237,9 +1343,13 @@ class ESDFMap:
         if fresh:
             self._view_ring = (rg.tobytes(), torch.from_numpy(rg).to(dev) if M else torch.zeros((1, 5), dtype=torch.float64, device=dev))
         ring_dev = self._view_ring[1]
+        split = max_size > 0 or max_extent > 0
         while True:
             b = self._frontier_alloc()
             cap = b["label"].shape[0]
+            if split and "split" not in b:
+                fresh = True
+            sp = self._split_alloc(b) if split else None
             # the clusters get a capacity of their own (they are few): it sizes the views, kcap * len(ring) of them
             kcap = min(cap, self._view_cluster_capacity)
             if kcap * max(M, 1) > 1 << 24:
@@ -1261,10 +1371,15 @@ class ESDFMap:
             outs = {name: b[name].data_ptr() for name, _ in ClusterResult._fields_}
             self.ClusterVoxelsDevice(b["vox"].data_ptr(), cap, head + 8, mask_dev_ptr=b["mask"].data_ptr(), n_dev_ptr=head,
                                      connectivity=connectivity, min_size=min_size, cluster_capacity=kcap, member_capacity=cap, out=outs)
-            # (kcap groups; the device count -- info.n_clusters at head + 8 -- cuts them down to the clusters there are)
-            self.ViewCoverageDevice(b["vox"].data_ptr(), cap, vb["info"].data_ptr(), centroid_dev_ptr=b["centroid"].data_ptr(),
-                                    ring_dev_ptr=ring_dev.data_ptr(), n_ring=M, offsets_dev_ptr=b["offsets"].data_ptr(),
-                                    members_dev_ptr=b["members"].data_ptr(), n_groups=kcap, n_groups_dev_ptr=head + 8, n_members=cap,
+            g = b
+            if split:   # (the groups are the parts: their count -- info.n_parts -- and arrays come from the split's buffers)
+                self._split_enqueue(b, sp, kcap, kcap, max_size, max_extent, max_depth)
+                g = sp
+            # (kcap groups; the device count -- info.n_clusters at head + 8, or info.n_parts -- cuts them down to the groups there are)
+            self.ViewCoverageDevice(b["vox"].data_ptr(), cap, vb["info"].data_ptr(), centroid_dev_ptr=g["centroid"].data_ptr(),
+                                    ring_dev_ptr=ring_dev.data_ptr(), n_ring=M, offsets_dev_ptr=g["offsets"].data_ptr(),
+                                    members_dev_ptr=g["members"].data_ptr(), n_groups=kcap,
+                                    n_groups_dev_ptr=sp["info"].data_ptr() if split else head + 8, n_members=cap,
                                     min_range=min_range, max_range=max_range, tan_h=tan_h, tan_v=tan_v, block_mask=block_mask, omni=omni,
                                     min_clearance=view_clearance, min_visible=min_visible,
                                     out={name: vb[name].data_ptr() for name, _ in ViewResult._fields_})
@@ -1276,8 +1391,9 @@ class ESDFMap:
             if n > cap:
                 self._frontier_buffers, self._frontier_capacity = None, min(max(n + n // 4, 1024), 1 << 24)
                 continue
-            if int(h[1]) > kcap:
-                self._view_cluster_capacity = int(h[1]) + int(h[1]) // 4
+            groups = max(int(h[1]), int(sp["info"][0].item())) if split else int(h[1])
+            if groups > kcap:
+                self._view_cluster_capacity = groups + groups // 4
                 continue
             break
         info = {name: int(h[1 + i]) for i, (name, _) in enumerate(ClusterInfo._fields_)}
@@ -1287,6 +1403,8 @@ class ESDFMap:
         out["members"] = b["members"][:info["n_members"]].cpu().numpy()
         out["vox"], out["mask"], out["label"] = b["vox"][:n].cpu().numpy(), b["mask"][:n].cpu().numpy(), b["label"][:n].cpu().numpy()
         out.update(info)
+        if split:
+            k = self._split_results(out, sp, n)
         for name in ("view_class", "n_in_view", "n_visible"):
             out[name] = vb[name][:k * M].cpu().numpy()
         for name in ("cover_count", "first_view"):

@@ -605,6 +605,58 @@ class ESDFMap {
     }
     return out;
   }
+  // Cluster splitting (fiesta_hip_split_clusters, include/fiesta_hip.h): every part of a cluster that holds more than max_size members
+  // or spans more than max_extent voxels (0: criterion off) is cut at the middle of its box's longest axis, at most max_depth levels
+  // deep -- view-sized pieces of a large frontier.  offsets / members: the CSR pair of ClusterVoxels over the same `vox`; the parts
+  // come cluster-major, low before high.  Parts need not be connected.
+  struct ClusterParts {
+    std::vector<int32_t> parent;  // per part from here on: the cluster it was cut from
+    std::vector<uint8_t> depth;
+    std::vector<int32_t> size;
+    std::vector<int64_t> root;
+    std::vector<Eigen::Vector3i> box_lo, box_hi;  // inclusive
+    std::vector<Eigen::Vector3d> centroid;        // metres
+    std::vector<uint8_t> mask_or;
+    std::vector<int32_t> key_min;
+    std::vector<int64_t> key_argmin;
+    std::vector<int64_t> offsets, members;
+    std::vector<int32_t> label;  // per entry: the last part that lists it; -1: none
+    fiesta_hip_split_info info{};
+    size_t count() const { return size.size(); }
+  };
+  ClusterParts SplitClusters(const std::vector<Eigen::Vector3i> &vox, const std::vector<int64_t> &offsets, const std::vector<int64_t> &members,
+                             const std::vector<uint8_t> *mask = nullptr, const std::vector<int32_t> *key = nullptr, int32_t max_size = 0,
+                             int32_t max_extent = 0, int32_t max_depth = FIESTA_HIP_SPLIT_MAX_DEPTH) {
+    Flush();
+    const int64_t n = (int64_t)vox.size(), K = offsets.empty() ? 0 : (int64_t)offsets.size() - 1, M = (int64_t)members.size();
+    if ((mask && (int64_t)mask->size() != n) || (key && (int64_t)key->size() != n))
+      throw std::invalid_argument("SplitClusters: mask and key need one value per entry");
+    std::vector<int32_t> v;
+    for (const auto &p : vox) v.insert(v.end(), {p(0), p(1), p(2)});
+    const int32_t *vp = v.empty() ? nullptr : v.data();
+    const uint8_t *mp = mask && n ? mask->data() : nullptr;
+    const int32_t *kp = key && n ? key->data() : nullptr;
+    const int64_t *op = K ? offsets.data() : nullptr, *bp = M ? members.data() : nullptr;
+    ClusterParts out;
+    ck(fiesta_hip_split_clusters(h_, vp, mp, kp, n, op, bp, K, M, max_size, max_extent, max_depth, 0, nullptr, &out.info));  // sizes the buffers
+    const size_t k = (size_t)out.info.n_parts;
+    out.label.assign((size_t)n + 1, -1);  // (one spare entry in every array: never a null pointer)
+    out.parent.assign(k + 1, 0), out.depth.assign(k + 1, 0), out.size.assign(k + 1, 0), out.root.assign(k + 1, 0), out.mask_or.assign(k + 1, 0);
+    out.key_min.assign(k + 1, 0), out.key_argmin.assign(k + 1, 0), out.offsets.assign(k + 1, 0), out.members.assign((size_t)M + 1, 0);
+    std::vector<int32_t> lo(3 * k + 1), hi(3 * k + 1);
+    std::vector<double> cen(3 * k + 1);
+    const fiesta_hip_split_result r{out.parent.data(), out.depth.data(),   out.size.data(),       out.root.data(),    lo.data(),          hi.data(),       cen.data(),
+                                    out.mask_or.data(), out.key_min.data(), out.key_argmin.data(), out.offsets.data(), out.members.data(), out.label.data()};
+    ck(fiesta_hip_split_clusters(h_, vp, mp, kp, n, op, bp, K, M, max_size, max_extent, max_depth, (int64_t)k, &r, &out.info));
+    out.label.resize((size_t)n), out.parent.resize(k), out.depth.resize(k), out.size.resize(k), out.root.resize(k), out.mask_or.resize(k);
+    out.key_min.resize(k), out.key_argmin.resize(k), out.members.resize((size_t)out.info.n_members);
+    for (size_t c = 0; c < k; ++c) {
+      out.box_lo.push_back(Eigen::Vector3i(lo[3 * c], lo[3 * c + 1], lo[3 * c + 2]));
+      out.box_hi.push_back(Eigen::Vector3i(hi[3 * c], hi[3 * c + 1], hi[3 * c + 2]));
+      out.centroid.push_back(Eigen::Vector3d(cen[3 * c], cen[3 * c + 1], cen[3 * c + 2]));
+    }
+    return out;
+  }
   // GetFrontierVoxels and ClusterVoxels composed (both null: the whole map): the frontier voxels, their masks and their clusters
   VoxelClusters GetFrontierClusters(const Eigen::Vector3i *lo, const Eigen::Vector3i *hi, double min_clearance, int32_t connectivity,
                                     int32_t min_size, std::vector<Eigen::Vector3i> &vox, std::vector<uint8_t> *mask = nullptr) {

@@ -133,8 +133,8 @@ const char *fiesta_hip_last_error(void);
  * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev], fiesta_hip_ray_query[_dev], fiesta_hip_reach_field[_dev] and
  * fiesta_hip_reach_paths[_dev] came later without a new number, and so did fiesta_hip_cluster_voxels[_dev],
  * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_site_tour[_dev], fiesta_hip_free_boxes[_dev],
- * fiesta_hip_path_corridor[_dev], fiesta_hip_path_refine[_dev] and fiesta_hip_corridor_bounds[_dev]: detect them by symbol lookup
- * (dlsym). */
+ * fiesta_hip_path_corridor[_dev], fiesta_hip_path_refine[_dev], fiesta_hip_corridor_bounds[_dev] and
+ * fiesta_hip_split_clusters[_dev]: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -1143,6 +1143,107 @@ int fiesta_hip_cluster_voxels(fiesta_hip_map *m, const int32_t *vox, const uint8
 int fiesta_hip_cluster_voxels_dev(fiesta_hip_map *m, const int32_t *vox_dev, const uint8_t *mask_dev, const int32_t *key_dev, int64_t n,
                                   const unsigned long long *n_dev, int32_t connectivity, int32_t min_size, int64_t cluster_capacity,
                                   int64_t member_capacity, const fiesta_hip_cluster_result *result, fiesta_hip_cluster_info *info_dev);
+
+/* ---- cluster splitting: bisect large clusters into view-sized parts, on the device ----
+ * The step between fiesta_hip_cluster_voxels and fiesta_hip_view_coverage: frontier surfaces touch one another, so one cluster can
+ * hold most of a frontier, and a ring of views around the centroid of such a cluster looks at nothing.  Every frontier planner of
+ * this family cuts large frontiers into view-sized pieces before it places viewpoints; this call does that.  Read-only: nothing of
+ * the map is read but its resolution and origin, so the call is the same for dense maps, shards and hash-block maps (there is no
+ * shard-group call).  No reference counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.
+ * Inputs: the cluster call's vox (n x 3 int32), the nullable per-entry mask (uint8) and key (int32), the cluster call's CSR pair
+ *   offsets (n_clusters + 1 int64) and members (n_members int64 entry indices), and three parameters: max_size >= 0, max_extent >= 0
+ *   and 0 <= max_depth <= 63 (FIESTA_HIP_SPLIT_MAX_DEPTH).  For max_size and max_extent, 0 means the criterion is off.
+ * A PART is a multiset of member indices.  Each non-empty cluster segment members[offsets[k] .. offsets[k + 1]) starts as one part at
+ *   depth 0.  An empty segment yields no part.  For a part: its box is the tight inclusive box of its members' voxels;
+ *   extent[c] = hi[c] - lo[c] + 1.  A part is OVERSIZE if max_size > 0 && size > max_size, or if max_extent > 0 &&
+ *   max(extent) > max_extent.
+ * An oversize part at depth < max_depth is split as follows: the axis a is the one with the largest extent, ties go to the lowest
+ *   axis; mid = lo[a] + ((hi[a] - lo[a]) >> 1); members with c[a] <= mid form the low child and the rest form the high child, both
+ *   at depth + 1.  An oversize part of distinct voxels (what the cluster call lists) always has extent >= 2 on a, so both children
+ *   are non-empty, and the extent on a at least halves (rounded up).  A part whose members all name ONE voxel (a member listed
+ *   more than once) has extent 1 and is never split: if max_size calls it oversize it stays so and counts in n_oversize.  With the cluster call's coordinate limit (|c| < 2^20 - 1) no recursion is deeper than 63: max_depth = 63
+ *   never cuts anything.
+ * Parts are numbered cluster-major and, inside a cluster, in order with low before high.  That is the order of their segments in
+ *   the output members.  The numbering is a function of the member sets alone.  The order inside a part's segment is unspecified;
+ *   the set is exact.  A member listed twice counts twice.  PARTS NEED NOT BE CONNECTED: a cut plane can separate a part into
+ *   pieces that only touched through the other side.
+ * Outputs; every pointer of the result struct is nullable, and so is the struct.  The per-part arrays are written for
+ *   p < min(P, part_capacity), P the number of parts:
+ *   parent      int32: the input cluster of the part
+ *   depth       uint8
+ *   size        int32
+ *   root        int64: the lowest entry index in the part
+ *   box_lo / box_hi  3 int32 each, inclusive
+ *   centroid    3 f64, metres: ((double)sum_c / (double)size + 0.5) * resolution + origin[c], sum_c the exact int64 coordinate sum
+ *               over the part's members: exactly the cluster call's expression and operation order
+ *   mask_or     uint8, key_min int32, key_argmin int64: under the cluster call's rules, over the part's members
+ *   offsets     int64, CSR: part p occupies members[offsets[p] .. offsets[p + 1]).  part_capacity + 1 entries, of which
+ *               min(P, part_capacity) + 1 are written.  A split is a partition inside the part's own range, so offsets[0] and
+ *               offsets[P] are the input's offsets[0] and offsets[n_clusters]
+ *   members     int64, n_members entries: the positions offsets[0] .. offsets[P) are written (the host variant copies the input's
+ *               values below offsets[0]; the _dev variant leaves those positions untouched)
+ *   label       int32 per entry: filled with -1, then set to the part that lists the entry.  If several parts list an entry, the
+ *               largest part index wins.
+ *   info        whatever the capacities (so a call with part_capacity 0 sizes the buffers): n_parts = P; n_members = offsets[P];
+ *               n_split_clusters, the clusters cut at least once; n_oversize, the parts left oversize by max_depth; largest, the
+ *               size of the largest part; depth, the deepest level used; status, FIESTA_HIP_SPLIT_OK or _INVALID.
+ *   With both criteria off the call is the identity: every per-part array then equals the cluster call's per-cluster array bit for
+ *   bit.  Every value is an integer but the centroid, every reduction is exact and commutative: every output other than the order
+ *   inside a member segment has the same bits for any launch shape, and the bits of fiesta_amd.split_model (the definition in plain
+ *   Python).  OUTPUTS MUST NOT OVERLAP INPUTS (members in particular: the call reads the input members while it writes the output).
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): n, n_clusters or n_members negative or above
+ *   2^24; max_size < 0, max_extent < 0, max_depth outside 0 .. 63; vox NULL with n > 0, offsets NULL with n_clusters > 0, members
+ *   NULL with n_members > 0, info NULL; a negative part_capacity.
+ * Data errors: offsets[0] < 0, or a decreasing offset; offsets[n_clusters] > n_members; a member index outside [0, n); a member
+ *   whose voxel breaks the cluster call's coordinate limit.  On a data error the host variant returns FIESTA_HIP_ERR_INVALID.  The
+ *   _dev variant cannot refuse a batch: it sets info.status = FIESTA_HIP_SPLIT_INVALID and n_parts = 0 (every other counter 0) and
+ *   writes nothing else but the label fill -- one validation pass sets a device flag that every later kernel tests first.  This is
+ *   also how a cluster call cut off by its member_capacity shows up (its offsets end above the members that were written).
+ * The scratch memory, O(n_members) (there can never be more parts than members), belongs to the map: allocated on first use, grown
+ *   on demand, freed by fiesta_hip_destroy.
+ * fiesta_hip_split_clusters      host arrays; stages through the path queries' buffers, runs, copies back and synchronises once.
+ *                                Per-part entries at and beyond n_parts read 0.
+ * fiesta_hip_split_clusters_dev  every array, and info, is a device pointer (the result struct itself is a host object).
+ *                                n_clusters_dev, nullable: a device int64, e.g. &info_dev->n_clusters of
+ *                                fiesta_hip_cluster_voxels_dev; the effective cluster count is min(n_clusters, *n_clusters_dev), and
+ *                                the effective member count is offsets[that].  &info_dev->n_parts, offsets, members and centroid go
+ *                                straight into fiesta_hip_view_coverage_dev as n_groups_dev and the group arrays.  Only enqueued on
+ *                                the map's stream: nothing data-dependent is read back.  The host enqueues max_depth levels, and a
+ *                                level with no oversize part returns at once on a device counter. */
+#define FIESTA_HIP_SPLIT_MAX_DEPTH 63
+#define FIESTA_HIP_SPLIT_OK 0
+#define FIESTA_HIP_SPLIT_INVALID 1
+typedef struct fiesta_hip_split_result { /* every pointer nullable */
+  int32_t *parent;                       /* per part */
+  uint8_t *depth;                        /* per part */
+  int32_t *size;                         /* per part */
+  int64_t *root;                         /* per part */
+  int32_t *box_lo;                       /* per part x 3 */
+  int32_t *box_hi;                       /* per part x 3 */
+  double *centroid;                      /* per part x 3, metres */
+  uint8_t *mask_or;                      /* per part */
+  int32_t *key_min;                      /* per part */
+  int64_t *key_argmin;                   /* per part */
+  int64_t *offsets;                      /* part_capacity + 1 */
+  int64_t *members;                      /* n_members */
+  int32_t *label;                        /* per entry */
+} fiesta_hip_split_result;
+typedef struct fiesta_hip_split_info {
+  int64_t n_parts;
+  int64_t n_members;
+  int64_t n_split_clusters;
+  int64_t n_oversize;
+  int64_t largest;
+  int64_t depth;
+  int64_t status;
+} fiesta_hip_split_info;
+int fiesta_hip_split_clusters(fiesta_hip_map *m, const int32_t *vox, const uint8_t *mask, const int32_t *key, int64_t n, const int64_t *offsets,
+                              const int64_t *members, int64_t n_clusters, int64_t n_members, int32_t max_size, int32_t max_extent,
+                              int32_t max_depth, int64_t part_capacity, const fiesta_hip_split_result *result, fiesta_hip_split_info *info);
+int fiesta_hip_split_clusters_dev(fiesta_hip_map *m, const int32_t *vox_dev, const uint8_t *mask_dev, const int32_t *key_dev, int64_t n,
+                                  const int64_t *offsets_dev, const int64_t *members_dev, int64_t n_clusters, const int64_t *n_clusters_dev,
+                                  int64_t n_members, int32_t max_size, int32_t max_extent, int32_t max_depth, int64_t part_capacity,
+                                  const fiesta_hip_split_result *result, fiesta_hip_split_info *info_dev);
 
 /* ---- view coverage: which target voxels would a sensor at each candidate viewpoint see, per view, per target and per group ----
  * The step after fiesta_hip_cluster_voxels: a frontier planner samples candidate poses around each cluster, counts how many of the
