@@ -100,11 +100,7 @@ __global__ __launch_bounds__(64 * kBoundsWaves) void k_corridor_bounds(const int
           const long long dx = (long long)pw[3 * i + 3] - x, dy = (long long)pw[3 * i + 4] - y, dz = (long long)pw[3 * i + 5] - z;
           dn = (dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy) + (dz < 0 ? -dz : dz);
         }
-        long long incl = dn;
-        for (int o = 1; o < 64; o <<= 1) {
-          const long long u = __shfl_up(incl, o, 64);
-          if (lane >= o) incl += u;
-        }
+        const long long incl = wave_inclusive_sum(dn);
         const long long c = carry + incl - dn;  // c_i
         carry += __shfl(incl, 63, 64);
         const long long b = in ? (long long)bounds_search(pe, nb, c) : 0;

@@ -11,7 +11,7 @@
 //   k_cluster_link<C>  per representative the lexicographically FORWARD half of the stencil (3 / 9 / 13 probes): a neighbour found in
 //                      the table joins the two trees of a lock-free union-find over entry indices (see cluster_unite)
 //   k_cluster_flatten  every entry finds its root; representatives add to their root's counter, one atomic per wave and root
-//   k_cluster_number   ONE work-group striding with a carry (the shape of k_reach_path_scan, 4096 entries per trip): roots with
+//   k_cluster_number   ONE work-group striding with a carry (block_scan_stride of wave_ops.hpp, 4096 entries per trip): roots with
 //                      size >= min_size get ids in increasing root order, their sizes scan into the member offsets; the totals
 //   k_cluster_reduce   labels; per-cluster coordinate sums, box, mask OR, packed (key, index) minimum and the member scatter, all
 //                      aggregated inside the wave first: one atomic per wave, cluster and quantity (see there)
@@ -26,6 +26,7 @@
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
 #include "dense_map.hpp"
+#include "wave_ops.hpp"
 
 namespace fiesta {
 struct ClusterArgs {  // the call's arguments as fiesta_hip_cluster_voxels[_dev] takes them, already checked
@@ -64,6 +65,7 @@ struct ClusterWork {
   int32_t *csize;            // C
   unsigned long long *ctr;   // [0] invalid entries, [1] duplicates
   int64_t S, C;
+  __device__ VoxelAcc acc() const { return VoxelAcc{sum, box, mor, kmin}; }
 };
 struct ClusterIn {
   const int32_t *vox;
@@ -82,6 +84,7 @@ struct ClusterOut {  // device pointers, every one nullable
   int64_t *key_argmin, *offsets, *members;
   fiesta_hip_cluster_info *info;
   int64_t cluster_capacity, member_capacity;
+  __device__ VoxelStatsOut stats() const { return VoxelStatsOut{box_lo, box_hi, centroid, mask_or, key_min, key_argmin}; }
 };
 
 __device__ inline int64_t cluster_count(const ClusterIn &in) {
@@ -109,12 +112,7 @@ __global__ __launch_bounds__(kClusterBlock) void k_cluster_init(ClusterWork w, C
   const int64_t t = blockIdx.x * (int64_t)kClusterBlock + threadIdx.x;
   for (int64_t s = t; s < w.S; s += stride) w.keys[s] = kClusterEmpty, w.tidx[s] = INT32_MAX;
   for (int64_t i = t; i < n; i += stride) w.cnt[i] = 0;
-  for (int64_t k = t; k < w.C; k += stride) {
-    w.sum[3 * k] = w.sum[3 * k + 1] = w.sum[3 * k + 2] = 0;
-    w.box[6 * k] = w.box[6 * k + 1] = w.box[6 * k + 2] = INT32_MAX;
-    w.box[6 * k + 3] = w.box[6 * k + 4] = w.box[6 * k + 5] = INT32_MIN;
-    w.mor[k] = 0, w.kmin[k] = ~0ull, w.csize[k] = 0;
-  }
+  for (int64_t k = t; k < w.C; k += stride) w.acc().reset(k), w.csize[k] = 0;
   if (t < 2) w.ctr[t] = 0;
 }
 
@@ -250,13 +248,7 @@ __global__ __launch_bounds__(kClusterBlock) void k_cluster_flatten(ClusterWork w
         w.lab[i] = rep ? root : (root | kClusterDup);
       }
     }
-    unsigned long long todo = __ballot(rep);
-    while (todo) {
-      const int r = __shfl(root, __ffsll((long long)todo) - 1);
-      const unsigned long long same = __ballot(rep && root == r);
-      if (lane == __ffsll((long long)same) - 1) atomicAdd(&w.cnt[r], __popcll(same));
-      todo &= ~same;
-    }
+    wave_count_keys(w.cnt, rep, root);
   }
 }
 
@@ -267,60 +259,35 @@ __global__ __launch_bounds__(kClusterScanBlock) void k_cluster_number(ClusterWor
   __shared__ unsigned long long s_dropped;
   __shared__ int s_largest;
   const int64_t n = cluster_count(in);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   if (tid == 0) s_dropped = 0, s_largest = 0;
-  unsigned long long carry = 0, dropped = 0;
+  unsigned long long dropped = 0;
   int largest = 0;
-  for (int64_t base = 0; base < n; base += kClusterScanBlock * kClusterScanItems) {  // (the same trip count for every lane: the barriers)
-    const int64_t i0 = base + (int64_t)tid * kClusterScanItems;
-    int sz[kClusterScanItems];
-    unsigned long long v = 0;
-#pragma unroll
-    for (int k = 0; k < kClusterScanItems; ++k) {
-      const int64_t i = i0 + k;
-      sz[k] = -1;  // not a root
-      if (i < n && w.lab[i] == (int)i) {
-        sz[k] = w.cnt[i];
-        if (sz[k] >= min_size) v += (1ull << 32) + (unsigned long long)sz[k], largest = max(largest, sz[k]);
-        else ++dropped;
-      }
-    }
-    unsigned long long inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned long long u = __shfl_up(inc, off);
-      if (lane >= off) inc += u;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned long long before = 0, total = 0;
-    for (int x = 0; x < kClusterScanBlock / 64; ++x) {
-      const unsigned long long s = s_wave[x];
-      if (x < wave) before += s;
-      total += s;
-    }
-    unsigned long long run = carry + before + inc - v;  // exclusive
-#pragma unroll
-    for (int k = 0; k < kClusterScanItems; ++k) {
-      if (sz[k] < 0) continue;
-      const int64_t i = i0 + k;
-      if (sz[k] < min_size) {
-        w.cnt[i] = -1;
-        continue;
-      }
-      const int64_t id = (int64_t)(run >> 32), at = (int64_t)(run & 0xFFFFFFFFull);
-      w.cnt[i] = (int)id;
-      w.parent[i] = (int)at;
-      if (id < w.C) w.csize[id] = sz[k];
-      if (id < o.cluster_capacity) {
-        if (o.size) o.size[id] = sz[k];
-        if (o.root) o.root[id] = i;
-      }
-      if (id <= o.cluster_capacity && o.offsets) o.offsets[id] = at;
-      run += (1ull << 32) + (unsigned long long)sz[k];
-    }
-    carry += total;
-    __syncthreads();  // (the next trip overwrites s_wave)
-  }
+  const unsigned long long carry = block_scan_stride<kClusterScanItems, kClusterScanBlock / 64>(
+      n, s_wave,
+      [&](int64_t i) -> unsigned long long {  // a kept root's word; a dropped root is marked here, its word is 0
+        if (w.lab[i] != (int)i) return 0;
+        const int sz = w.cnt[i];
+        if (sz >= min_size) {
+          largest = max(largest, sz);
+          return (1ull << 32) + (unsigned long long)sz;
+        }
+        ++dropped, w.cnt[i] = -1;
+        return 0;
+      },
+      [&](int64_t i, unsigned long long run, unsigned long long v) {
+        if (!v) return;
+        const int64_t id = (int64_t)(run >> 32), at = (int64_t)(run & 0xFFFFFFFFull);
+        const int sz = (int)(v & 0xFFFFFFFFull);
+        w.cnt[i] = (int)id;
+        w.parent[i] = (int)at;
+        if (id < w.C) w.csize[id] = sz;
+        if (id < o.cluster_capacity) {
+          if (o.size) o.size[id] = sz;
+          if (o.root) o.root[id] = i;
+        }
+        if (id <= o.cluster_capacity && o.offsets) o.offsets[id] = at;
+      });
   if (dropped) atomicAdd(&s_dropped, dropped);
   if (largest) atomicMax(&s_largest, largest);
   __syncthreads();
@@ -368,44 +335,18 @@ __global__ __launch_bounds__(kClusterBlock) void k_cluster_reduce(ClusterWork w,
         }
       }
     }
-    unsigned long long todo = __ballot(rep);
-    while (todo) {
-      const int c = __shfl(id, __ffsll((long long)todo) - 1);
-      const bool mine = rep && id == c;
-      const unsigned long long same = __ballot(mine);
-      todo &= ~same;
+    wave_for_each_key(rep, id, [&](int c, bool mine, unsigned long long same) {
       const int cnt = __popcll(same), first = __ffsll((long long)same) - 1;
       // members: the first lane takes cnt places at the cluster's cursor, lane r-th of the cluster writes the r-th of them
       int at = 0;
       if (lane == first) at = atomicAdd(&w.parent[root], cnt);
       at = __shfl(at, first) + __popcll(same & ((1ull << lane) - 1));
       if (mine && o.members && at < o.member_capacity) o.members[at] = i;
-      if (c >= w.C) continue;  // (uniform)
-      int sx = mine ? x : 0, sy = mine ? y : 0, sz = mine ? z : 0;
-      int lx = mine ? x : INT32_MAX, ly = mine ? y : INT32_MAX, lz = mine ? z : INT32_MAX;
-      int hx = mine ? x : INT32_MIN, hy = mine ? y : INT32_MIN, hz = mine ? z : INT32_MIN;
-      uint32_t mm = mine ? mk : 0;
-      unsigned long long kk = mine ? kp : ~0ull;
-      if (cnt > 1) {
-        for (int off = 32; off >= 1; off >>= 1) {
-          sx += __shfl_xor(sx, off), sy += __shfl_xor(sy, off), sz += __shfl_xor(sz, off);
-          lx = min(lx, __shfl_xor(lx, off)), ly = min(ly, __shfl_xor(ly, off)), lz = min(lz, __shfl_xor(lz, off));
-          hx = max(hx, __shfl_xor(hx, off)), hy = max(hy, __shfl_xor(hy, off)), hz = max(hz, __shfl_xor(hz, off));
-          mm |= __shfl_xor(mm, off);
-          const unsigned long long ok = __shfl_xor(kk, off);
-          kk = ok < kk ? ok : kk;
-        }
-      }
-      if (lane == first) {
-        atomicAdd(&w.sum[3 * c], (unsigned long long)(long long)sx);
-        atomicAdd(&w.sum[3 * c + 1], (unsigned long long)(long long)sy);
-        atomicAdd(&w.sum[3 * c + 2], (unsigned long long)(long long)sz);
-        atomicMin(&w.box[6 * c], lx), atomicMin(&w.box[6 * c + 1], ly), atomicMin(&w.box[6 * c + 2], lz);
-        atomicMax(&w.box[6 * c + 3], hx), atomicMax(&w.box[6 * c + 4], hy), atomicMax(&w.box[6 * c + 5], hz);
-        if (mm) atomicOr(&w.mor[c], mm);
-        if (kk != ~0ull) atomicMin(&w.kmin[c], kk);
-      }
-    }
+      if (c >= w.C) return;  // (uniform)
+      VoxelStats st = VoxelStats::at(mine, x, y, z, mk, kp);
+      if (cnt > 1) st.reduce();
+      if (lane == first) st.commit(w.acc(), c);
+    });
   }
 }
 
@@ -415,17 +356,7 @@ __global__ __launch_bounds__(kClusterBlock) void k_cluster_finish(ClusterWork w,
   for (int64_t k = blockIdx.x * (int64_t)kClusterBlock + threadIdx.x; k < w.C; k += stride) {
     const int size = w.csize[k];
     if (size <= 0) continue;  // beyond the number of clusters
-    if (o.box_lo) o.box_lo[3 * k] = w.box[6 * k], o.box_lo[3 * k + 1] = w.box[6 * k + 1], o.box_lo[3 * k + 2] = w.box[6 * k + 2];
-    if (o.box_hi) o.box_hi[3 * k] = w.box[6 * k + 3], o.box_hi[3 * k + 1] = w.box[6 * k + 4], o.box_hi[3 * k + 2] = w.box[6 * k + 5];
-    if (o.centroid) {
-      const double org[3] = {ox, oy, oz};
-#pragma unroll
-      for (int c = 0; c < 3; ++c) o.centroid[3 * k + c] = ((double)(long long)w.sum[3 * k + c] / (double)size + 0.5) * res + org[c];
-    }
-    if (o.mask_or) o.mask_or[k] = (uint8_t)w.mor[k];
-    const unsigned long long kk = w.kmin[k];
-    if (o.key_min) o.key_min[k] = kk == ~0ull ? INT32_MAX : (int32_t)(kk >> 32);
-    if (o.key_argmin) o.key_argmin[k] = kk == ~0ull ? -1 : (int64_t)(kk & 0xFFFFFFFFull);
+    voxel_stats_write(w.acc(), o.stats(), k, size, res, ox, oy, oz);
   }
 }
 

@@ -12,13 +12,14 @@
 //                     built by ballot from the page's field words (two rows per wave instruction) into LDS; x / y neighbours
 //                     inside the tile are rows of the same page, neighbours across a tile face are read through PAGES::addr,
 //                     the map-wide lookup of the queries (no page there: all unknown)
-// Both end in frontier_emit: the lanes' candidate counts are prefix-summed across the wave (__shfl_up), ONE integer atomicAdd per
+// Both end in frontier_emit: the lanes' candidate counts are prefix-summed across the wave (wave_ops.hpp), ONE integer atomicAdd per
 // wave and iteration reserves the wave's range in the output, every lane writes its entries at base + prefix (guarded by the
 // capacity).  That atomic is the only one; the SET of (voxel, mask) pairs depends on nothing but the map, the order on scheduling.
 #pragma once
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
 #include "hash_map.hpp"
+#include "wave_ops.hpp"
 
 namespace fiesta {
 struct FrontierArgs {  // the call's arguments as fiesta_hip_get_frontier_voxels[_dev] takes them, already checked
@@ -66,11 +67,7 @@ __device__ inline void frontier_emit(const FrontierOut &out, uint32_t cand, int 
                                      uint32_t vp, uint32_t wm, uint32_t wp) {
   const int lane = threadIdx.x & 63;
   const int cnt = __popc(cand);
-  int incl = cnt;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d);
-    if (lane >= d) incl += t;
-  }
+  const int incl = wave_inclusive_sum(cnt);
   const int total = __shfl(incl, 63);
   if (!total) return;  // (uniform across the wave)
   unsigned long long base = 0;

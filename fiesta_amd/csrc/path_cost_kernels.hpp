@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void k_cost_eval(Eval ev, const double *w, con
       for (int c = 0; c < 7; ++c) cs[c] = __shfl(x[c], 63, 64);
       jw = (int64_t)__shfl((long long)j, 63, 64) + (sg + 64 >= __shfl(end, 63, 64) ? 1 : 0);
     }
-    for (int o = 32; o > 0; o >>= 1) nb += __shfl_xor(nb, o, 64);
+    nb = wave_sum(nb);
     if (lane == 0) {  // the piece's last segment: the tail record, or still the head
       double *dst = ck == jfirst ? out->h : out->t;
 #pragma unroll
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void k_cost_finish(const double *w, const int6
   long long nb = 0;
   if (n > 0)
     for (int64_t k = poff[p] + lane; k < poff[p + 1]; k += 64) nb += rec[k].nb;
-  for (int o = 32; o > 0; o >>= 1) nb += __shfl_xor(nb, o, 64);
+  nb = wave_sum(nb);
   double cost = 0, length = 0;     // (uniform: every lane adds the same terms in segment order)
   double ce[3] = {0, 0, 0};        // the contribution of the previous chunk's last segment to this chunk's first waypoint
   for (int64_t c = 0; c < nw; c += 64) {

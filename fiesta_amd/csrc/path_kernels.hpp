@@ -31,6 +31,7 @@
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
 #include "dense_map.hpp"
+#include "wave_ops.hpp"
 
 namespace fiesta {
 // the arguments as fiesta_hip_path_clearance[_dev] and fiesta_hip_path_cost[_dev] take them (R: the call's result struct),
@@ -136,26 +137,6 @@ __host__ __device__ inline void path_write(Eval &ev, const fiesta_hip_path_resul
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
-// inclusive scan of one value per thread over a work-group of up to 16 waves; *total = the whole group's
-template <class Op>
-__device__ inline long long block_inclusive(long long v, long long ident, Op op, long long *lds, long long *total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long u = __shfl_up(v, o, 64);
-    if (lane >= o) v = op(v, u);
-  }
-  if (lane == 63) lds[wv] = v;
-  __syncthreads();
-  long long pre = ident, tot = ident;
-  for (int k = 0; k < nwv; ++k) {
-    if (k < wv) pre = op(pre, lds[k]);
-    tot = op(tot, lds[k]);
-  }
-  __syncthreads();
-  *total = tot;
-  return op(pre, v);
-}
-
 // Device variant: path p is flagged (nsamp = -1) when its range is reversed, leaves [0, n_wp], or starts below an earlier offset
 // that lies in [0, n_wp] (it could overlap an earlier path).  Valid paths therefore own disjoint waypoint ranges: k_path_plan's
 // writes never race.  Entries outside [0, n_wp] do not enter the running maximum: a garbage offset costs its own two paths only.
@@ -167,8 +148,7 @@ __global__ __launch_bounds__(1024) void k_path_check(const int64_t *off, int64_t
     const int64_t p = c + threadIdx.x;
     const long long o0 = p < n_paths ? (long long)off[p] : LLONG_MIN;
     long long tot;
-    long long m = block_inclusive(o0 >= 0 && o0 <= n_wp ? o0 : LLONG_MIN, LLONG_MIN, [](long long a, long long b) { return a > b ? a : b; },
-                                  lds, &tot);
+    long long m = block_inclusive<16>(o0 >= 0 && o0 <= n_wp ? o0 : LLONG_MIN, (long long)LLONG_MIN, WaveMax{}, lds, &tot);
     m = m > carry ? m : carry;  // max of the in-range entries of off[0 .. p]
     if (p < n_paths) {
       const long long o1 = off[p + 1];
@@ -201,11 +181,7 @@ __global__ __launch_bounds__(256) void k_path_plan(const double *w, const int64_
       lane_bad = !path_finite(a);
       if (i + 1 < o1 && !path_segment_samples(a, a + 3, step, &S)) lane_bad = 1;
     }
-    long long incl = S;
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
-    }
+    const long long incl = wave_inclusive_sum(S);
     if (i < o1) base[i] = carry + incl - S;
     carry += __shfl(incl, 63, 64);
     bad |= __any(lane_bad);
@@ -216,23 +192,16 @@ __global__ __launch_bounds__(256) void k_path_plan(const double *w, const int64_
 // one work-group: poff[p] = first piece of path p, poff[n_paths] = pieces in total (read by k_path_eval, never by the host)
 __global__ __launch_bounds__(1024) void k_path_pieces(const int64_t *nsamp, int64_t n_paths, long long max_pieces, int64_t *poff) {
   __shared__ long long lds[16];
-  long long carry = 0;
-  for (int64_t c = 0; c < n_paths; c += blockDim.x) {
-    const int64_t p = c + threadIdx.x;
-    long long k = 0;
-    if (p < n_paths) {
-      const long long n = nsamp[p];
-      if (n > 0) {
+  const long long total = block_scan_stride<1, 16>(
+      n_paths, lds,
+      [&](int64_t p) {
+        const long long n = nsamp[p];
+        if (n <= 0) return 0ll;
         const long long ps = path_piece_size(n, max_pieces);
-        k = (n + ps - 1) / ps;
-      }
-    }
-    long long tot;
-    const long long incl = block_inclusive(k, 0ll, [](long long a, long long b) { return a + b; }, lds, &tot);
-    if (p < n_paths) poff[p] = carry + incl - k;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) poff[n_paths] = carry;
+        return (n + ps - 1) / ps;
+      },
+      [&](int64_t p, long long first, long long) { poff[p] = first; });
+  if (threadIdx.x == 0) poff[n_paths] = total;
 }
 
 template <class Eval>

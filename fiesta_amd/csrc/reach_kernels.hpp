@@ -99,8 +99,7 @@ __global__ __launch_bounds__(256) void k_reach_mask(SRC src, ReachBox b, double 
       const int c = __shfl(cb, from), v = __shfl(nv, from);
       if (k < v) cost[c + k] = ((tw >> k) & 1u) ? INT32_MAX : -1;
     }
-    int cnt = __popc(t);
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+    const int cnt = wave_sum(__popc(t));
     if (lane == 0 && cnt) atomicAdd(&ctr[R_NTRAV], (unsigned long long)cnt);
   }
 }
@@ -227,7 +226,7 @@ __global__ __launch_bounds__(256) void k_reach_stats(const int32_t *cost, int64_
     const int c = cost[i];
     if (c >= 0 && c != INT32_MAX) ++cnt, mx = max(mx, c);
   }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off), mx = max(mx, __shfl_down(mx, off));
+  cnt = wave_sum(cnt), mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0 && cnt) {
     atomicAdd(&ctr[R_REACHED], (unsigned long long)cnt);
     atomicMax(&ctr[R_MAXCOST], (unsigned long long)mx);

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void k_rmx_count(const int32_t *planes, int64_
     const int c = cost[i];
     if (c >= 0 && c != INT32_MAX) ++cnt;
   }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+  cnt = wave_sum(cnt);
   if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&reached[blockIdx.y], (unsigned long long)cnt);
 }
 

@@ -26,6 +26,7 @@
 #include "common.hpp"
 #include "dense_map.hpp"
 #include "ray_walk.hpp"
+#include "wave_ops.hpp"
 
 namespace fiesta {
 struct ReachPathArgs {  // the call's arguments as fiesta_hip_reach_paths[_dev] takes them, already checked
@@ -240,28 +241,10 @@ __global__ __launch_bounds__(kReachPathBlock) void k_reach_path_count(ReachPathF
 // offsets[1 .. n]: counts -> inclusive running totals; offsets[0] = 0.  One work-group of 256, 256 entries per trip, the carry in a register.
 __global__ __launch_bounds__(256) void k_reach_path_scan(int64_t *offsets, int64_t n) {
   __shared__ long long s_wave[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) offsets[0] = 0;
-  long long carry = 0;
-  for (int64_t base = 0; base < n; base += 256) {  // (the same trip count for every lane: the barriers below need all of them)
-    const int64_t i = base + tid;
-    long long v = i < n ? (long long)offsets[1 + i] : 0;
-    for (int off = 1; off < 64; off <<= 1) {
-      const long long u = __shfl_up(v, off);
-      if (lane >= off) v += u;
-    }
-    if (lane == 63) s_wave[wave] = v;
-    __syncthreads();
-    long long before = 0, total = 0;
-    for (int w = 0; w < 4; ++w) {
-      const long long s = s_wave[w];
-      if (w < wave) before += s;
-      total += s;
-    }
-    if (i < n) offsets[1 + i] = (int64_t)(carry + before + v);
-    carry += total;
-    __syncthreads();  // (the next trip overwrites s_wave)
-  }
+  if (threadIdx.x == 0) offsets[0] = 0;
+  (void)block_scan_stride<1, 4>(
+      n, s_wave, [&](int64_t i) { return (long long)offsets[1 + i]; },
+      [&](int64_t i, long long before, long long v) { offsets[1 + i] = (int64_t)(before + v); });
 }
 
 template <int CONN, bool SHORTCUT>

@@ -48,22 +48,12 @@ struct RefineK {  // fiesta_hip_refine_params as the kernel uses it
   int iterations;
 };
 
-struct RefineMax {
-  __device__ double operator()(double a, double b) const { return a > b ? a : b; }
-};
-struct RefineMin {
-  __device__ double operator()(double a, double b) const { return a < b ? a : b; }
-};
-struct RefineSum {
-  __device__ double operator()(double a, double b) const { return a + b; }
-};
-
 // v reduced over the team; every lane returns the same bits (op is commutative: both partners of a butterfly step compute the same
 // value).  Holds exactly one barrier, which also orders the team's LDS writes before it against the reads after it.  red: TEAM / 64
 // words that no reduction of the two before this one used.
 template <int TEAM, class Op>
 __device__ inline double refine_reduce(double v, double *red, Op op) {
-  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+  v = wave_reduce(v, op);
   if (TEAM > 64) {
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -127,7 +117,7 @@ __global__ __launch_bounds__(TEAM) void k_refine(Eval ev, const double *w, const
             if (!(lo <= hi)) lane_bad = 1.0;  // lo > hi, or a NaN
           }
       }
-      bad = __builtin_amdgcn_readfirstlane(refine_reduce<TEAM>(lane_bad, red[rb++ & 1], RefineMax()) > 0.0 ? 1 : 0) != 0;
+      bad = __builtin_amdgcn_readfirstlane(refine_reduce<TEAM>(lane_bad, red[rb++ & 1], WaveMax{}) > 0.0 ? 1 : 0) != 0;
     }
     if (bad) {  // its rows keep the input (the row copy, or the caller's own array)
       if (t == 0) {
@@ -186,14 +176,14 @@ __global__ __launch_bounds__(TEAM) void k_refine(Eval ev, const double *w, const
         }
       }
       if (fin) break;
-      last = refine_reduce<TEAM>(mv, red[rb++ & 1], RefineMax());
+      last = refine_reduce<TEAM>(mv, red[rb++ & 1], WaveMax{});
       ++it, P ^= 1;
       stop = __builtin_amdgcn_readfirstlane(last <= k.tol ? 1 : 0) != 0;  // (every lane holds the team's maximum: a scalar branch)
     }
-    j1 = refine_reduce<TEAM>(j1, red[rb++ & 1], RefineSum());
-    j0 = it > 0 ? refine_reduce<TEAM>(j0, red[rb++ & 1], RefineSum()) : j1;  // (nothing ran: the input is the result)
-    nb = refine_reduce<TEAM>(nb, red[rb++ & 1], RefineSum());
-    md = refine_reduce<TEAM>(md, red[rb++ & 1], RefineMin());
+    j1 = refine_reduce<TEAM>(j1, red[rb++ & 1], WaveSum{});
+    j0 = it > 0 ? refine_reduce<TEAM>(j0, red[rb++ & 1], WaveSum{}) : j1;  // (nothing ran: the input is the result)
+    nb = refine_reduce<TEAM>(nb, red[rb++ & 1], WaveSum{});
+    md = refine_reduce<TEAM>(md, red[rb++ & 1], WaveMin{});
     if (t == 0) {
       if (r.cost) r.cost[2 * p] = j0, r.cost[2 * p + 1] = j1;
       if (r.last_move) r.last_move[p] = last;

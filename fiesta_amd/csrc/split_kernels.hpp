@@ -14,7 +14,7 @@
 //   k_split_first     the depth-0 parts: a lane per member copies its index and takes its part
 //   per level L < max_depth (the host enqueues all of them; a level without an oversize part returns at once on a device counter):
 //   k_split_box       a lane per member of a depth-L part: box min / max into per-part words, aggregated inside the wave first
-//                     (the members of a part are contiguous: a wave touches few parts), as k_cluster_reduce does, and over the 16
+//                     (the members of a part are contiguous: a wave touches few parts; VoxelBox of wave_ops.hpp), and over the 16
 //                     chunks a wave takes in a row; a word that already covers the wave's box gets no atomic
 //   k_split_decide    a lane per part: oversize? then the axis (largest extent, lowest axis among equals) and mid; counts the cuts
 //   k_split_partial   a lane per member: one flag byte -- bit 0: on the high side of its part's cut, bit 1: first member of a part
@@ -25,7 +25,7 @@
 //                     side); the new position is the part's start plus the rank on its side; written into the OTHER member buffer
 //   after the last level:
 //   k_split_acc_init / k_split_stats / k_split_finish / k_split_info   per-part sums, box, mask OR, packed (key, index) minimum,
-//                     root and the labels with k_cluster_reduce's wave aggregation, then k_cluster_finish's arithmetic
+//                     root and the labels with the wave aggregation of wave_ops.hpp (VoxelStats), then voxel_stats_write
 // The member scan is reduce-then-scan: no decoupled look-back, no single striding work-group.  Every loop is bounded by a count the
 // host passed.  Every quantity is a commutative exact integer reduction and the partition is stable: all outputs but the order
 // inside a member segment are the same bits for any launch shape, and the bits of fiesta_amd.split_model.  No scratch memory.
@@ -83,6 +83,7 @@ struct SplitWork {
   unsigned long long *kmin;            // M
   unsigned long long *ctr;             // kSplitWords
   int64_t M, T;
+  __device__ VoxelAcc acc() const { return VoxelAcc{sum, box, mor, kmin}; }
 };
 struct SplitIn {
   const int32_t *vox;
@@ -105,35 +106,14 @@ struct SplitOut {  // device pointers, every one nullable
   int32_t *label;
   fiesta_hip_split_info *info;
   int64_t part_capacity;
+  __device__ VoxelStatsOut stats() const { return VoxelStatsOut{box_lo, box_hi, centroid, mask_or, key_min, key_argmin}; }
 };
 
 __device__ inline bool split_bad(const SplitWork &w) { return w.ctr[kSplitBad] != 0; }
 __device__ inline bool split_oversize(int size, int ex, int ey, int ez, int max_size, int max_extent) {
   return (max_size > 0 && size > max_size) || (max_extent > 0 && max(ex, max(ey, ez)) > max_extent);
 }
-__device__ inline void split_box_reset(int32_t *box, int64_t p) {
-  box[6 * p] = box[6 * p + 1] = box[6 * p + 2] = INT32_MAX;
-  box[6 * p + 3] = box[6 * p + 4] = box[6 * p + 5] = INT32_MIN;
-}
-// the sum of v over the work-group's lanes, in every lane (s: kSplitBlock / 64 words); the exclusive prefix of the lane in *excl
-__device__ inline unsigned long long split_block_scan(unsigned long long v, unsigned long long *s, unsigned long long *excl, int nwaves) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned long long inc = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned long long u = __shfl_up(inc, off);
-    if (lane >= off) inc += u;
-  }
-  if (lane == 63) s[wave] = inc;
-  __syncthreads();
-  unsigned long long before = 0, total = 0;
-  for (int x = 0; x < nwaves; ++x) {
-    const unsigned long long t = s[x];
-    if (x < wave) before += t;
-    total += t;
-  }
-  *excl = before + inc - v;
-  return total;
-}
+__device__ inline void split_box_reset(int32_t *box, int64_t p) { VoxelBox::reset(box + 6 * p); }
 
 __global__ __launch_bounds__(kSplitBlock) void k_split_init(SplitWork w, SplitIn in, SplitOut o) {
   const int64_t stride = (int64_t)gridDim.x * kSplitBlock, t = blockIdx.x * (int64_t)kSplitBlock + threadIdx.x;
@@ -206,8 +186,8 @@ __global__ __launch_bounds__(kSplitBlock) void k_split_partial(SplitWork w, Spli
     }
     v += ((unsigned long long)(f >> 1) << 32) | (unsigned long long)(f & 1);
   }
-  unsigned long long excl;
-  const unsigned long long total = split_block_scan(v, s_wave, &excl, kSplitBlock / 64);
+  unsigned long long total;
+  (void)block_inclusive<kSplitBlock / 64>(v, 0ull, WaveSum{}, s_wave, &total);
   if (threadIdx.x == 0) w.partial[blockIdx.x] = total;
 }
 
@@ -223,8 +203,8 @@ __global__ __launch_bounds__(kSplitScanBlock) void k_split_scan(SplitWork w, int
   unsigned long long v = 0;
   for (int k = 0; k < items; ++k)
     if (i0 + k < n_tiles) v += w.partial[i0 + k];
-  unsigned long long run;
-  const unsigned long long total = split_block_scan(v, s_wave, &run, kSplitScanBlock / 64);
+  unsigned long long total;
+  unsigned long long run = block_inclusive<kSplitScanBlock / 64>(v, 0ull, WaveSum{}, s_wave, &total) - v;
   for (int k = 0; k < items; ++k)
     if (i0 + k < n_tiles) {
       const unsigned long long x = w.partial[i0 + k];
@@ -257,9 +237,8 @@ __global__ __launch_bounds__(kSplitBlock) void k_split_rescan(SplitWork w, int l
     const unsigned f = (unsigned)(f8 >> (8 * k)) & 0xFFu;
     v += ((unsigned long long)(f >> 1) << 32) | (unsigned long long)(f & 1u);
   }
-  unsigned long long run;
-  const unsigned long long total = split_block_scan(v, s_wave, &run, kSplitBlock / 64);
-  run += w.partial[blockIdx.x];
+  unsigned long long total;
+  unsigned long long run = w.partial[blockIdx.x] + block_inclusive<kSplitBlock / 64>(v, 0ull, WaveSum{}, s_wave, &total) - v;
 #pragma unroll
   for (int k = 0; k < kSplitItems; ++k) {
     const unsigned f = (unsigned)(f8 >> (8 * k)) & 0xFFu;
@@ -289,16 +268,16 @@ __global__ __launch_bounds__(kSplitBlock) void k_split_first(SplitWork w, SplitI
 // part reduce among themselves with a butterfly in which the others carry the identity, so every lane holds the part's box of the
 // chunk.  The members of a part are contiguous, so the parts of a run come in order: the wave keeps ONE running box, in every lane
 // alike, and flushes it when the part changes and at the end of the run -- one flush per wave, run and part.
-__device__ inline void split_box_flush(int32_t *box, int c, int lx, int ly, int lz, int hx, int hy, int hz) {
+__device__ inline void split_box_flush(int32_t *box, int c, const VoxelBox &v) {
   // A word only ever moves outwards during this kernel, so a value read now (a relaxed atomic load: the L2's copy, or an older
   // one) that already covers the wave's needs no atomic: after the first waves of a large part almost none does.
   int32_t *b = box + 6 * (int64_t)c;
-  if (lx < cluster_load(b)) atomicMin(b, lx);
-  if (ly < cluster_load(b + 1)) atomicMin(b + 1, ly);
-  if (lz < cluster_load(b + 2)) atomicMin(b + 2, lz);
-  if (hx > cluster_load(b + 3)) atomicMax(b + 3, hx);
-  if (hy > cluster_load(b + 4)) atomicMax(b + 4, hy);
-  if (hz > cluster_load(b + 5)) atomicMax(b + 5, hz);
+  if (v.lx < cluster_load(b)) atomicMin(b, v.lx);
+  if (v.ly < cluster_load(b + 1)) atomicMin(b + 1, v.ly);
+  if (v.lz < cluster_load(b + 2)) atomicMin(b + 2, v.lz);
+  if (v.hx > cluster_load(b + 3)) atomicMax(b + 3, v.hx);
+  if (v.hy > cluster_load(b + 4)) atomicMax(b + 4, v.hy);
+  if (v.hz > cluster_load(b + 5)) atomicMax(b + 5, v.hz);
 }
 __global__ __launch_bounds__(kSplitBlock) void k_split_box(SplitWork w, SplitIn in, int level) {
   if (split_bad(w) || (level > 0 && w.ctr[kSplitCuts + level - 1] == 0)) return;
@@ -306,7 +285,8 @@ __global__ __launch_bounds__(kSplitBlock) void k_split_box(SplitWork w, SplitIn 
   const int64_t span = 64 * (int64_t)kSplitBoxRun, stride = (int64_t)gridDim.x * (kSplitBlock / 64) * span;
   const int cur = (int)w.ctr[kSplitCur + level], lane = threadIdx.x & 63;
   for (int64_t run = m0 + (blockIdx.x * (int64_t)(kSplitBlock / 64) + (threadIdx.x >> 6)) * span; run < m1; run += stride) {  // (whole waves: the ballot)
-    int rc = -1, rlx = INT32_MAX, rly = INT32_MAX, rlz = INT32_MAX, rhx = INT32_MIN, rhy = INT32_MIN, rhz = INT32_MIN;  // the running box: uniform
+    int rc = -1;  // the running box and its part: uniform
+    VoxelBox rb = VoxelBox::identity();
     for (int k = 0; k < kSplitBoxRun; ++k) {
       const int64_t j = run + 64 * (int64_t)k + lane;
       int p = -1, x = 0, y = 0, z = 0;
@@ -319,26 +299,18 @@ __global__ __launch_bounds__(kSplitBlock) void k_split_box(SplitWork w, SplitIn 
           x = in.vox[3 * i], y = in.vox[3 * i + 1], z = in.vox[3 * i + 2];
         }
       }
-      unsigned long long todo = __ballot(on);
-      while (todo) {
-        const int c = __shfl(p, __ffsll((long long)todo) - 1);
-        const bool mine = on && p == c;
-        todo &= ~__ballot(mine);
-        int lx = mine ? x : INT32_MAX, ly = mine ? y : INT32_MAX, lz = mine ? z : INT32_MAX;
-        int hx = mine ? x : INT32_MIN, hy = mine ? y : INT32_MIN, hz = mine ? z : INT32_MIN;
-        for (int off = 32; off >= 1; off >>= 1) {
-          lx = min(lx, __shfl_xor(lx, off)), ly = min(ly, __shfl_xor(ly, off)), lz = min(lz, __shfl_xor(lz, off));
-          hx = max(hx, __shfl_xor(hx, off)), hy = max(hy, __shfl_xor(hy, off)), hz = max(hz, __shfl_xor(hz, off));
-        }
+      wave_for_each_key(on, p, [&](int c, bool mine, unsigned long long) {
+        VoxelBox b = VoxelBox::at(mine, x, y, z);
+        b.reduce();
         if (c != rc) {  // (uniform)
-          if (rc >= 0 && lane == 0) split_box_flush(w.box, rc, rlx, rly, rlz, rhx, rhy, rhz);
-          rc = c, rlx = lx, rly = ly, rlz = lz, rhx = hx, rhy = hy, rhz = hz;
+          if (rc >= 0 && lane == 0) split_box_flush(w.box, rc, rb);
+          rc = c, rb = b;
         } else {
-          rlx = min(rlx, lx), rly = min(rly, ly), rlz = min(rlz, lz), rhx = max(rhx, hx), rhy = max(rhy, hy), rhz = max(rhz, hz);
+          rb.combine(b);
         }
-      }
+      });
     }
-    if (rc >= 0 && lane == 0) split_box_flush(w.box, rc, rlx, rly, rlz, rhx, rhy, rhz);
+    if (rc >= 0 && lane == 0) split_box_flush(w.box, rc, rb);
   }
 }
 
@@ -409,13 +381,11 @@ __global__ __launch_bounds__(kSplitBlock) void k_split_acc_init(SplitWork w, int
   if (split_bad(w)) return;
   const int64_t stride = (int64_t)gridDim.x * kSplitBlock, P = (int64_t)w.ctr[kSplitParts + levels];
   for (int64_t p = blockIdx.x * (int64_t)kSplitBlock + threadIdx.x; p < P; p += stride) {
-    w.sum[3 * p] = w.sum[3 * p + 1] = w.sum[3 * p + 2] = 0;
-    split_box_reset(w.box, p);
-    w.mor[p] = 0, w.kmin[p] = ~0ull, w.proot[p] = INT32_MAX;
+    w.acc().reset(p), w.proot[p] = INT32_MAX;
   }
 }
 
-// labels, the output members and the per-part reductions: k_cluster_reduce's wave aggregation (a wave's coordinate sum fits 32 bits)
+// labels, the output members and the per-part reductions: the wave aggregation of wave_ops.hpp (VoxelStats)
 __global__ __launch_bounds__(kSplitBlock) void k_split_stats(SplitWork w, SplitIn in, SplitOut o, int levels) {
   if (split_bad(w)) return;
   const int64_t stride = (int64_t)gridDim.x * kSplitBlock, m0 = (int64_t)w.ctr[kSplitM0], m1 = (int64_t)w.ctr[kSplitM1];
@@ -437,40 +407,12 @@ __global__ __launch_bounds__(kSplitBlock) void k_split_stats(SplitWork w, SplitI
         if (kv >= 0) kp = ((unsigned long long)(uint32_t)kv << 32) | (unsigned long long)(uint32_t)i;
       }
     }
-    unsigned long long todo = __ballot(on);
-    while (todo) {
-      const int c = __shfl(p, __ffsll((long long)todo) - 1);
-      const bool mine = on && p == c;
-      const unsigned long long same = __ballot(mine);
-      todo &= ~same;
-      int sx = mine ? x : 0, sy = mine ? y : 0, sz = mine ? z : 0, ri = mine ? i : INT32_MAX;
-      int lx = mine ? x : INT32_MAX, ly = mine ? y : INT32_MAX, lz = mine ? z : INT32_MAX;
-      int hx = mine ? x : INT32_MIN, hy = mine ? y : INT32_MIN, hz = mine ? z : INT32_MIN;
-      uint32_t mm = mine ? mk : 0;
-      unsigned long long kk = mine ? kp : ~0ull;
-      if (__popcll(same) > 1) {
-        for (int off = 32; off >= 1; off >>= 1) {
-          sx += __shfl_xor(sx, off), sy += __shfl_xor(sy, off), sz += __shfl_xor(sz, off);
-          lx = min(lx, __shfl_xor(lx, off)), ly = min(ly, __shfl_xor(ly, off)), lz = min(lz, __shfl_xor(lz, off));
-          hx = max(hx, __shfl_xor(hx, off)), hy = max(hy, __shfl_xor(hy, off)), hz = max(hz, __shfl_xor(hz, off));
-          mm |= __shfl_xor(mm, off);
-          ri = min(ri, __shfl_xor(ri, off));
-          const unsigned long long ok = __shfl_xor(kk, off);
-          kk = ok < kk ? ok : kk;
-        }
-      }
-      if (lane == __ffsll((long long)same) - 1) {
-        const int64_t q = c;
-        atomicAdd(&w.sum[3 * q], (unsigned long long)(long long)sx);
-        atomicAdd(&w.sum[3 * q + 1], (unsigned long long)(long long)sy);
-        atomicAdd(&w.sum[3 * q + 2], (unsigned long long)(long long)sz);
-        atomicMin(&w.box[6 * q], lx), atomicMin(&w.box[6 * q + 1], ly), atomicMin(&w.box[6 * q + 2], lz);
-        atomicMax(&w.box[6 * q + 3], hx), atomicMax(&w.box[6 * q + 4], hy), atomicMax(&w.box[6 * q + 5], hz);
-        atomicMin(&w.proot[q], ri);
-        if (mm) atomicOr(&w.mor[q], mm);
-        if (kk != ~0ull) atomicMin(&w.kmin[q], kk);
-      }
-    }
+    wave_for_each_key(on, p, [&](int c, bool mine, unsigned long long same) {
+      VoxelStats st = VoxelStats::at(mine, x, y, z, mk, kp);
+      int ri = mine ? i : INT32_MAX;  // the part's root: its lowest entry index
+      if (__popcll(same) > 1) st.reduce(), ri = wave_min(ri);
+      if (wave_first_of(same)) st.commit(w.acc(), c), atomicMin(&w.proot[c], ri);
+    });
   }
 }
 
@@ -496,23 +438,10 @@ __global__ __launch_bounds__(kSplitBlock) void k_split_finish(SplitWork w, Split
         if (o.depth) o.depth[p] = (uint8_t)deep;
         if (o.size) o.size[p] = size;
         if (o.root) o.root[p] = w.proot[p];
-        if (o.box_lo) o.box_lo[3 * p] = b[0], o.box_lo[3 * p + 1] = b[1], o.box_lo[3 * p + 2] = b[2];
-        if (o.box_hi) o.box_hi[3 * p] = b[3], o.box_hi[3 * p + 1] = b[4], o.box_hi[3 * p + 2] = b[5];
-        if (o.centroid) {
-          const double org[3] = {ox, oy, oz};
-#pragma unroll
-          for (int c = 0; c < 3; ++c) o.centroid[3 * p + c] = ((double)(long long)w.sum[3 * p + c] / (double)size + 0.5) * res + org[c];
-        }
-        if (o.mask_or) o.mask_or[p] = (uint8_t)w.mor[p];
-        const unsigned long long kk = w.kmin[p];
-        if (o.key_min) o.key_min[p] = kk == ~0ull ? INT32_MAX : (int32_t)(kk >> 32);
-        if (o.key_argmin) o.key_argmin[p] = kk == ~0ull ? -1 : (int64_t)(kk & 0xFFFFFFFFull);
+        voxel_stats_write(w.acc(), o.stats(), p, size, res, ox, oy, oz);
       }
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-      size = max(size, __shfl_xor(size, off)), deep = max(deep, __shfl_xor(deep, off));
-      over += __shfl_xor(over, off), cutc += __shfl_xor(cutc, off);
-    }
+    size = wave_max(size), deep = wave_max(deep), over = wave_sum(over), cutc = wave_sum(cutc);
     if ((threadIdx.x & 63) == 0) {
       if (size) atomicMax(&w.ctr[kSplitLargest], (unsigned long long)size);
       if (deep) atomicMax(&w.ctr[kSplitDeepest], (unsigned long long)deep);

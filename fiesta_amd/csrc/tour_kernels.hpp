@@ -32,6 +32,7 @@
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
 #include "dense_map.hpp"
+#include "wave_ops.hpp"
 
 namespace fiesta {
 struct TourArgs {  // the call's arguments as fiesta_hip_site_tour[_dev] takes them, already checked
@@ -65,10 +66,7 @@ __device__ inline unsigned long long tour_mix(unsigned long long x) {
 // the work-group's minimum / sum, wave first, then through red[2][4] (alternating halves: one barrier per call, which also
 // orders the LDS traffic around it)
 __device__ inline unsigned long long tour_block_min(unsigned long long v, unsigned long long *red, int &par) {
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(v, off);
-    v = o < v ? o : v;
-  }
+  v = wave_min(v);
   if ((threadIdx.x & 63) == 0) red[par * 4 + (threadIdx.x >> 6)] = v;
   __syncthreads();
   unsigned long long r = red[par * 4];
@@ -77,7 +75,7 @@ __device__ inline unsigned long long tour_block_min(unsigned long long v, unsign
   return r;
 }
 __device__ inline long long tour_block_sum(long long v, unsigned long long *red, int &par) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) red[par * 4 + (threadIdx.x >> 6)] = (unsigned long long)v;
   __syncthreads();
   long long r = 0;

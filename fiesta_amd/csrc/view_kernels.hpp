@@ -20,7 +20,7 @@
 //                    waits for the next batch, and everything left goes after the last one.  So the divergent dda_walk runs on full
 //                    waves where a work-group has batches enough to fill the queue (a call of more than 2048 batches; with a
 //                    survival rate s a drain needs 256 / (1024 s) batches), and on one partial drain per work-group otherwise.
-//                    Per-view counts: per wave over the DISTINCT views present (the __shfl / __ballot loop of k_cluster_reduce),
+//                    Per-view counts: per wave over the DISTINCT views present (wave_count_keys of wave_ops.hpp),
 //                    one atomicAdd per wave, view and quantity.  cover_count: atomicAdd; first_view: unsigned atomicMin (-1 is
 //                    the identity).  The totals: one atomicAdd per wave.
 //   k_view_finish    per view: the counts out; one packed 64-bit atomicMax (n_visible << 32 | ~index) into its group
@@ -37,6 +37,7 @@
 #include "dense_map.hpp"
 #include "ray_query_kernels.hpp"
 #include "ray_walk.hpp"
+#include "wave_ops.hpp"
 
 namespace fiesta {
 struct ViewArgs {  // the call's arguments as fiesta_hip_view_coverage[_dev] takes them, already checked
@@ -197,47 +198,9 @@ __global__ __launch_bounds__(kViewBlock) void k_view_pass(VS s, const ViewCall *
 // exclusive scan of P[0 .. V] in place (P[V] is written with the total); one work-group, the carry in a register
 __global__ __launch_bounds__(kViewScanBlock) void k_view_scan(ViewWork w, int64_t V) {
   __shared__ long long s_wave[kViewScanBlock / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  long long carry = 0;
-  for (int64_t base = 0; base < V; base += kViewScanBlock * kViewScanItems) {  // (the same trip count for every lane: the barriers)
-    const int64_t i0 = base + (int64_t)tid * kViewScanItems;
-    long long x[kViewScanItems], sum = 0;
-#pragma unroll
-    for (int k = 0; k < kViewScanItems; ++k) x[k] = i0 + k < V ? w.P[i0 + k] : 0, sum += x[k];
-    long long inc = sum;
-    for (int off = 1; off < 64; off <<= 1) {
-      const long long u = __shfl_up(inc, off);
-      if (lane >= off) inc += u;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    long long before = 0, total = 0;
-    for (int k = 0; k < kViewScanBlock / 64; ++k) {
-      const long long t = s_wave[k];
-      if (k < wave) before += t;
-      total += t;
-    }
-    long long run = carry + before + inc - sum;
-#pragma unroll
-    for (int k = 0; k < kViewScanItems; ++k) {
-      if (i0 + k < V) w.P[i0 + k] = run;
-      run += x[k];
-    }
-    carry += total;
-    __syncthreads();  // (the next trip overwrites s_wave)
-  }
-  if (tid == 0) w.P[V] = carry, w.ctr[1] = (unsigned long long)carry;
-}
-
-// one atomicAdd per distinct view among the lanes with `flag` (uniform trip count: the number of distinct views in the wave)
-__device__ inline void view_count(int32_t *acc, bool flag, int view, int lane) {
-  unsigned long long todo = __ballot(flag);
-  while (todo) {
-    const int r = __shfl(view, __ffsll((long long)todo) - 1);
-    const unsigned long long same = __ballot(flag && view == r);
-    if (lane == __ffsll((long long)same) - 1) atomicAdd(&acc[r], __popcll(same));
-    todo &= ~same;
-  }
+  const long long total = block_scan_stride<kViewScanItems, kViewScanBlock / 64>(
+      V, s_wave, [&](int64_t v) { return (long long)w.P[v]; }, [&](int64_t v, long long before, long long) { w.P[v] = before; });
+  if (threadIdx.x == 0) w.P[V] = total, w.ctr[1] = (unsigned long long)total;
 }
 
 // the view of pair index idx: the largest v with P[v] <= idx (views without pairs share their successor's P and are skipped)
@@ -317,7 +280,7 @@ __global__ __launch_bounds__(kViewBlock) void k_view_pairs(SRC src, const ViewCa
         if (lane == 0) at = atomicAdd(&s_qn, __popcll(b)), atomicAdd(&w.ctr[2], (unsigned long long)__popcll(b));
         at = __shfl(at, 0) + __popcll(b & ((1ull << lane) - 1));
         if (keep) s_qview[at] = view, s_qent[at] = ent;  // at < kViewQueue: at most 255 left over + the kViewQueueBatch pairs of a batch
-        view_count(w.vin, keep, view, lane);
+        wave_count_keys(w.vin, keep, view);
       }
     }
     __syncthreads();
@@ -365,7 +328,7 @@ __global__ __launch_bounds__(kViewBlock) void k_view_pairs(SRC src, const ViewCa
       const unsigned long long b = __ballot(vis);
       if (b) {  // (uniform per wave)
         if (lane == 0) atomicAdd(&w.ctr[3], (unsigned long long)__popcll(b));
-        view_count(w.vvis, vis, view, lane);
+        wave_count_keys(w.vvis, vis, view);
         if (vis && o.cover_count) atomicAdd(&o.cover_count[ent], 1);
         if (vis && o.first_view) atomicMin((unsigned int *)&o.first_view[ent], (unsigned int)view);
       }

@@ -163,6 +163,36 @@ def test_batch_sizes(scenes, kind):
     assert want["largest"] > 64                          # one cluster across several waves
 
 
+def rods(n, seed):
+    """n entries: rods of 1 .. 3 voxels along x in a lattice of pitch (4, 2, 2) -- no two rods touch, not even across a corner --
+    shuffled, and as the LAST entry a single voxel far from all of them: a root of its own at index n - 1"""
+    rng = np.random.RandomState(seed)
+    cells = np.argwhere(np.ones((24, 16, 16), bool)) * np.array([4, 2, 2]) - np.array([50, 17, 9])
+    length = rng.randint(1, 4, len(cells))
+    vox = np.repeat(cells, length, 0)
+    vox[:, 0] += np.arange(len(vox)) - np.repeat(np.cumsum(length) - length, length)
+    assert len(vox) >= n - 1
+    vox = vox[:n - 1][rng.permutation(n - 1)]
+    return np.ascontiguousarray(np.concatenate([vox, [[300, -200, 100]]]).astype(np.int32))
+
+
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 8193])
+def test_numbering_scan_trips(anymap, n):
+    """k_cluster_number takes kClusterScanBlock * kClusterScanItems = 4096 entries per trip: one entry short of a trip, a whole
+    trip, one entry into the second trip, one into the third.  Thousands of small clusters whose roots lie all over the list, so the
+    ids and member offsets of the later trips are the carry plus a prefix; the last entry is a root alone in its trip at 4097 and
+    8193.  min_size 2 drops the single voxels: the same scan then numbers fewer roots and counts the dropped ones"""
+    vox = rods(n, n)
+    rng = np.random.RandomState(n + 1)
+    mask, key = rng.randint(0, 64, n).astype(np.uint8), rng.randint(-2, 500, n).astype(np.int32)
+    want = check(anymap, vox, mask, key, 26, 1, f"rods n={n}")
+    assert want["n_clusters"] > n // 3 and want["largest"] == 3 and want["root"][-1] == n - 1 and want["size"][-1] == 1
+    assert (np.diff(want["root"]) > 0).all() and want["offsets"][-1] == n
+    kept = check(anymap, vox, mask, key, 6, 2, f"rods n={n}, min_size 2")
+    assert 0 < kept["n_clusters"] < want["n_clusters"] and kept["n_dropped_clusters"] == want["n_clusters"] - kept["n_clusters"]
+    assert kept["label"][-1] == -1
+
+
 def snake(nx=28, ny=28, nz=8):
     """a 6-connected serpentine one voxel wide, in path order: rows along x at every second y, joined at alternating ends by one
     voxel; layers at every second z joined the same way.  Rows and layers are two apart, so no two voxels that are not neighbours

@@ -584,6 +584,39 @@ def test_a_garbage_offset_costs_its_own_two_paths(hip_lib):
     m.close()
 
 
+def test_path_counts_around_the_1024_thread_trip(hip_lib):
+    """device variant, 1023 / 1024 / 1025 paths of two waypoints: k_path_check and k_path_pieces take 1024 paths per trip.  First the
+    offsets as they are (at 1025 the last path's first piece is the carry alone); then the LAST path's first offset is set to 5: in
+    range, so within its own trip (at 1025 it is alone there) it is the largest entry so far -- only the running maximum carried
+    over from the trip before shows that it lies below an earlier offset.  It flags the two paths that share it, nothing else"""
+    import torch
+    from fiesta_amd.esdf_map import PATH_FIELDS
+    m, _ = dense_map(32, obstacles=30)
+    dev = torch.device("cuda", 0)
+    rng = np.random.RandomState(26)
+    for n in (1023, 1024, 1025):
+        a = 0.4 + rng.rand(n, 3) * 2.2
+        W = np.ascontiguousarray(np.stack([a, a + rng.randn(n, 3) * 0.15], 1).reshape(-1, 3))
+        off = np.arange(0, 2 * n + 1, 2).astype(np.int64)
+        want = model(m, W, off, 0.05, 0.25)
+        assert (want["n_samples"] >= 2).all() and (want["first_below"] >= 0).any() and (want["first_below"] < 0).any()
+        bad = off.copy()
+        bad[n - 1] = 5
+        wt = torch.from_numpy(W).to(dev)
+        for offsets, flagged in ((off, []), (bad, [n - 2, n - 1])):
+            outs = {name: torch.full((n,) + shape, -7, dtype=torch.float64 if dt == np.float64 else torch.int64, device=dev)
+                    for name, dt, shape in PATH_FIELDS}
+            ot = torch.from_numpy(offsets).to(dev)
+            torch.cuda.synchronize()   # (the map's stream does not wait for torch's: the fills above must have landed)
+            m.PathClearanceDevice(wt.data_ptr(), len(W), ot.data_ptr(), n, 0.05, 0.25, {k: v.data_ptr() for k, v in outs.items()})
+            m.synchronize()
+            got = {k: v.cpu().numpy() for k, v in outs.items()}
+            assert list(np.nonzero(got["n_samples"] < 0)[0]) == flagged, (n, got["n_samples"][-3:])
+            keep = [q for q in range(n) if q not in flagged]
+            assert_same({k: v[keep] for k, v in got.items()}, {k: v[keep] for k, v in want.items()}, f"{n} paths, flagged {flagged}")
+    m.close()
+
+
 def test_hash_block_map_device_variant_and_host_cache(hip_lib):
     """hash-block map: the device variant with its offset check, and the host brick cache over a field that varies"""
     import torch

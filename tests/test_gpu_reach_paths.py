@@ -392,9 +392,10 @@ def test_capacity(maze):
         assert m.ReachPaths(tg, connectivity=conn, shortcut=shortcut, max_span=span, want_pos=False)["waypoints_pos"] is None
 
 
-@pytest.mark.parametrize("count", [1, 63, 64, 65, 257])
+@pytest.mark.parametrize("count", [1, 63, 64, 65, 257, 513])
 def test_batch_shape(maze, count):
-    """raw mode takes a lane per target, shortcut mode a wave: the per-target results do not depend on the batch"""
+    """raw mode takes a lane per target, shortcut mode a wave: the per-target results do not depend on the batch (257, 513: a second
+    and a third trip of the 256 entries the offset scan takes at a time)"""
     m, conn = maze.m, 26
     maze.flood(conn)
     n = len(maze.targets)

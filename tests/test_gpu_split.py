@@ -108,6 +108,34 @@ def test_the_sheet(maps, kind, params):
         assert want["n_parts"] >= 81 and want["n_oversize"] == 0 and want["deepest"] >= 7
 
 
+def two_sheets(n_members):
+    """two clusters of unequal size -- a strip 7 voxels wide with a third of the members, a strip 13 wide with the rest, far apart --
+    over a shuffled entry list, each segment's members in a shuffled order"""
+    rng = np.random.RandomState(n_members)
+    na = n_members // 3
+    nb = n_members - na
+    a = np.stack([np.arange(na) // 7, np.arange(na) % 7, np.zeros(na, int)], 1) + (-60, 4, 9)
+    b = np.stack([np.arange(nb) % 13, np.full(nb, 2), np.arange(nb) // 13], 1) + (200, -30, -11)
+    place = rng.permutation(n_members)                                     # entry index of voxel j of a ++ b
+    v = np.empty((n_members, 3), np.int32)
+    v[place] = np.concatenate([a, b])
+    mem = np.concatenate([rng.permutation(place[:na]), rng.permutation(place[na:])]).astype(np.int64)
+    mask, key = (1 << rng.randint(0, 7, n_members)).astype(np.uint8), rng.randint(-2, 900, n_members).astype(np.int32)
+    return np.ascontiguousarray(v), np.array([0, na, n_members], np.int64), mem, mask, key
+
+
+@pytest.mark.parametrize("kind", ["dense", "hash"])
+@pytest.mark.parametrize("n_members", [2047, 2048, 2049, 4097])
+def test_member_counts_around_the_scan_tile(maps, kind, n_members):
+    """kSplitTile = 2048 members are one work-group's share of the member scan: one member short of a tile, a whole tile, one member
+    into the second tile, one into the third.  The second cluster starts inside the first tile, so that tile holds a head flag in
+    its middle and high-side flags of two parts; max_size makes the smaller cluster cut once and the larger at least twice"""
+    v, off, mem, mask, key = two_sheets(n_members)
+    want = check(maps[kind], v, off, mem, mask, key, what=f"{kind} {n_members} members", max_size=n_members // 5)
+    assert want["n_split_clusters"] == 2 and want["deepest"] >= 2 and want["n_oversize"] == 0 and want["n_members"] == n_members
+    assert 0 < off[1] < 2048 and sorted(set(want["parent"].tolist())) == [0, 1]
+
+
 def test_three_clusters_with_duplicates_invalid_entries_and_dropped_specks(maps):
     v, mask, key = three_clusters()
     m = maps["dense"]

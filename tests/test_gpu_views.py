@@ -259,6 +259,26 @@ def test_view_counts(scene, n_views):
     assert_same(s.call(**kw), s.model(**kw), f"{n_views} views")
 
 
+def test_one_view_past_a_trip_of_the_pair_scan(scene):
+    """4097 views: k_view_scan takes kViewScanBlock * kViewScanItems = 4096 pair counts per trip, so the last view's first pair is
+    the carry alone, and the total is the carry plus that view's count.  Six groups of 0 .. 3 targets that lie close together (the
+    model stays cheap); the views repeat the scene's, the last two are usable ones of groups that have members"""
+    s = scene
+    n_views = 4097
+    sizes = np.array([3, 1, 2, 0, 3, 1])
+    offsets = np.concatenate([[0], np.cumsum(sizes)])
+    near = np.argsort(np.abs(s.vox - s.vox[40]).sum(1), kind="stable")[:6]
+    members = near[np.arange(offsets[-1]) % 6]
+    idx = (np.arange(n_views) * 5) % len(s.pos)
+    usable = np.flatnonzero((s.main(3)["n_visible"] >= 0) & (sizes[np.clip(s.group, 0, 5)] > 0))
+    idx[-2:] = usable[[3, len(usable) // 2]]
+    kw = dict(pos=s.pos[idx], dir=s.dir[idx], group=s.group[idx], offsets=offsets, members=members, min_visible=1)
+    want = s.model(**kw)
+    assert (want["n_visible"][-2:] >= 0).all() and (want["n_visible"] < 0).any() and want["pairs_visible"] > 0
+    assert want["n_pairs"] == sizes[s.group[idx][want["n_visible"] >= 0]].sum() > 0
+    assert_same(s.call(**kw), want, "4097 views")
+
+
 def test_many_tiny_groups_share_a_wave(scene):
     """groups of 0 .. 3 members: one wave of the pair kernel serves dozens of views"""
     s = scene
