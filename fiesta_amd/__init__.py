@@ -9,8 +9,8 @@ from .esdf_map import (D2_INF, INFINITY, UNDEFINED, ESDFMap, frontier_model, pat
 from .cluster_model import cluster_model, cluster_stencil  # noqa: F401
 from .split_model import SPLIT_INVALID, SPLIT_MAX_DEPTH, SPLIT_OK, split_model  # noqa: F401
 from .view_model import VIEW_OMNI, view_coverage_model, view_ring  # noqa: F401
-from .reach_model import (REACH_PATHS_SHORTCUT, REACH_THROUGH_UNKNOWN, reach_matrix_model, reach_model, reach_moves,  # noqa: F401
-                          reach_paths_model, reach_visible, reach_walk)
+from .reach_model import (LEG_BAD_INDEX, LEG_NO_SOURCE, REACH_PATHS_SHORTCUT, REACH_THROUGH_UNKNOWN, leg_paths_model,  # noqa: F401
+                          reach_matrix_model, reach_model, reach_moves, reach_paths_model, reach_visible, reach_walk)
 from .corridor_model import (CORRIDOR_BLOCKED, CORRIDOR_INVALID, CORRIDOR_MAX_GROW, CORRIDOR_OK, CORRIDOR_STOP_BLOCKED,  # noqa: F401
                              CORRIDOR_STOP_EDGE, CORRIDOR_STOP_LIMIT, CORRIDOR_THROUGH_UNKNOWN, FREE_BOX_BLOCKED, FREE_BOX_OK,
                              FREE_BOX_OUTSIDE, corridor_chain, corridor_model, free_box_model)
@@ -21,5 +21,5 @@ from .tour_model import TOUR_CLOSED, best_move, tour_model  # noqa: F401
 __all__ = ["path_refine_model", "path_refine_gradient", "corridor_bounds", "corridor_bounds_model", "BOUNDS_VOID_BROKEN","REFINE_OK", "REFINE_INVALID", "REFINE_MAX_WAYPOINTS",
            "REFINE_MAX_ITERATIONS", "free_box_model", "corridor_chain", "corridor_model", "CORRIDOR_THROUGH_UNKNOWN", "CORRIDOR_MAX_GROW", "CORRIDOR_STOP_BLOCKED",
            "CORRIDOR_STOP_EDGE", "CORRIDOR_STOP_LIMIT", "FREE_BOX_OK", "FREE_BOX_OUTSIDE", "FREE_BOX_BLOCKED", "CORRIDOR_OK", "CORRIDOR_INVALID",
-           "CORRIDOR_BLOCKED", "tour_model", "best_move", "TOUR_CLOSED", "ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "reach_model", "reach_matrix_model", "REACH_THROUGH_UNKNOWN", "reach_moves", "reach_paths_model", "reach_visible", "reach_walk", "REACH_PATHS_SHORTCUT", "cluster_model", "cluster_stencil", "split_model", "SPLIT_OK", "SPLIT_INVALID", "SPLIT_MAX_DEPTH", "view_coverage_model", "view_ring", "VIEW_OMNI", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
+           "CORRIDOR_BLOCKED", "tour_model", "best_move", "TOUR_CLOSED", "ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "reach_model", "reach_matrix_model", "REACH_THROUGH_UNKNOWN", "reach_moves", "reach_paths_model", "leg_paths_model", "LEG_NO_SOURCE", "LEG_BAD_INDEX", "reach_visible", "reach_walk", "REACH_PATHS_SHORTCUT", "cluster_model", "cluster_stencil", "split_model", "SPLIT_OK", "SPLIT_INVALID", "SPLIT_MAX_DEPTH", "view_coverage_model", "view_ring", "VIEW_OMNI", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
            "D2_INF"]

@@ -124,6 +124,18 @@ class ReachPathsResult(C.Structure):
                 ("n_moves", C.c_void_p)]
 
 
+class LegPathsResult(C.Structure):
+    """fiesta_hip_leg_paths_result: offsets is required, every other pointer nullable"""
+    _fields_ = [("offsets", C.c_void_p), ("waypoints_vox", C.c_void_p), ("waypoints_pos", C.c_void_p), ("status", C.c_void_p),
+                ("n_moves", C.c_void_p), ("cost", C.c_void_p)]
+
+
+class LegPathsInfo(C.Structure):
+    """fiesta_hip_leg_paths_info: the batch a map retains from its last fiesta_hip_reach_matrix call"""
+    _fields_ = [("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3), ("connectivity", C.c_int32), ("reserved", C.c_int32),
+                ("n_sources", C.c_int64)]
+
+
 class FreeBoxesResult(C.Structure):
     """fiesta_hip_free_boxes_result: one array per output of fiesta_hip_free_boxes, every pointer nullable"""
     _fields_ = [("box", C.c_void_p), ("box_pos", C.c_void_p), ("stop", C.c_void_p), ("volume", C.c_void_p), ("status", C.c_void_p)]
@@ -309,6 +321,8 @@ def load():
         "fiesta_hip_site_tour_dev": (C.c_int, [vp, vp, i32, i64, i32, i32, i32, C.c_uint64, i32, vp, vp]),
         "fiesta_hip_reach_paths": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
         "fiesta_hip_reach_paths_dev": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i64, vp]),
+        "fiesta_hip_leg_paths": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, vp, vp]),
+        "fiesta_hip_leg_paths_dev": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, vp, vp]),
         "fiesta_hip_free_boxes": (C.c_int, [vp, vp, vp, vp, i64, dbl, i32, i32, vp]),
         "fiesta_hip_free_boxes_dev": (C.c_int, [vp, vp, vp, vp, i64, dbl, i32, i32, vp]),
         "fiesta_hip_path_corridor": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i64, vp]),

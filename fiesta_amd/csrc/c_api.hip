@@ -7,12 +7,13 @@
 #include <string>
 
 #include "../../include/fiesta_hip.h"
-#include "bounds_kernels.hpp"  // (the thirteen planner headers: for the calls' argument aggregates; no kernel is used here)
+#include "bounds_kernels.hpp"  // (the fourteen planner headers: for the calls' argument aggregates; no kernel is used here)
 #include "cluster_kernels.hpp"
 #include "corridor_kernels.hpp"
 #include "dense_map.hpp"
 #include "frontier_kernels.hpp"
 #include "hash_map.hpp"
+#include "leg_path_kernels.hpp"
 #include "path_cost_kernels.hpp"
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
@@ -177,6 +178,19 @@ void reach_paths(fiesta_hip_map *m, const fiesta::ReachPathArgs &a) {
   }
   need(m != nullptr, "null map handle");
   on_store(m, [&](auto &s) { s.reach_paths(a); });
+}
+// none of these errors needs a device, and all are checked before the handle is touched; whether a batch is retained is the map's to say
+void leg_paths(fiesta_hip_map *m, const fiesta::LegPathArgs &a) {
+  need(a.res != nullptr, "leg_paths: result is null");
+  need(a.res->offsets != nullptr, "leg_paths: result->offsets is null");
+  need(a.n_legs >= 0, "leg_paths: negative count");
+  need(a.capacity >= 0, "leg_paths: negative capacity");
+  need((a.flags & ~FIESTA_HIP_REACH_PATHS_SHORTCUT) == 0, "leg_paths: unknown flag bits");
+  need(!(a.flags & FIESTA_HIP_REACH_PATHS_SHORTCUT) || a.max_span >= 1, "leg_paths: max_span must be >= 1 with SHORTCUT");
+  need(a.from != nullptr || a.n_legs == 0, "leg_paths: from is null");
+  need((a.to != nullptr) != (a.to_vox != nullptr) || a.n_legs == 0, "leg_paths: exactly one of to and to_vox must be given");
+  need(m != nullptr, "null map handle");
+  on_store(m, [&](auto &s) { s.leg_paths(a); });
 }
 // fiesta_hip_free_boxes and fiesta_hip_path_corridor: none of these errors needs a device, and all are checked before the handle
 // is touched (a host batch: the CSR rules as well)
@@ -725,6 +739,15 @@ int fiesta_hip_reach_paths_dev(fiesta_hip_map *m, const int32_t *cost_dev, const
                                const int32_t *targets_dev, int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span,
                                int64_t capacity, const fiesta_hip_reach_paths_result *result) {
   return guarded([&] { reach_paths(m, {cost_dev, box_lo, box_hi, targets_dev, n_targets, connectivity, flags, max_span, capacity, result, true}); });
+}
+int fiesta_hip_leg_paths(fiesta_hip_map *m, const int32_t *from, const int32_t *to, const int32_t *to_vox, int64_t n_legs, int32_t flags,
+                         int32_t max_span, int64_t capacity, const fiesta_hip_leg_paths_result *result, fiesta_hip_leg_paths_info *info) {
+  return guarded([&] { leg_paths(m, {from, to, to_vox, n_legs, flags, max_span, capacity, result, info, false}); });
+}
+int fiesta_hip_leg_paths_dev(fiesta_hip_map *m, const int32_t *from_dev, const int32_t *to_dev, const int32_t *to_vox_dev, int64_t n_legs,
+                             int32_t flags, int32_t max_span, int64_t capacity, const fiesta_hip_leg_paths_result *result,
+                             fiesta_hip_leg_paths_info *info) {
+  return guarded([&] { leg_paths(m, {from_dev, to_dev, to_vox_dev, n_legs, flags, max_span, capacity, result, info, true}); });
 }
 int fiesta_hip_free_boxes(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], const int32_t *seeds, int64_t n, double min_clearance,
                           int32_t max_grow, int32_t flags, const fiesta_hip_free_boxes_result *result) {

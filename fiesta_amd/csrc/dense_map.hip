@@ -28,6 +28,7 @@
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
 #include "reach_matrix_kernels.hpp"
+#include "leg_path_kernels.hpp"
 #include "reach_path_kernels.hpp"
 #include "corridor_kernels.hpp"
 #include "tour_kernels.hpp"
@@ -2603,6 +2604,8 @@ void DenseMap::reach_matrix(const ReachMatrixArgs &a) {
 
 // fiesta_hip_reach_paths[_dev], fiesta_hip_cluster_voxels[_dev] and fiesta_hip_split_clusters[_dev]: nothing of the map is read but its resolution and origin
 void DenseMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
+// fiesta_hip_leg_paths[_dev] (leg_path_kernels.hpp): the same, and the batch the last reach_matrix call retained
+void DenseMap::leg_paths(const LegPathArgs &a) { use_device(), leg_paths_run(stream_, planner_, g_.res, g_.org, a); }
 void DenseMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
 void DenseMap::split_clusters(const SplitArgs &a) { use_device(), split_clusters_run(stream_, planner_, g_.res, g_.org, a); }
 // fiesta_hip_corridor_bounds[_dev] (bounds_kernels.hpp): nothing of the map is read at all

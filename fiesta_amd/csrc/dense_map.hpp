@@ -66,10 +66,20 @@ struct ReachScratch {
 // scratch of fiesta_hip_reach_matrix (reach_matrix_kernels.hpp), owned by a map: the cost planes of one batch of floods, the flags and
 // lists of their (flood, tile) items for both round parities, the counters, and the per-source status and reached counts; allocated
 // on first use, grown on demand, freed with the map.  (The bitmap is ReachScratch::bits; ReachScratch::cost is never touched.)
+// batch_*: what `planes` holds for fiesta_hip_leg_paths (leg_path_kernels.hpp) -- the RETAINED batch: valid after a reach_matrix call
+// that succeeded with at least one source, a non-empty box and all sources in ONE batch (plane s is source s's flood, `status` its
+// per-source status); its inclusive box in map voxel coordinates, its connectivity, the number of sources and `sites`, the
+// call's own copy of the source voxels.  batch_why says what the last call left when it left no batch.
 struct ReachMatrixScratch {
-  DevBuf<int32_t> planes, status;
+  enum { kNoCallYet = 0, kManyBatches = 1, kNothingToKeep = 2 };
+  DevBuf<int32_t> planes, status, sites;
   DevBuf<uint32_t> flags, lists;
   DevBuf<unsigned long long> ctr, reached;
+  bool batch_valid = false;
+  int batch_why = kNoCallYet;
+  int32_t batch_lo[3] = {0, 0, 0}, batch_hi[3] = {0, 0, 0};
+  int batch_connectivity = 0;
+  int64_t batch_sources = 0;
 };
 
 // scratch of fiesta_hip_site_tour (tour_kernels.hpp), owned by a map: the call's header words and info, the visited sites and the
@@ -160,6 +170,7 @@ struct RayArgs;
 struct ReachArgs;
 struct ReachMatrixArgs;
 struct ReachPathArgs;
+struct LegPathArgs;
 struct CorridorArgs;
 struct PathRefineArgs;
 struct CorridorBoundsArgs;
@@ -276,6 +287,7 @@ class DenseMap {
   void reach_matrix(const ReachMatrixArgs &a);
   void site_tour(const TourArgs &a);
   void reach_paths(const ReachPathArgs &a);
+  void leg_paths(const LegPathArgs &a);
   void corridor(const CorridorArgs &a);
   void corridor_bounds(const CorridorBoundsArgs &a);
   void cluster_voxels(const ClusterArgs &a);

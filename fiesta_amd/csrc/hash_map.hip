@@ -25,6 +25,7 @@
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
 #include "reach_matrix_kernels.hpp"
+#include "leg_path_kernels.hpp"
 #include "reach_path_kernels.hpp"
 #include "corridor_kernels.hpp"
 #include "tour_kernels.hpp"
@@ -1631,6 +1632,8 @@ void HashMap::reach_matrix(const ReachMatrixArgs &a) {
 
 // fiesta_hip_reach_paths[_dev], fiesta_hip_cluster_voxels[_dev] and fiesta_hip_split_clusters[_dev]: nothing of the map is read but its resolution and origin
 void HashMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
+// fiesta_hip_leg_paths[_dev] (leg_path_kernels.hpp): the same, and the batch the last reach_matrix call retained
+void HashMap::leg_paths(const LegPathArgs &a) { use_device(), leg_paths_run(stream_, planner_, g_.res, g_.org, a); }
 void HashMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
 void HashMap::split_clusters(const SplitArgs &a) { use_device(), split_clusters_run(stream_, planner_, g_.res, g_.org, a); }
 // fiesta_hip_corridor_bounds[_dev] (bounds_kernels.hpp): nothing of the map is read at all

@@ -88,6 +88,7 @@ class HashMap {
   void reach_matrix(const ReachMatrixArgs &a);
   void site_tour(const TourArgs &a);
   void reach_paths(const ReachPathArgs &a);
+  void leg_paths(const LegPathArgs &a);
   void corridor(const CorridorArgs &a);
   void corridor_bounds(const CorridorBoundsArgs &a);
   void cluster_voxels(const ClusterArgs &a);

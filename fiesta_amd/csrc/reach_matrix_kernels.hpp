@@ -137,12 +137,14 @@ __global__ __launch_bounds__(256) void k_rmx_count(const int32_t *planes, int64_
 
 // Both variants of the call on a map's stream; lo / hi / off as for reach_run.  Both variants synchronise.
 // Neither ReachScratch::cost nor field_valid is touched: what fiesta_hip_reach_paths retains stays as it was.
+// What fiesta_hip_leg_paths descends (ReachMatrixScratch::batch_*) is cleared on entry and set by a call that ends in one batch.
 template <class SRC>
 void reach_matrix_run(hipStream_t st, PlannerScratch &P, const SRC &src, const int64_t lo[3], const int64_t hi[3], const int off[3],
                       const ReachMatrixArgs &a) {
   ReachMatrixScratch &S = P.reach_matrix;
   const fiesta_hip_reach_matrix_result &res = *a.res;
   const int64_t n = a.n_sources, n_cols = a.targets ? a.n_targets : n;
+  S.batch_valid = false, S.batch_why = ReachMatrixScratch::kNothingToKeep;  // (fiesta_hip_leg_paths' retained batch: set at the very end)
   if (a.info) *a.info = fiesta_hip_reach_matrix_info{};
   const bool want_cost = res.cost && n > 0 && n_cols > 0;
   // the staged inputs and the staged matrix of the host variant
@@ -253,7 +255,22 @@ void reach_matrix_run(hipStream_t st, PlannerScratch &P, const SRC &src, const i
     }
   }
   if (n == 0) read_counters();  // (the traversable count alone)
+  // one batch: plane s is source s's flood and stays so until the next call -- the batch fiesta_hip_leg_paths descends.  The sources
+  // are copied: the caller's array may be freed, the host variant's staging is the next call's
+  const bool keep = n > 0 && batches == 1;
+  if (keep) {
+    S.sites.ensure((size_t)(3 * n), st);
+    FIESTA_HIP_CHECK(hipMemcpyAsync(S.sites.p, dsources, (size_t)(3 * n) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  }
   results_back();
+  if (keep) {
+    S.batch_lo[0] = ox, S.batch_lo[1] = oy, S.batch_lo[2] = oz;
+    for (int c = 0; c < 3; ++c) S.batch_hi[c] = (int32_t)(hi[c] + off[c]);
+    S.batch_connectivity = a.connectivity, S.batch_sources = n;
+    S.batch_valid = true;
+  } else if (n > 0) {
+    S.batch_why = ReachMatrixScratch::kManyBatches;
+  }
   if (a.info) {
     fiesta_hip_reach_matrix_info &I = *a.info;
     I.box_lo[0] = ox, I.box_lo[1] = oy, I.box_lo[2] = oz;

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, BoundsResult, Stats, TourInfo, TourResult, check
+from ._lib import ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, LegPathsInfo, LegPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, BoundsResult, Stats, TourInfo, TourResult, check
 from .refine_model import BOUNDS_VOID_BROKEN
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
@@ -929,6 +929,80 @@ class ESDFMap:
         check(self._lib.fiesta_hip_reach_paths_dev(self._h, C.c_void_p(cost_dev_ptr or None), _p(blo), _p(bhi), C.c_void_p(targets_dev_ptr or None),
                                                    int(n_targets), int(connectivity), 1 if shortcut else 0, int(max_span), int(capacity),
                                                    C.byref(res)))
+
+    @staticmethod
+    def _leg_info(info) -> dict:
+        return {"box_lo": list(info.box_lo), "box_hi": list(info.box_hi), "connectivity": int(info.connectivity), "n_sources": int(info.n_sources)}
+
+    def LegPaths(self, from_, to=None, to_vox=None, shortcut=False, max_span=4096, want_pos=True) -> dict:
+        """fiesta_hip_leg_paths: per leg the path from site from_[k] -- an index into the sources of the map's last ReachMatrix call,
+        whose floods the map retains while they fitted one batch (its "batches" == 1) -- to site to[k], or to map voxel to_vox[k]
+        (exactly one of the two), with nothing flooded again.  A tour's legs: from_ = order[:m - 1], to = order[1:m] of SiteTour.
+        shortcut / max_span as in ReachPaths; the connectivity is the retained batch's.  Returns offsets ((n + 1,) int64 CSR),
+        waypoints_vox ((N, 3) int32, each leg from its source to its target), waypoints_pos ((N, 3) f64 metres; None without
+        want_pos), status ((n,) int32: REACH_PATH_*, LEG_NO_SOURCE, LEG_BAD_INDEX), n_moves, cost ((n,) int32: the matrix entry of
+        the leg) and what is retained: box_lo, box_hi, connectivity, n_sources; fiesta_amd.leg_paths_model is the definition"""
+        if (to is None) == (to_vox is None):
+            raise ValueError("exactly one of to and to_vox must be given")
+        f = np.ascontiguousarray(from_, dtype=np.int32).reshape(-1)
+        n = len(f)
+        t = None if to is None else np.ascontiguousarray(to, dtype=np.int32).reshape(-1)
+        tv = None if to_vox is None else np.ascontiguousarray(to_vox, dtype=np.int32).reshape(-1, 3)
+        if len(t if tv is None else tv) != n:
+            raise ValueError("from_ and to / to_vox differ in length")
+        # (an empty batch keeps the pointers non-null: which of to / to_vox is meant does not matter then)
+        args = (_p(f) if n else None, _p(t) if n and t is not None else None, _p(tv) if n and tv is not None else None, n, 1 if shortcut else 0,
+                int(max_span))
+        out = {"offsets": np.zeros(n + 1, np.int64), "status": np.empty(n, np.int32), "n_moves": np.empty(n, np.int32), "cost": np.empty(n, np.int32)}
+        ptr = lambda k: out[k].ctypes.data if n else None  # noqa: E731
+        info = LegPathsInfo()
+        res = LegPathsResult(out["offsets"].ctypes.data, None, None, ptr("status"), ptr("n_moves"), ptr("cost"))
+        check(self._lib.fiesta_hip_leg_paths(self._h, *args, 0, C.byref(res), C.byref(info)))
+        total = int(out["offsets"][n])
+        out["waypoints_vox"] = np.empty((total, 3), np.int32)
+        out["waypoints_pos"] = np.empty((total, 3), np.float64) if want_pos else None
+        if total:
+            res = LegPathsResult(out["offsets"].ctypes.data, out["waypoints_vox"].ctypes.data, out["waypoints_pos"].ctypes.data if want_pos else None,
+                                 None, None, None)
+            check(self._lib.fiesta_hip_leg_paths(self._h, *args, total, C.byref(res), None))
+        out.update(self._leg_info(info))
+        return out
+
+    def LegPathsDevice(self, from_dev_ptr: int, n_legs: int, offsets_dev_ptr: int, to_dev_ptr: int = 0, to_vox_dev_ptr: int = 0, shortcut=False,
+                       max_span=4096, capacity: int = 0, waypoints_vox_dev_ptr: int = 0, waypoints_pos_dev_ptr: int = 0, status_dev_ptr: int = 0,
+                       n_moves_dev_ptr: int = 0, cost_dev_ptr: int = 0) -> dict:
+        """fiesta_hip_leg_paths_dev: from, to (n_legs int32 each; they may be views into the order array where SiteTourDevice left
+        it) or to_vox (n_legs x 3 int32) and the outputs resident on the device (offsets: n_legs + 1 int64, required; 0: that array
+        is not written); only enqueued on the map's stream.  offsets holds the true totals whatever `capacity` is: enqueue with
+        capacity 0 to size the buffers.  Returns what the map retains: box_lo, box_hi, connectivity, n_sources"""
+        res = LegPathsResult(*[int(v) or None for v in (offsets_dev_ptr, waypoints_vox_dev_ptr, waypoints_pos_dev_ptr, status_dev_ptr,
+                                                        n_moves_dev_ptr, cost_dev_ptr)])
+        info = LegPathsInfo()
+        check(self._lib.fiesta_hip_leg_paths_dev(self._h, C.c_void_p(from_dev_ptr or None), C.c_void_p(to_dev_ptr or None),
+                                                 C.c_void_p(to_vox_dev_ptr or None), int(n_legs), 1 if shortcut else 0, int(max_span), int(capacity),
+                                                 C.byref(res), C.byref(info)))
+        return self._leg_info(info)
+
+    def TourRoute(self, sites, start=0, closed=False, lo=None, hi=None, min_clearance=0.0, connectivity=26, flags=0, restarts=64, seed=0,
+                  max_moves=0, shortcut=False, max_span=4096, want_pos=True) -> dict:
+        """ReachMatrix -> SiteTour -> LegPaths: the order in which to visit `sites` ((n, 3) map voxels) from sites[start] and the way
+        along every leg, the box flooded once per site and never again.  The matrix arguments are ReachMatrix's (all sites must fit
+        one batch: else ValueError), the tour's SiteTour's, the paths' LegPaths'.  Leg k runs from order[k] to order[k + 1]; a
+        closed tour gets the wrap-around leg order[m - 1] -> order[0] as its last.  Returns SiteTour's dict plus matrix (the cost
+        matrix), source_status and legs: LegPaths' dict with its `from` and `to`"""
+        mx = self.ReachMatrix(sites, lo=lo, hi=hi, min_clearance=min_clearance, connectivity=connectivity, flags=flags)
+        if mx["batches"] != 1:
+            raise ValueError("the sites' floods do not fit one batch (or the box is empty): no legs can be extracted")
+        out = self.SiteTour(mx["cost"], start=start, closed=closed, restarts=restarts, seed=seed, max_moves=max_moves)
+        m = int(out["n_visited"])
+        order = out["order"][:m]
+        fr, to = order[:-1], order[1:]
+        if closed and m >= 2:
+            fr, to = order, np.concatenate([order[1:], order[:1]])
+        legs = self.LegPaths(fr, to=to, shortcut=shortcut, max_span=max_span, want_pos=want_pos)
+        legs["from"], legs["to"] = np.array(fr, np.int32), np.array(to, np.int32)
+        out.update(matrix=mx["cost"], source_status=mx["source_status"], legs=legs)
+        return out
 
     @staticmethod
     def _window(lo, hi):

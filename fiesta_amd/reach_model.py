@@ -314,3 +314,68 @@ def reach_paths_model(cost3d, box_lo, targets, connectivity=26, flags=0, max_spa
     vox = np.array([w for p in paths for w in p], np.int64).reshape(-1, 3) + np.array(lo, np.int64)
     pos = (vox.astype(np.float64) + 0.5) * float(resolution) + np.asarray(origin, np.float64).reshape(3)
     return {"offsets": offsets, "waypoints_vox": vox.astype(np.int32), "waypoints_pos": pos, "status": status, "n_moves": n_moves}
+
+
+# ---- fiesta_hip_leg_paths: the legs of a tour, out of the reach matrix's floods ---------------------------------------------------
+LEG_NO_SOURCE = 5              # FIESTA_HIP_LEG_NO_SOURCE: the leg's source is not REACH_SITE_OK
+LEG_BAD_INDEX = 6              # FIESTA_HIP_LEG_BAD_INDEX: from, or to, is no index into the sources
+
+
+def leg_paths_model(observed, occupied, sources, from_, to=None, to_vox=None, dist=None, lo=None, hi=None, min_clearance=0.0, connectivity=26,
+                    flags=0, path_flags=0, max_span=4096, origin_vox=(0, 0, 0), origin=(0.0, 0.0, 0.0), resolution=1.0, floods=None):
+    """The definition of fiesta_hip_leg_paths (include/fiesta_hip.h), plain and slow.  The arrays, `sources`, the box and the
+    traversability arguments are reach_matrix_model's: they stand for the batch the matrix call retained.  Leg k runs from source
+    from_[k] to source to[k], or to map voxel to_vox[k]; exactly one of `to` and `to_vox` is given.  One reach_model flood per
+    distinct usable `from`, then reach_paths_model (path_flags: REACH_PATHS_SHORTCUT or 0; max_span) on that flood's cost for the
+    legs that start there.  Status by precedence: LEG_BAD_INDEX (from or to outside 0 .. n - 1), LEG_NO_SOURCE (the source is not
+    REACH_SITE_OK), else reach_paths_model's.  Returns reach_paths_model's dict -- the paths run from the source to the target --
+    plus cost ((n_legs,) int32: the source's flood at the target voxel, -1 outside the box, -1 for NO_SOURCE and BAD_INDEX) and
+    box_lo, box_hi, connectivity, n_sources.  An empty clipped box or no source retains no batch: ValueError.  `floods`: a dict
+    that keeps reach_model's result per source index between calls on the SAME batch (same arrays, sources, box and traversability)."""
+    if (to is None) == (to_vox is None):
+        raise ValueError("exactly one of to and to_vox must be given")
+    src = np.asarray(sources, dtype=np.int64).reshape(-1, 3)
+    n = len(src)
+    kw = dict(dist=dist, lo=lo, hi=hi, min_clearance=min_clearance, connectivity=connectivity, flags=flags, origin_vox=origin_vox)
+    base = reach_model(observed, occupied, np.zeros((0, 3), np.int64), targets=src, **kw)   # no seed: the box and traversable(source)
+    if n == 0 or base["cost"].size == 0:
+        raise ValueError("no batch is retained: no source, or an empty clipped box")
+    blo, bhi = np.array(base["box_lo"], np.int64), np.array(base["box_hi"], np.int64)
+    usable = np.all((src >= blo) & (src <= bhi), axis=1) & (base["target_cost"] != REACH_BLOCKED)
+    fr = np.asarray(from_, dtype=np.int64).reshape(-1)
+    legs = len(fr)
+    if to is not None:
+        ti = np.asarray(to, dtype=np.int64).reshape(-1)
+        good = (fr >= 0) & (fr < n) & (ti >= 0) & (ti < n)
+        tv = src[np.where(good, ti, 0)]
+    else:
+        tv = np.asarray(to_vox, dtype=np.int64).reshape(-1, 3)
+        good = (fr >= 0) & (fr < n)
+    if len(tv) != legs:
+        raise ValueError("from and to / to_vox differ in length")
+    status = np.full(legs, LEG_BAD_INDEX, np.int32)
+    n_moves = np.full(legs, -1, np.int32)
+    cost = np.full(legs, REACH_BLOCKED, np.int32)
+    paths = [(np.zeros((0, 3), np.int32), np.zeros((0, 3), np.float64))] * legs
+    status[good & ~usable[np.where(good, fr, 0)]] = LEG_NO_SOURCE
+    for s in sorted(set(fr[good & usable[np.where(good, fr, 0)]].tolist())):
+        k = np.flatnonzero(good & (fr == s))
+        if floods is None or s not in floods:
+            field = reach_model(observed, occupied, src[s:s + 1], **kw)
+            if floods is not None:
+                floods[s] = field
+        field = field if floods is None else floods[s]
+        r = reach_paths_model(field["cost"], field["box_lo"], tv[k], connectivity, path_flags, max_span, origin, resolution)
+        status[k], n_moves[k] = r["status"], r["n_moves"]
+        loc = tv[k] - blo
+        inside = np.all((loc >= 0) & (loc <= bhi - blo), axis=1)
+        cost[k[inside]] = field["cost"][loc[inside, 0], loc[inside, 1], loc[inside, 2]]
+        for j, leg in enumerate(k):
+            a, b = int(r["offsets"][j]), int(r["offsets"][j + 1])
+            paths[leg] = (r["waypoints_vox"][a:b], r["waypoints_pos"][a:b])
+    offsets = np.zeros(legs + 1, np.int64)
+    offsets[1:] = np.cumsum([len(p[0]) for p in paths])
+    vox = np.concatenate([p[0] for p in paths] + [np.zeros((0, 3), np.int32)]).astype(np.int32)
+    pos = np.concatenate([p[1] for p in paths] + [np.zeros((0, 3), np.float64)]).astype(np.float64)
+    return {"offsets": offsets, "waypoints_vox": vox, "waypoints_pos": pos, "status": status, "n_moves": n_moves, "cost": cost,
+            "box_lo": base["box_lo"], "box_hi": base["box_hi"], "connectivity": int(connectivity), "n_sources": n}

@@ -425,6 +425,65 @@ class ESDFMap {
     }
     return out;
   }
+  // Leg paths (fiesta_hip_leg_paths, include/fiesta_hip.h): per leg the path from site from[k] -- an index into the sources of the
+  // last ReachMatrix call, whose floods the map retains while they fitted one batch (info.batches == 1) -- to site to[k], with nothing
+  // flooded again; `to_vox` (non-null: `to` is ignored) names map voxels as targets instead.  shortcut / max_span as in ReachPaths; the
+  // connectivity is the retained batch's.  The set is ReachPaths' (each leg from its source to its target: consecutive legs of a
+  // tour concatenate) plus cost, the matrix entry of every leg, and info, what is retained.  status: FIESTA_HIP_REACH_PATH_*,
+  // FIESTA_HIP_LEG_NO_SOURCE, FIESTA_HIP_LEG_BAD_INDEX.
+  struct LegPathsResult {
+    ReachPathSet paths;
+    std::vector<int32_t> cost;
+    fiesta_hip_leg_paths_info info;
+  };
+  LegPathsResult LegPaths(const std::vector<int32_t> &from, const std::vector<int32_t> &to, bool shortcut = false, int32_t max_span = 4096,
+                          const std::vector<Eigen::Vector3i> *to_vox = nullptr) {
+    Flush();
+    const int64_t n = (int64_t)from.size();
+    if ((to_vox ? to_vox->size() : to.size()) != from.size()) throw std::invalid_argument("LegPaths: from and to differ in length");
+    std::vector<int32_t> tv;
+    for (size_t k = 0; to_vox && k < to_vox->size(); ++k) tv.insert(tv.end(), {(*to_vox)[k](0), (*to_vox)[k](1), (*to_vox)[k](2)});
+    const int32_t *pf = n ? from.data() : nullptr, *pt = n && !to_vox ? to.data() : nullptr, *pv = n && to_vox ? tv.data() : nullptr;
+    const int32_t flags = shortcut ? FIESTA_HIP_REACH_PATHS_SHORTCUT : 0;
+    LegPathsResult out;
+    ReachPathSet &p = out.paths;
+    p.offsets.assign((size_t)n + 1, 0);
+    p.status.assign((size_t)n + 1, 0), p.n_moves.assign((size_t)n + 1, -1), out.cost.assign((size_t)n + 1, -1);  // (one spare entry: never null)
+    out.info = fiesta_hip_leg_paths_info{};
+    fiesta_hip_leg_paths_result r{p.offsets.data(), nullptr, nullptr, p.status.data(), p.n_moves.data(), out.cost.data()};
+    ck(fiesta_hip_leg_paths(h_, pf, pt, pv, n, flags, max_span, 0, &r, &out.info));  // sizes the buffers
+    p.status.resize((size_t)n), p.n_moves.resize((size_t)n), out.cost.resize((size_t)n);
+    const int64_t total = p.offsets[(size_t)n];
+    p.vox.assign((size_t)total * 3, 0), p.pos.assign((size_t)total * 3, 0.0);
+    if (total > 0) {
+      r = fiesta_hip_leg_paths_result{p.offsets.data(), p.vox.data(), p.pos.data(), nullptr, nullptr, nullptr};
+      ck(fiesta_hip_leg_paths(h_, pf, pt, pv, n, flags, max_span, total, &r, nullptr));
+    }
+    return out;
+  }
+  // Tour route: ReachMatrix -> SiteTour -> LegPaths.  The order in which to visit `sites` from sites[start] and the way along every
+  // leg, the box flooded once per site and never again.  Leg k runs from order[k] to order[k + 1]; a closed tour gets the wrap-around
+  // leg order[m - 1] -> order[0] as its last.  All sites must fit one batch of floods (else std::runtime_error).
+  struct TourRouteResult {
+    std::vector<int32_t> matrix, source_status;  // ReachMatrix: n x n, row-major
+    SiteTourResult tour;
+    std::vector<int32_t> leg_from, leg_to;
+    LegPathsResult legs;
+  };
+  TourRouteResult TourRoute(const std::vector<Eigen::Vector3i> &sites, int32_t start = 0, bool closed = false, const Eigen::Vector3i *lo = nullptr,
+                            const Eigen::Vector3i *hi = nullptr, double min_clearance = 0.0, int32_t connectivity = 26, int32_t flags = 0,
+                            int32_t restarts = 64, uint64_t seed = 0, int32_t max_moves = 0, bool shortcut = false, int32_t max_span = 4096) {
+    TourRouteResult out;
+    const fiesta_hip_reach_matrix_info mi = ReachMatrix(lo, hi, sites, {}, min_clearance, connectivity, flags, &out.matrix, &out.source_status);
+    if (mi.batches != 1) throw std::runtime_error("TourRoute: the sites' floods do not fit one batch (or the box is empty)");
+    out.tour = SiteTour(out.matrix, (int32_t)sites.size(), start, closed, restarts, seed, max_moves);
+    const std::vector<int32_t> &order = out.tour.order;
+    const size_t m = order.size();
+    for (size_t k = 0; k + 1 < m; ++k) out.leg_from.push_back(order[k]), out.leg_to.push_back(order[k + 1]);
+    if (closed && m >= 2) out.leg_from.push_back(order[m - 1]), out.leg_to.push_back(order[0]);
+    out.legs = LegPaths(out.leg_from, out.leg_to, shortcut, max_span);
+    return out;
+  }
   // Free boxes (fiesta_hip_free_boxes, include/fiesta_hip.h): around every seed voxel the axis-aligned box of traversable voxels
   // (ReachField's traversability; flags: FIESTA_HIP_CORRIDOR_THROUGH_UNKNOWN) grown face by face, at most max_grow <= 256 steps per
   // face, inside the inclusive voxel window [lo, hi] (both null: a dense map's whole array, everything on a hash-block map).  box:

@@ -133,8 +133,8 @@ const char *fiesta_hip_last_error(void);
  * fiesta_hip_path_cost[_dev], fiesta_hip_get_frontier_voxels[_dev], fiesta_hip_ray_query[_dev], fiesta_hip_reach_field[_dev] and
  * fiesta_hip_reach_paths[_dev] came later without a new number, and so did fiesta_hip_cluster_voxels[_dev],
  * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_site_tour[_dev], fiesta_hip_free_boxes[_dev],
- * fiesta_hip_path_corridor[_dev], fiesta_hip_path_refine[_dev], fiesta_hip_corridor_bounds[_dev] and
- * fiesta_hip_split_clusters[_dev]: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_path_corridor[_dev], fiesta_hip_path_refine[_dev], fiesta_hip_corridor_bounds[_dev],
+ * fiesta_hip_split_clusters[_dev] and fiesta_hip_leg_paths[_dev]: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -614,6 +614,12 @@ int fiesta_hip_reach_field_dev(fiesta_hip_map *m, const int32_t lo[3], const int
  *   the map usable.  FIESTA_HIP_ERR_STATE: a batch ran more rounds than there are traversable voxels + 1 (a defect, never expected).
  * The field that fiesta_hip_reach_paths RETAINS is left alone: this call neither reads nor writes it, so a reach_field /
  *   reach_paths pair may be interleaved with it.
+ * The BATCH that fiesta_hip_leg_paths descends is RETAINED by this call, in the map's scratch memory: the cost planes of all floods,
+ *   the clipped box, the connectivity, the per-source status and a copy of the source voxels.  Every call that gets past the
+ *   whole-call argument errors above first drops what was retained; a batch is retained when the call then succeeds with
+ *   n_sources >= 1, a non-empty clipped box and ALL sources in one batch -- info->batches == 1 says so.  The retained batch is a
+ *   SNAPSHOT, as the retained field is: map updates do not invalidate it, and reach_field / reach_paths calls neither read nor
+ *   write it.  No output of this call depends on it.
  * fiesta_hip_reach_matrix      host arrays; stages, runs, synchronises, copies back.
  * fiesta_hip_reach_matrix_dev  sources / targets and the arrays the result struct names are device pointers; writes exactly
  *                              n_sources * n_cols costs and nothing beyond them.  Synchronises with the map's stream like
@@ -786,6 +792,62 @@ int fiesta_hip_reach_paths(fiesta_hip_map *m, const int32_t *cost, const int32_t
 int fiesta_hip_reach_paths_dev(fiesta_hip_map *m, const int32_t *cost_dev, const int32_t box_lo[3], const int32_t box_hi[3],
                                const int32_t *targets_dev, int64_t n_targets, int32_t connectivity, int32_t flags, int32_t max_span,
                                int64_t capacity, const fiesta_hip_reach_paths_result *result);
+
+/* ---- leg paths: the legs of a tour, extracted from the floods the reach matrix has just run ----
+ * Where the two halves of the planner chain meet: fiesta_hip_reach_matrix -> fiesta_hip_site_tour gives an ORDER of sites and integer
+ * leg costs, fiesta_hip_path_corridor -> fiesta_hip_corridor_bounds -> fiesta_hip_path_refine take PATHS.  This call gives the way
+ * along every leg without flooding anything again: it descends the cost planes that the map's last fiesta_hip_reach_matrix call
+ * RETAINED (see there: that call succeeded, n_sources >= 1, a non-empty box, info->batches == 1).  Read-only; no reference
+ * counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.  fiesta_amd.leg_paths_model is the
+ * definition.
+ * Legs: leg k runs from site from[k], an index into the retained batch's sources, to site to[k], or to map voxel
+ *   to_vox[3k .. 3k + 2]; exactly one of to and to_vox is non-NULL when n_legs > 0.  The legs of a tour need no array to be built:
+ *   with `order` and n_visited of fiesta_hip_site_tour, from = order, to = order + 1, n_legs = n_visited - 1 (a closed tour's last
+ *   leg, order[n_visited - 1] -> order[0], is one more leg of its own).  flags: 0 or FIESTA_HIP_REACH_PATHS_SHORTCUT; max_span as
+ *   in fiesta_hip_reach_paths.  There is no connectivity argument: the retained batch's is used.
+ * status[k], in this order of precedence: FIESTA_HIP_LEG_BAD_INDEX, from[k] or to[k] outside 0 .. n_sources - 1;
+ *   FIESTA_HIP_LEG_NO_SOURCE, source from[k] is not FIESTA_HIP_REACH_SITE_OK in the retained batch; else the FIESTA_HIP_REACH_PATH_*
+ *   status (0 .. 4) of fiesta_hip_reach_paths for the leg's target on the source's plane.
+ * Path: for status OK, bit for bit what fiesta_hip_reach_paths returns for that target on the explicit field of
+ *   fiesta_hip_reach_field with seeds = {source from[k]} and the matrix call's box, clearance, flags and connectivity, with the
+ *   same flags and max_span: stored SOURCE FIRST, TARGET LAST, so consecutive legs of a tour concatenate into the route (the last
+ *   waypoint of one leg is the first of the next).  from[k] == to[k] yields one waypoint and 0 moves; a leg that is not OK has no
+ *   waypoint and n_moves -1.
+ * cost[k]: the source's plane at the target voxel -- -1 outside the box or not traversable, INT32_MAX not reached -- and -1 for
+ *   NO_SOURCE and BAD_INDEX; with `to` therefore cost[from[k]][to[k]] of the matrix call's square form, bit for bit.
+ * offsets (REQUIRED, n_legs + 1, always the true totals), waypoints_vox, waypoints_pos and capacity behave exactly as in
+ *   fiesta_hip_reach_paths: entries below `capacity` are written, nothing beyond it is touched, capacity 0 sizes the buffers.
+ *   n_legs = 0 is no error: offsets[0] = 0.  info (a HOST struct in both variants, nullable): what is retained -- the clipped box,
+ *   the connectivity and the number of sources -- filled from the host-side record.
+ * Whole-call errors, FIESTA_HIP_ERR_INVALID, checked before the map handle is looked at: result or result->offsets NULL, a negative
+ *   n_legs or capacity, unknown flag bits, SHORTCUT with max_span < 1, from NULL with n_legs > 0, both or neither of to / to_vox
+ *   with n_legs > 0.  FIESTA_HIP_ERR_STATE: the map retains no batch; the message says why (no fiesta_hip_reach_matrix call yet, the
+ *   last one ran more than one batch -- lower the box or raise max_fields -- or it had nothing to keep).  Nothing is written then.
+ * fiesta_hip_leg_paths      host arrays; stages, runs, copies back min(total, capacity) waypoints, synchronises.
+ * fiesta_hip_leg_paths_dev  from / to / to_vox and the result's arrays are device pointers (from and to may be views into the order
+ *                           array where fiesta_hip_site_tour_dev left it); only enqueued on the map's stream (count, scan, write),
+ *                           like fiesta_hip_reach_paths_dev. */
+#define FIESTA_HIP_LEG_NO_SOURCE 5 /* the leg's source is not FIESTA_HIP_REACH_SITE_OK in the retained batch */
+#define FIESTA_HIP_LEG_BAD_INDEX 6 /* from, or to, outside 0 .. n_sources - 1 */
+typedef struct fiesta_hip_leg_paths_result {
+  int64_t *offsets;       /* n_legs + 1, CSR; REQUIRED: always the true totals */
+  int32_t *waypoints_vox; /* capacity x 3, map voxel coordinates; nullable */
+  double *waypoints_pos;  /* capacity x 3, metres (Vox2Pos); nullable */
+  int32_t *status;        /* per leg; nullable */
+  int32_t *n_moves;       /* per leg; nullable */
+  int32_t *cost;          /* per leg; nullable */
+} fiesta_hip_leg_paths_result;
+typedef struct fiesta_hip_leg_paths_info {
+  int32_t box_lo[3], box_hi[3]; /* the retained batch's clipped box, map voxel coordinates, inclusive */
+  int32_t connectivity;
+  int32_t reserved;
+  int64_t n_sources;
+} fiesta_hip_leg_paths_info;
+int fiesta_hip_leg_paths(fiesta_hip_map *m, const int32_t *from, const int32_t *to, const int32_t *to_vox, int64_t n_legs, int32_t flags,
+                         int32_t max_span, int64_t capacity, const fiesta_hip_leg_paths_result *result, fiesta_hip_leg_paths_info *info);
+int fiesta_hip_leg_paths_dev(fiesta_hip_map *m, const int32_t *from_dev, const int32_t *to_dev, const int32_t *to_vox_dev, int64_t n_legs,
+                             int32_t flags, int32_t max_span, int64_t capacity, const fiesta_hip_leg_paths_result *result,
+                             fiesta_hip_leg_paths_info *info);
 
 /* ---- free-space corridors: box inflation around voxels, and a corridor of overlapping boxes along voxel polylines ----
  * What a trajectory optimiser takes after the chain frontier voxels -> reachability -> reach paths: not a voxel staircase but a
