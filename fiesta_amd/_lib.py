@@ -159,6 +159,18 @@ class RefineResult(C.Structure):
                 ("n_below", C.c_void_p), ("min_dist", C.c_void_p), ("status", C.c_void_p)]
 
 
+class TimingParams(C.Structure):
+    """fiesta_hip_timing_params: the sample spacing, the margin and the robot's speed and acceleration limits of fiesta_hip_path_timing"""
+    _fields_ = [("step", C.c_double), ("margin", C.c_double), ("v_max", C.c_double), ("v_min", C.c_double), ("a_max", C.c_double),
+                ("corner_dev", C.c_double), ("v_start", C.c_double), ("v_end", C.c_double)]
+
+
+class TimingResult(C.Structure):
+    """fiesta_hip_path_timing_result: one array per output of fiesta_hip_path_timing, every pointer nullable"""
+    _fields_ = [("duration", C.c_void_p), ("length", C.c_void_p), ("n_samples", C.c_void_p), ("n_below", C.c_void_p),
+                ("min_speed", C.c_void_p), ("min_index", C.c_void_p), ("status", C.c_void_p), ("time", C.c_void_p), ("speed", C.c_void_p)]
+
+
 class BoundsResult(C.Structure):
     """fiesta_hip_bounds_result: one array per output of fiesta_hip_corridor_bounds, every pointer nullable"""
     _fields_ = [("bounds", C.c_void_p), ("ok", C.c_void_p), ("box", C.c_void_p)]
@@ -329,6 +341,8 @@ def load():
         "fiesta_hip_path_corridor_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, i64, vp]),
         "fiesta_hip_path_refine": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp]),
         "fiesta_hip_path_refine_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp]),
+        "fiesta_hip_path_timing": (C.c_int, [vp, vp, i64, vp, i64, vp, vp]),
+        "fiesta_hip_path_timing_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, vp]),
         "fiesta_hip_corridor_bounds": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, dbl, i32, vp]),
         "fiesta_hip_corridor_bounds_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, dbl, i32, vp]),
         "fiesta_hip_cluster_voxels": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i64, i64, vp, vp]),

@@ -20,6 +20,7 @@
 #include "reach_matrix_kernels.hpp"
 #include "reach_path_kernels.hpp"
 #include "refine_kernels.hpp"
+#include "timing_kernels.hpp"
 #include "shard_group.hpp"
 #include "split_kernels.hpp"
 #include "tour_kernels.hpp"
@@ -243,6 +244,28 @@ void path_refine(fiesta_hip_map *m, const fiesta::PathRefineArgs &a) {
   }
   need(m != nullptr, "null map handle");
   on_store(m, [&](auto &s) { s.path_refine(a); });
+}
+// fiesta_hip_path_timing: none of these errors needs a device, and all are checked before the handle is touched (a host batch: the
+// CSR rules as well)
+void path_timing(fiesta_hip_map *m, const fiesta::PathTimingArgs &a) {
+  need(a.w && a.off && a.par && a.res, "path_timing: waypoints, offsets, params or result is null");
+  need(a.n_wp >= 0 && a.n_paths >= 0, "path_timing: negative count");
+  need(a.n_paths <= (1ll << 30), "path_timing: more than 2^30 paths");
+  const fiesta_hip_timing_params &p = *a.par;
+  need(std::isfinite(p.step) && p.step > 0, "path_timing: step must be finite and > 0");
+  need(std::isfinite(p.margin) && p.margin >= 0, "path_timing: margin must be finite and >= 0");
+  need(std::isfinite(p.v_max) && p.v_max > 0, "path_timing: v_max must be finite and > 0");
+  need(std::isfinite(p.v_min) && p.v_min > 0 && p.v_min <= p.v_max, "path_timing: v_min must be finite, 0 < v_min <= v_max");
+  need(std::isfinite(p.a_max) && p.a_max > 0, "path_timing: a_max must be finite and > 0");
+  need(p.corner_dev > 0, "path_timing: corner_dev must be > 0 (+inf: no corner rule)");  // (a NaN fails the comparison)
+  need(std::isfinite(p.v_start) && p.v_start >= 0, "path_timing: v_start must be finite and >= 0");
+  need(std::isfinite(p.v_end) && p.v_end >= 0, "path_timing: v_end must be finite and >= 0");
+  if (!a.dev) {
+    need(a.off[0] == 0 && a.off[a.n_paths] == a.n_wp, "path_timing: offsets[0] must be 0 and offsets[n_paths] = n_waypoints");
+    for (int64_t i = 0; i < a.n_paths; ++i) need(a.off[i] <= a.off[i + 1], "path_timing: offsets must be non-decreasing");
+  }
+  need(m != nullptr, "null map handle");
+  on_store(m, [&](auto &s) { s.path_timing(a); });
 }
 // fiesta_hip_corridor_bounds: none of these errors needs a device, and all are checked before the handle is touched (a host batch:
 // the CSR rules of both offset arrays as well)
@@ -630,6 +653,14 @@ int fiesta_hip_path_refine(fiesta_hip_map *m, const double *w, int64_t n_wp, con
 int fiesta_hip_path_refine_dev(fiesta_hip_map *m, const double *w_dev, int64_t n_wp, const int64_t *off_dev, int64_t n_paths,
                                const double *bounds_dev, const fiesta_hip_refine_params *par, const fiesta_hip_refine_result *r) {
   return guarded([&] { path_refine(m, {w_dev, n_wp, off_dev, n_paths, bounds_dev, par, r, true}); });
+}
+int fiesta_hip_path_timing(fiesta_hip_map *m, const double *w, int64_t n_wp, const int64_t *off, int64_t n_paths,
+                           const fiesta_hip_timing_params *par, const fiesta_hip_path_timing_result *r) {
+  return guarded([&] { path_timing(m, {w, n_wp, off, n_paths, par, r, false}); });
+}
+int fiesta_hip_path_timing_dev(fiesta_hip_map *m, const double *w_dev, int64_t n_wp, const int64_t *off_dev, int64_t n_paths,
+                               const fiesta_hip_timing_params *par, const fiesta_hip_path_timing_result *r) {
+  return guarded([&] { path_timing(m, {w_dev, n_wp, off_dev, n_paths, par, r, true}); });
 }
 int fiesta_hip_corridor_bounds(fiesta_hip_map *m, const int32_t *w, int64_t n_wp, const int64_t *off, int64_t n_paths, const int64_t *box_off,
                                const int32_t *boxes, const double *boxes_pos, const int32_t *entry, const int32_t *status, int64_t n_boxes,

@@ -41,6 +41,7 @@
 #include "level_kernels.hpp"
 #include "path_cost_kernels.hpp"
 #include "refine_kernels.hpp"
+#include "timing_kernels.hpp"
 #include "bounds_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
@@ -2438,6 +2439,11 @@ void DenseMap::path_refine(const PathRefineArgs &a) {
   if (a.n_paths <= 0) return;
   use_device();
   path_refine_run(stream_, planner_, path_eval(), a);
+}
+void DenseMap::path_timing(const PathTimingArgs &a) {
+  if (a.n_paths <= 0) return;
+  use_device();
+  path_timing_run(stream_, planner_, path_eval(), a);
 }
 void DenseMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n <= 0) return;

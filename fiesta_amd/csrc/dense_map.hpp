@@ -173,6 +173,7 @@ struct ReachPathArgs;
 struct LegPathArgs;
 struct CorridorArgs;
 struct PathRefineArgs;
+struct PathTimingArgs;
 struct CorridorBoundsArgs;
 struct TourArgs;
 struct ClusterArgs;
@@ -276,6 +277,7 @@ class DenseMap {
   void path_clearance(const PathArgs<fiesta_hip_path_result> &a);
   void path_cost(const PathArgs<fiesta_hip_path_cost_result> &a);
   void path_refine(const PathRefineArgs &a);
+  void path_timing(const PathTimingArgs &a);
   int64_t host_brick_fetches() const;  // bricks fetched for scalar queries so far (tests, bench)
 
   void download_field(int32_t *d2, int32_t *coc, uint8_t *occ, double *logodds);

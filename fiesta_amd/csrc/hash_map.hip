@@ -20,6 +20,7 @@
 #include "level_kernels.hpp"
 #include "path_cost_kernels.hpp"
 #include "refine_kernels.hpp"
+#include "timing_kernels.hpp"
 #include "bounds_kernels.hpp"
 #include "frontier_kernels.hpp"
 #include "ray_query_kernels.hpp"
@@ -1499,6 +1500,11 @@ void HashMap::path_refine(const PathRefineArgs &a) {
   if (a.n_paths <= 0) return;
   use_device();
   path_refine_run(stream_, planner_, path_eval(page_table()), a);
+}
+void HashMap::path_timing(const PathTimingArgs &a) {
+  if (a.n_paths <= 0) return;
+  use_device();
+  path_timing_run(stream_, planner_, path_eval(page_table()), a);
 }
 void HashMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n > 0 && n <= kHostQueries) {

@@ -82,6 +82,7 @@ class HashMap {
   void path_clearance(const PathArgs<fiesta_hip_path_result> &a);
   void path_cost(const PathArgs<fiesta_hip_path_cost_result> &a);
   void path_refine(const PathRefineArgs &a);
+  void path_timing(const PathTimingArgs &a);
   int64_t frontier_voxels(const FrontierArgs &a);
   void ray_query(const RayArgs &a);
   void reach_field(const ReachArgs &a);

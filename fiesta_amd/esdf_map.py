@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, LegPathsInfo, LegPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, BoundsResult, Stats, TourInfo, TourResult, check
+from ._lib import ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, LegPathsInfo, LegPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, TimingParams, TimingResult, BoundsResult, Stats, TourInfo, TourResult, check
 from .refine_model import BOUNDS_VOID_BROKEN
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
@@ -105,6 +105,12 @@ PATH_COST_FIELDS = (("cost", np.float64, "path", ()), ("grad", np.float64, "wayp
 REFINE_FIELDS = (("waypoints", np.float64, "waypoint", (3,)), ("cost", np.float64, "path", (2,)), ("last_move", np.float64, "path", ()),
                  ("iterations", np.int32, "path", ()), ("n_below", np.int64, "path", ()), ("min_dist", np.float64, "path", ()),
                  ("status", np.int32, "path", ()))
+
+# fiesta_hip_path_timing_result, in struct order: (name, dtype, one row per "path" or per "waypoint", row shape)
+TIMING_FIELDS = (("duration", np.float64, "path", ()), ("length", np.float64, "path", ()), ("n_samples", np.int64, "path", ()),
+                 ("n_below", np.int64, "path", ()), ("min_speed", np.float64, "path", ()), ("min_index", np.int64, "path", ()),
+                 ("status", np.int32, "path", ()), ("time", np.float64, "waypoint", ()), ("speed", np.float64, "waypoint", ()))
+TIMING_PARAMS = ("step", "margin", "v_max", "v_min", "a_max", "corner_dev", "v_start", "v_end")   # fiesta_hip_timing_params, in struct order
 
 
 def path_cost_model(query, waypoints, offsets, step, margin):
@@ -657,6 +663,33 @@ class ESDFMap:
         res = RefineResult(*[int(out.get(name, 0)) or None for name, _, _, _ in REFINE_FIELDS])
         check(self._lib.fiesta_hip_path_refine_dev(self._h, C.c_void_p(waypoints_dev_ptr), int(n_waypoints), C.c_void_p(offsets_dev_ptr),
                                                    int(n_paths), C.c_void_p(bounds_dev_ptr or None), C.byref(par), C.byref(res)))
+
+    def PathTiming(self, waypoints, offsets, *, step, margin, v_max, v_min, a_max, corner_dev, v_start=0.0, v_end=0.0) -> dict:
+        """fiesta_hip_path_timing: per path (CSR `offsets` over `waypoints`) the travel time of the fastest speed profile that
+        stays below the clearance limit 2 a_max (d - margin) of every sample (path_samples; v_min below the margin), the
+        junction-deviation limit at every bend (corner_dev metres; inf: none), v_start / v_end at the ends and the acceleration
+        bound a_max.  Returns a dict of numpy arrays named as the fields of fiesta_hip_path_timing_result (time, speed: one row per
+        waypoint); fiesta_amd.path_timing_model is the definition"""
+        w = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if len(off) < 1:
+            raise ValueError("offsets needs n_paths + 1 entries")
+        n = len(off) - 1
+        out = {name: np.empty((n if per == "path" else len(w),) + shape, dtype) for name, dtype, per, shape in TIMING_FIELDS}
+        par = TimingParams(float(step), float(margin), float(v_max), float(v_min), float(a_max), float(corner_dev), float(v_start), float(v_end))
+        res = TimingResult(*[out[name].ctypes.data for name, _, _, _ in TIMING_FIELDS])
+        check(self._lib.fiesta_hip_path_timing(self._h, _p(w), len(w), _p(off), n, C.byref(par), C.byref(res)))
+        return out
+
+    def PathTimingDevice(self, waypoints_dev_ptr: int, n_waypoints: int, offsets_dev_ptr: int, n_paths: int, *, step, margin, v_max, v_min,
+                         a_max, corner_dev, v_start=0.0, v_end=0.0, out=None):
+        """fiesta_hip_path_timing_dev: inputs and outputs resident on the device (`out` maps field names of
+        fiesta_hip_path_timing_result to device pointers, missing fields are not written); only enqueued on the map's stream"""
+        out = out or {}
+        par = TimingParams(float(step), float(margin), float(v_max), float(v_min), float(a_max), float(corner_dev), float(v_start), float(v_end))
+        res = TimingResult(*[int(out.get(name, 0)) or None for name, _, _, _ in TIMING_FIELDS])
+        check(self._lib.fiesta_hip_path_timing_dev(self._h, C.c_void_p(waypoints_dev_ptr), int(n_waypoints), C.c_void_p(offsets_dev_ptr),
+                                                   int(n_paths), C.byref(par), C.byref(res)))
 
     @property
     def host_cache_fetches(self) -> int:

@@ -615,6 +615,54 @@ class ESDFMap {
     out.min_dist.resize(n), out.status.resize(n);
     return out;
   }
+  // Path timing (fiesta_hip_path_timing, include/fiesta_hip.h): how long every path of the CSR batch (waypoints: 3 doubles each,
+  // metres, e.g. ReachPathSet::pos and ::offsets, or RefineSet::pos) takes.  Per sample (spacing p.step, the sample rule of
+  // PathSample) the speed is limited to the one from which the robot still stops within its free distance d - p.margin (never below
+  // p.v_min, never above p.v_max), at every bend by the junction deviation p.corner_dev (metres; infinity: no corner rule), at the
+  // ends by p.v_start / p.v_end, and it changes no faster than p.a_max allows.  The whole computation runs on the device.
+  struct TimingParams {
+    double step = 0.1, margin = 0.3, v_max = 2.0, v_min = 0.1, a_max = 2.0, corner_dev = 0.05, v_start = 0.0, v_end = 0.0;
+  };
+  struct TimingSet {
+    std::vector<double> duration;    // per path from here on: the travel time, seconds
+    std::vector<double> length;      // metres
+    std::vector<int64_t> n_samples;
+    std::vector<int64_t> n_below;    // samples with d < margin (they run at v_min)
+    std::vector<double> min_speed;
+    std::vector<int64_t> min_index;  // the first sample that runs at min_speed
+    std::vector<int32_t> status;     // FIESTA_HIP_TIMING_*
+    std::vector<double> time;        // per waypoint: its time stamp
+    std::vector<double> speed;       // per waypoint: the speed there
+  };
+  TimingSet PathTiming(const std::vector<double> &waypoints, const std::vector<int64_t> &offsets, const TimingParams &p) {
+    Flush();
+    if (offsets.empty() || waypoints.size() % 3 != 0) throw std::invalid_argument("PathTiming: offsets needs n_paths + 1 entries, waypoints 3 doubles each");
+    const size_t n = offsets.size() - 1, nw = waypoints.size() / 3;
+    TimingSet out;
+    out.duration.assign(n + 1, 0.0), out.length.assign(n + 1, 0.0), out.n_samples.assign(n + 1, 0), out.n_below.assign(n + 1, 0);
+    out.min_speed.assign(n + 1, 0.0), out.min_index.assign(n + 1, 0), out.status.assign(n + 1, 0);
+    out.time.assign(nw + 1, 0.0), out.speed.assign(nw + 1, 0.0);
+    const fiesta_hip_timing_params par{p.step, p.margin, p.v_max, p.v_min, p.a_max, p.corner_dev, p.v_start, p.v_end};
+    const fiesta_hip_path_timing_result r{out.duration.data(),  out.length.data(), out.n_samples.data(), out.n_below.data(), out.min_speed.data(),
+                                          out.min_index.data(), out.status.data(), out.time.data(),      out.speed.data()};
+    const std::vector<double> none(1, 0.0);  // (the call wants a waypoint pointer even for no waypoints)
+    ck(fiesta_hip_path_timing(h_, waypoints.empty() ? none.data() : waypoints.data(), (int64_t)nw, offsets.data(), (int64_t)n, &par, &r));
+    out.duration.resize(n), out.length.resize(n), out.n_samples.resize(n), out.n_below.resize(n), out.min_speed.resize(n);
+    out.min_index.resize(n), out.status.resize(n), out.time.resize(nw), out.speed.resize(nw);
+    return out;
+  }
+  // One polyline: its travel time (0 for fewer than two waypoints, NaN for a path the call does not time: a non-finite waypoint, a
+  // segment longer than 2^24 steps, more than 1024 waypoints or 4096 samples), optionally every waypoint's time stamp and speed.
+  double GetPathDuration(const std::vector<Eigen::Vector3d> &waypoints, const TimingParams &p, std::vector<double> *time = nullptr,
+                         std::vector<double> *speed = nullptr) {
+    std::vector<double> w(3 * waypoints.size());
+    for (size_t i = 0; i < waypoints.size(); ++i)
+      for (int c = 0; c < 3; ++c) w[3 * i + c] = waypoints[i](c);
+    const TimingSet t = PathTiming(w, {0, (int64_t)waypoints.size()}, p);
+    if (time) *time = t.time;
+    if (speed) *speed = t.speed;
+    return t.duration[0];
+  }
   // Voxel clusters (fiesta_hip_cluster_voxels, include/fiesta_hip.h): the connected groups (connectivity 6, 18 or 26) of a voxel list
   // -- typically GetFrontierVoxels' -- with those below min_size distinct voxels dropped and the rest numbered by their lowest entry
   // index.  mask (nullable): the frontier call's unknown-neighbour bits; key (nullable): one int32 per entry, e.g. ReachField's

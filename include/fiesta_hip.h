@@ -134,7 +134,8 @@ const char *fiesta_hip_last_error(void);
  * fiesta_hip_reach_paths[_dev] came later without a new number, and so did fiesta_hip_cluster_voxels[_dev],
  * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_site_tour[_dev], fiesta_hip_free_boxes[_dev],
  * fiesta_hip_path_corridor[_dev], fiesta_hip_path_refine[_dev], fiesta_hip_corridor_bounds[_dev],
- * fiesta_hip_split_clusters[_dev] and fiesta_hip_leg_paths[_dev]: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_split_clusters[_dev], fiesta_hip_leg_paths[_dev] and fiesta_hip_path_timing[_dev]: detect them by symbol lookup
+ * (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -1126,6 +1127,92 @@ int fiesta_hip_corridor_bounds_dev(fiesta_hip_map *m, const int32_t *waypoints_v
                                    int64_t n_paths, const int64_t *box_offsets_dev, const int32_t *boxes_dev, const double *boxes_pos_dev,
                                    const int32_t *entry_dev, const int32_t *status_dev, int64_t n_boxes, double inset, int32_t flags,
                                    const fiesta_hip_bounds_result *result);
+
+/* ---- path timing: clearance-limited speed profiles and travel times of a CSR batch of polylines, on the device ----
+ * Every other cost of the planner chain is a length; this call says how long a path TAKES.  The robot brakes where the distance
+ * field says obstacles are near, slows at bends, starts and ends at given speeds (rest by default) and changes speed no faster
+ * than its acceleration limit allows.  Per path the call returns the travel time and the slowest sample, per waypoint a time stamp
+ * and a speed.  The paths are independent: one launch runs every path's whole computation.  Read-only on the map; no reference
+ * counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.  fiesta_amd.path_timing_model (numpy) is
+ * the definition.
+ * Input: waypoints and offsets are path clearance's CSR polylines; params: every field f64 --
+ *   step finite, > 0; margin finite, >= 0; v_max finite, > 0; v_min finite, 0 < v_min <= v_max; a_max finite, > 0; corner_dev in
+ *   metres, > 0, +inf switches the corner rule off; v_start and v_end finite, >= 0.
+ * Samples: path clearance's, by the same rule and with the same indices: per segment j of a path of m waypoints d[c] = b[c] - a[c],
+ *   L_j, S_j, Sd_j = (double)S_j; n = sum S + 1 samples, sample 0 of segment i is waypoint i, the final sample is the last waypoint.
+ *   A sample's value d is fiesta_hip_get_dist_grad's at its position, bit for bit (dense maps, a single shard, hash-block maps; -1
+ *   outside a dense map, +10000 at unobserved corners).
+ * The rule, in f64, every operation rounded once (the library is built with -ffp-contract=off), every min and clamp a comparison
+ *   `if (x < y) y = x`.  A = 2.0 * a_max, Vq = v_max * v_max, Mq = v_min * v_min.
+ *   Arc length: W_0 = 0, W_{j+1} = W_j + L_j in segment order; length = W_{m-1} (path cost's length bits).  Sample k of segment j
+ *     lies at s = W_j + L_j * ((double)k / Sd_j), the final sample at W_{m-1}; s is non-decreasing (rounding is monotone).
+ *   Clearance limit: if d < margin: lq = Mq and the sample counts in n_below; else e = d - margin; lq = A * e;
+ *     if (lq > Vq) lq = Vq; if (lq < Mq) lq = Mq.
+ *   Corner limit (junction deviation), at the sample of interior waypoint i (1 <= i <= m-2), only if corner_dev is finite and
+ *     L_{i-1} > 0 and L_i > 0:  u[c] = d_{i-1}[c] / L_{i-1};  w[c] = d_i[c] / L_i;  c = (u0*w0 + u1*w1) + u2*w2;
+ *     if (c > 1.0) c = 1.0; if (c < -1.0) c = -1.0;  sh = sqrt(0.5 * (1.0 + c));  den = 1.0 - sh;
+ *     if (den > 0): cq = ((a_max * corner_dev) * sh) / den;  if (cq < lq) lq = cq.   A straight joint limits nothing, a reversal
+ *     gives 0, a zero-length segment limits nothing.
+ *   Ends: sample 0: vs = v_start * v_start; if (vs < lq) lq = vs.  Sample n-1 the same with v_end.  A path of one sample takes both.
+ *   Profile: P_k = A * s_k;  f_k = min_{j <= k} (lq_j - P_j) + P_k;  b_k = min_{j >= k} (lq_j + P_j) - P_k;
+ *     q_k = lq_k; if (f_k < q_k) q_k = f_k; if (b_k < q_k) q_k = b_k;  v_k = sqrt(q_k).  min is exact and associative: any scan
+ *     shape gives the same bits; q_k >= 0 because P is non-decreasing.
+ *   Interval k, between samples k and k+1 in segment j: h = L_j / Sd_j; if (h == 0) dt = 0; else sv = v_k + v_{k+1};
+ *     if (sv > 0) dt = (2.0 * h) / sv (exact for constant acceleration); else dt = 2.0 * sqrt(h / a_max) (the rest-to-rest triangle).
+ * Outputs; every pointer of the result is nullable:
+ *   per path: duration (the sum of dt), length, n_samples, n_below, min_speed (the minimum v_k), min_index (the smallest sample
+ *     index that attains it), status:
+ *       FIESTA_HIP_TIMING_OK
+ *       FIESTA_HIP_TIMING_INVALID   a non-finite waypoint, a segment with L / step > 2^24; in the _dev variant only, offsets that
+ *                                   break path clearance's offset rules
+ *       FIESTA_HIP_TIMING_TOO_LONG  more than FIESTA_HIP_TIMING_MAX_WAYPOINTS waypoints or more than FIESTA_HIP_TIMING_MAX_SAMPLES
+ *                                   samples
+ *     checked in this order: the offset rules, the waypoint count (such a path's waypoints are not read), the waypoints and
+ *     segments, the sample count.
+ *   per waypoint (n_waypoints rows, every row written by every call): time (the sum of the dt before the waypoint's sample) and
+ *     speed (v at the waypoint's sample).
+ *   An empty path: duration 0, length 0, n_samples 0, n_below 0, min_speed +inf, min_index -1, status OK.  One waypoint: one
+ *   sample, duration 0.  An INVALID or TOO_LONG path: duration, length and min_speed NaN, n_samples -1, n_below -1, min_index -1,
+ *   its time and speed rows NaN; rows that belong to no path are NaN too; the other paths are unaffected.
+ *   Everything but duration and time has the model's bits for any launch shape, and so has every single dt.  duration and time
+ *   are sums whose order is free (fixed by the path's sample count alone): with n terms of absolute sum a they stay within
+ *   (n + 16) * 2^-52 * a of the model.  No floating-point atomics: the same call on the same map gives the same bits.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable; each is checked before the map handle is
+ *   looked at): a parameter outside its rule, a NULL waypoints, offsets, params or result, negative counts, more than 2^30 paths,
+ *   and in the host variant offsets that break the CSR rules.  n_paths = 0 does nothing.
+ * fiesta_hip_path_timing      host pointers; stages, runs, synchronises (no host route for small batches: always the device).
+ * fiesta_hip_path_timing_dev  waypoints, offsets and the result's arrays are device pointers (the two structs themselves are host
+ *                             objects); only enqueued on the map's stream, nothing is read back.  There is no shard-group call. */
+#define FIESTA_HIP_TIMING_MAX_WAYPOINTS 1024 /* per path */
+#define FIESTA_HIP_TIMING_MAX_SAMPLES 4096   /* per path */
+#define FIESTA_HIP_TIMING_OK 0
+#define FIESTA_HIP_TIMING_INVALID 1
+#define FIESTA_HIP_TIMING_TOO_LONG 2
+typedef struct fiesta_hip_timing_params {
+  double step;       /* sample spacing, metres */
+  double margin;     /* clearance the robot keeps: the free distance is d - margin */
+  double v_max;
+  double v_min;      /* the crawl below the margin and the floor of the clearance limit */
+  double a_max;
+  double corner_dev; /* junction deviation, metres; +inf: no corner rule */
+  double v_start;
+  double v_end;
+} fiesta_hip_timing_params;
+typedef struct fiesta_hip_path_timing_result { /* every pointer nullable */
+  double *duration;    /* n_paths */
+  double *length;      /* n_paths */
+  int64_t *n_samples;  /* n_paths */
+  int64_t *n_below;    /* n_paths */
+  double *min_speed;   /* n_paths */
+  int64_t *min_index;  /* n_paths */
+  int32_t *status;     /* n_paths: FIESTA_HIP_TIMING_* */
+  double *time;        /* n_waypoints */
+  double *speed;       /* n_waypoints */
+} fiesta_hip_path_timing_result;
+int fiesta_hip_path_timing(fiesta_hip_map *m, const double *waypoints, int64_t n_waypoints, const int64_t *offsets, int64_t n_paths,
+                           const fiesta_hip_timing_params *params, const fiesta_hip_path_timing_result *result);
+int fiesta_hip_path_timing_dev(fiesta_hip_map *m, const double *waypoints_dev, int64_t n_waypoints, const int64_t *offsets_dev,
+                               int64_t n_paths, const fiesta_hip_timing_params *params, const fiesta_hip_path_timing_result *result);
 
 /* ---- voxel clusters: the connected groups of a voxel list, with per-cluster statistics, on the device ----
  * The step between fiesta_hip_get_frontier_voxels and fiesta_hip_reach_field: a planner does not visit frontier voxels, it visits
