@@ -2,7 +2,7 @@
 //
 // The link between fiesta_hip_path_corridor and fiesta_hip_path_refine: per waypoint of a voxel polyline the box it may move in --
 // its corridor box, intersected with the next one where the path changes boxes -- and per path whether the corridor is whole.  It
-// reads no voxel: a pure function of the path batch and the corridor arrays, so both stores forward to corridor_bounds_run.
+// reads no voxel: a pure function of the path batch and the corridor arrays, so corridor_bounds_run serves both stores (planner.hip).
 //   k_path_check       path_kernels.hpp, unchanged (device variant only): waypoint offsets against the CSR rules
 //   k_bounds_fill      bounds = NaN, box = -1 over all n_waypoints rows: rows that no valid path owns are deterministic
 //   k_corridor_bounds  one wave per path (four paths per work-group, the 2-D grid of k_refine), lanes on consecutive waypoints in
@@ -20,25 +20,7 @@
 #include "path_kernels.hpp"
 
 namespace fiesta {
-// the arguments as fiesta_hip_corridor_bounds[_dev] take them, already checked
-struct CorridorBoundsArgs {
-  const int32_t *w;
-  int64_t n_wp;
-  const int64_t *off;
-  int64_t n_paths;
-  const int64_t *box_off;
-  const int32_t *boxes;
-  const double *boxes_pos;
-  const int32_t *entry;
-  const int32_t *status;
-  int64_t n_boxes;
-  double inset;
-  int32_t flags;
-  const fiesta_hip_bounds_result *res;
-  bool dev;
-};
-
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int64_t kBoundsGridX = 1 << 15;  // work-groups per grid row
 constexpr int kBoundsWaves = 4;            // paths per work-group

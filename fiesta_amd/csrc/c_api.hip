@@ -7,24 +7,11 @@
 #include <string>
 
 #include "../../include/fiesta_hip.h"
-#include "bounds_kernels.hpp"  // (the fourteen planner headers: for the calls' argument aggregates; no kernel is used here)
-#include "cluster_kernels.hpp"
-#include "corridor_kernels.hpp"
 #include "dense_map.hpp"
-#include "frontier_kernels.hpp"
 #include "hash_map.hpp"
-#include "leg_path_kernels.hpp"
-#include "path_cost_kernels.hpp"
-#include "ray_query_kernels.hpp"
-#include "reach_kernels.hpp"
-#include "reach_matrix_kernels.hpp"
-#include "reach_path_kernels.hpp"
-#include "refine_kernels.hpp"
-#include "timing_kernels.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "shard_group.hpp"
-#include "split_kernels.hpp"
-#include "tour_kernels.hpp"
-#include "view_kernels.hpp"
 
 using fiesta::DenseMap;
 using fiesta::Error;
@@ -73,7 +60,8 @@ DenseMap &dense(fiesta_hip_map *m, const char *what) {
   return *m->dense;
 }
 // The planner calls: one body per host / _dev pair.  Each checks the whole-call errors of include/fiesta_hip.h on the arguments as
-// the ABI took them (the aggregate of the call's kernel header), then hands the same object to the map's store.
+// the ABI took them (the call's aggregate of planner_args.hpp), then hands the same object on: to the map's store, or -- the six
+// calls that read no voxel -- to the call's function of planner.hpp with the store's planner_ctx().
 
 // shared by path_clearance and path_cost (R: the call's result struct); a host batch: the CSR rules as well
 template <typename R>
@@ -155,7 +143,7 @@ void site_tour(fiesta_hip_map *m, const fiesta::TourArgs &a) {
   need((a.flags & ~FIESTA_HIP_TOUR_CLOSED) == 0, "site_tour: unknown flag bits");
   need(a.max_moves >= 0, "site_tour: max_moves is negative");
   need(m != nullptr, "null map handle");
-  on_store(m, [&](auto &s) { s.site_tour(a); });
+  fiesta::site_tour(on_store(m, [](auto &s) { return s.planner_ctx(); }), a);
 }
 // none of these errors needs a device, and all but the last are checked before the handle is touched
 void reach_paths(fiesta_hip_map *m, const fiesta::ReachPathArgs &a) {
@@ -178,7 +166,7 @@ void reach_paths(fiesta_hip_map *m, const fiesta::ReachPathArgs &a) {
     }
   }
   need(m != nullptr, "null map handle");
-  on_store(m, [&](auto &s) { s.reach_paths(a); });
+  fiesta::reach_paths(on_store(m, [](auto &s) { return s.planner_ctx(); }), a);
 }
 // none of these errors needs a device, and all are checked before the handle is touched; whether a batch is retained is the map's to say
 void leg_paths(fiesta_hip_map *m, const fiesta::LegPathArgs &a) {
@@ -191,7 +179,7 @@ void leg_paths(fiesta_hip_map *m, const fiesta::LegPathArgs &a) {
   need(a.from != nullptr || a.n_legs == 0, "leg_paths: from is null");
   need((a.to != nullptr) != (a.to_vox != nullptr) || a.n_legs == 0, "leg_paths: exactly one of to and to_vox must be given");
   need(m != nullptr, "null map handle");
-  on_store(m, [&](auto &s) { s.leg_paths(a); });
+  fiesta::leg_paths(on_store(m, [](auto &s) { return s.planner_ctx(); }), a);
 }
 // fiesta_hip_free_boxes and fiesta_hip_path_corridor: none of these errors needs a device, and all are checked before the handle
 // is touched (a host batch: the CSR rules as well)
@@ -287,7 +275,7 @@ void corridor_bounds(fiesta_hip_map *m, const fiesta::CorridorBoundsArgs &a) {
     }
   }
   need(m != nullptr, "null map handle");
-  on_store(m, [&](auto &s) { s.corridor_bounds(a); });
+  fiesta::corridor_bounds(on_store(m, [](auto &s) { return s.planner_ctx(); }), a);
 }
 // none of these errors needs a device
 void cluster_voxels(fiesta_hip_map *m, const fiesta::ClusterArgs &a) {
@@ -298,7 +286,7 @@ void cluster_voxels(fiesta_hip_map *m, const fiesta::ClusterArgs &a) {
   need(a.cluster_capacity >= 0 && a.member_capacity >= 0, "cluster_voxels: negative capacity");
   need(a.vox != nullptr || a.n == 0, "cluster_voxels: vox is null");
   need(m != nullptr, "null map handle");
-  on_store(m, [&](auto &s) { s.cluster_voxels(a); });
+  fiesta::cluster_voxels(on_store(m, [](auto &s) { return s.planner_ctx(); }), a);
 }
 // fiesta_hip_split_clusters: none of these errors needs a device, and all are checked before the handle is touched (a host batch: the
 // data errors as well -- the _dev variant finds those on the device and reports them in info.status)
@@ -330,7 +318,7 @@ void split_clusters(fiesta_hip_map *m, const fiesta::SplitArgs &a) {
     }
   }
   need(m != nullptr, "null map handle");
-  on_store(m, [&](auto &s) { s.split_clusters(a); });
+  fiesta::split_clusters(on_store(m, [](auto &s) { return s.planner_ctx(); }), a);
 }
 // none of these errors needs a device
 void view_coverage(fiesta_hip_map *m, const fiesta::ViewArgs &a) {

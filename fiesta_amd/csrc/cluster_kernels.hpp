@@ -25,24 +25,12 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "wave_ops.hpp"
 
 namespace fiesta {
-struct ClusterArgs {  // the call's arguments as fiesta_hip_cluster_voxels[_dev] takes them, already checked
-  const int32_t *vox;
-  const uint8_t *mask;
-  const int32_t *key;
-  int64_t n;
-  const unsigned long long *n_dev;
-  int connectivity, min_size;
-  int64_t cluster_capacity, member_capacity;
-  const fiesta_hip_cluster_result *res;
-  fiesta_hip_cluster_info *info;
-  bool dev;
-};
-
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int64_t kClusterMaxEntries = 1ll << 24;
 constexpr int kClusterCoordLimit = (1 << 20) - 1;  // |c| >= this: INVALID (c and c +- 1, biased by 2^20, fit 21 bits)

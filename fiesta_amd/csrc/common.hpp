@@ -198,4 +198,43 @@ inline void require_gfx950(int device) {
     throw Error(2, std::string("device is ") + p.gcnArchName + ", this engine is built for gfx950 (MI355X) only");
 }
 
+// ---- a growing device array (the stores' queues and pools, the planner calls' scratch: planner.hpp) ----
+template <typename T>
+struct DevBuf {
+  T *p = nullptr;
+  size_t cap = 0;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  // Exactly n elements if there are fewer now, contents dropped (large scratch: no doubling).
+  void ensure_exact(size_t n, hipStream_t s) {
+    if (n <= cap) return;
+    if (p) {
+      FIESTA_HIP_CHECK(hipStreamSynchronize(s));
+      (void)hipFree(p);
+      p = nullptr, cap = 0;
+    }
+    FIESTA_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
+    cap = n;
+  }
+  // Grow to at least n elements; optionally preserve the first `keep` elements.
+  void ensure(size_t n, hipStream_t s, size_t keep = 0) {
+    if (n <= cap) return;
+    size_t ncap = cap ? cap : 1024;
+    while (ncap < n) ncap *= 2;
+    T *q = nullptr;
+    FIESTA_HIP_CHECK(hipMalloc((void **)&q, ncap * sizeof(T)));
+    if (p && keep) FIESTA_HIP_CHECK(hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, s));
+    if (p) {
+      FIESTA_HIP_CHECK(hipStreamSynchronize(s));
+      (void)hipFree(p);
+    }
+    p = q;
+    cap = ncap;
+  }
+};
+
 }  // namespace fiesta

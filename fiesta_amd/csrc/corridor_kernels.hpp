@@ -12,7 +12,7 @@
 //   k_free_boxes<SRC>        a wave per seed, grid-stride
 //   k_corridor_count<SRC>    a wave per path: checks the path, walks the voxel chain of every segment (candidate A, then B), runs the
 //                            greedy and writes the per-path outputs and the number of boxes into offsets[p + 1]
-//   k_reach_path_scan        (reach_path_kernels.hpp) offsets -> running totals
+//   k_reach_path_scan        (reach_path_kernels.hpp, through planner.hpp: reach_path_scan) offsets -> running totals
 //   k_corridor_write<SRC>    the greedy again, storing box k of path p at offsets[p] + k if that index lies below the capacity
 // A segment's chain: the reference traversal (ray_walk.hpp: dda_walk, f64) is computed redundantly by every lane; lane k & 63 keeps
 // voxel k, and every 64 voxels the lanes test theirs and a ballot finds the first that is not traversable.  The axis of every
@@ -30,28 +30,13 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "frontier_kernels.hpp"
 #include "ray_walk.hpp"
 #include "reach_kernels.hpp"
-#include "reach_path_kernels.hpp"
 
 namespace fiesta {
-struct CorridorArgs {  // the arguments of both call pairs as the ABI takes them, already checked
-  bool paths;          // fiesta_hip_path_corridor (else fiesta_hip_free_boxes)
-  const int32_t *lo, *hi;  // the window (host pointers; both null: none given)
-  const int32_t *vox;      // the seeds, or the waypoints
-  int64_t n_vox;
-  const int64_t *offsets;  // paths: CSR over the waypoints, n_paths + 1
-  int64_t n_paths;
-  double min_clearance;
-  int max_grow, flags;
-  int64_t capacity;
-  const fiesta_hip_free_boxes_result *boxes;   // free boxes
-  const fiesta_hip_corridor_result *corridor;  // paths
-  bool dev;
-};
-
 namespace {  // (this header is included by two translation units)
 
 constexpr int kCorridorBlock = 256, kCorridorMaxBlocks = 4096;
@@ -479,7 +464,7 @@ void corridor_run(hipStream_t st, PlannerScratch &P, const SRC &src, const Corri
       hipLaunchKernelGGL(k_corridor_count<SRC>, dim3(corridor_blocks(n)), dim3(kCorridorBlock), 0, st, src, w, rule, CorridorIn{a.vox, a.n_vox, a.offsets, n}, o);
       FIESTA_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_reach_path_scan, dim3(1), dim3(256), 0, st, r.offsets, n);
+    reach_path_scan(st, r.offsets, n);
     FIESTA_HIP_CHECK(hipGetLastError());
     if (n > 0 && a.capacity > 0 && (r.boxes || r.boxes_pos || r.stop || r.entry)) {
       hipLaunchKernelGGL(k_corridor_write<SRC>, dim3(corridor_blocks(n)), dim3(kCorridorBlock), 0, st, src, w, rule, CorridorIn{a.vox, a.n_vox, a.offsets, n}, o);
@@ -505,7 +490,7 @@ void corridor_run(hipStream_t st, PlannerScratch &P, const SRC &src, const Corri
   hipLaunchKernelGGL(k_corridor_count<SRC>, dim3(corridor_blocks(n)), dim3(kCorridorBlock), 0, st, src, w, rule,
                      CorridorIn{in.dev(wp), a.n_vox, in.dev(poff), n}, o);
   FIESTA_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_reach_path_scan, dim3(1), dim3(256), 0, st, o.offsets, n);
+  reach_path_scan(st, o.offsets, n);
   FIESTA_HIP_CHECK(hipGetLastError());
   out.back(offsets, cnt + 1), out.back(status, cnt), out.back(n_chain, cnt), out.back(bseg, cnt), out.back(bvox, 3 * cnt);
   FIESTA_HIP_CHECK(hipStreamSynchronize(st));

@@ -28,12 +28,7 @@
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
 #include "reach_matrix_kernels.hpp"
-#include "leg_path_kernels.hpp"
-#include "reach_path_kernels.hpp"
 #include "corridor_kernels.hpp"
-#include "tour_kernels.hpp"
-#include "cluster_kernels.hpp"
-#include "split_kernels.hpp"
 #include "view_kernels.hpp"
 #include "ft_kernels.hpp"
 #include "nn_kernels.hpp"
@@ -42,7 +37,6 @@
 #include "path_cost_kernels.hpp"
 #include "refine_kernels.hpp"
 #include "timing_kernels.hpp"
-#include "bounds_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
@@ -2608,17 +2602,6 @@ void DenseMap::reach_matrix(const ReachMatrixArgs &a) {
   reach_matrix_run(stream_, planner_, reach_source(), blo, bhi, g0, a);
 }
 
-// fiesta_hip_reach_paths[_dev], fiesta_hip_cluster_voxels[_dev] and fiesta_hip_split_clusters[_dev]: nothing of the map is read but its resolution and origin
-void DenseMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
-// fiesta_hip_leg_paths[_dev] (leg_path_kernels.hpp): the same, and the batch the last reach_matrix call retained
-void DenseMap::leg_paths(const LegPathArgs &a) { use_device(), leg_paths_run(stream_, planner_, g_.res, g_.org, a); }
-void DenseMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
-void DenseMap::split_clusters(const SplitArgs &a) { use_device(), split_clusters_run(stream_, planner_, g_.res, g_.org, a); }
-// fiesta_hip_corridor_bounds[_dev] (bounds_kernels.hpp): nothing of the map is read at all
-void DenseMap::corridor_bounds(const CorridorBoundsArgs &a) {
-  if (a.n_paths <= 0) return;
-  use_device(), corridor_bounds_run(stream_, planner_, a);
-}
 // fiesta_hip_free_boxes[_dev] and fiesta_hip_path_corridor[_dev] (corridor_kernels.hpp): the window is the caller's box clipped to the
 // array (both null: the whole array), in map voxel coordinates; reach_field's source
 void DenseMap::corridor(const CorridorArgs &a) {
@@ -2633,9 +2616,6 @@ void DenseMap::corridor(const CorridorArgs &a) {
   w.res = g_.res;
   corridor_run(stream_, planner_, reach_source(), w, a);
 }
-// fiesta_hip_site_tour[_dev] (tour_kernels.hpp): no voxel is read
-void DenseMap::site_tour(const TourArgs &a) { use_device(), site_tour_run(stream_, planner_, a); }
-
 // fiesta_hip_view_coverage[_dev] (view_kernels.hpp).  The ray query's source, the frontier call's distance (local array
 // coordinates: a FREE voxel lies inside the array).
 void DenseMap::view_coverage(const ViewArgs &a) {

@@ -8,177 +8,9 @@
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
 #include "engine_choice.hpp"
+#include "planner.hpp"
 
 namespace fiesta {
-
-template <typename T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t cap = 0;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  // Exactly n elements if there are fewer now, contents dropped (large scratch: no doubling).
-  void ensure_exact(size_t n, hipStream_t s) {
-    if (n <= cap) return;
-    if (p) {
-      FIESTA_HIP_CHECK(hipStreamSynchronize(s));
-      (void)hipFree(p);
-      p = nullptr, cap = 0;
-    }
-    FIESTA_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
-    cap = n;
-  }
-  // Grow to at least n elements; optionally preserve the first `keep` elements.
-  void ensure(size_t n, hipStream_t s, size_t keep = 0) {
-    if (n <= cap) return;
-    size_t ncap = cap ? cap : 1024;
-    while (ncap < n) ncap *= 2;
-    T *q = nullptr;
-    FIESTA_HIP_CHECK(hipMalloc((void **)&q, ncap * sizeof(T)));
-    if (p && keep) FIESTA_HIP_CHECK(hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, s));
-    if (p) {
-      FIESTA_HIP_CHECK(hipStreamSynchronize(s));
-      (void)hipFree(p);
-    }
-    p = q;
-    cap = ncap;
-  }
-};
-
-// scratch of fiesta_hip_reach_field (reach_kernels.hpp), owned by a map: the box's traversability bitmap, tile flags and lists of
-// both round parities, the counters, and a cost field for calls that pass none; allocated on first use, freed with the map.
-// field_*: what `cost` holds for fiesta_hip_reach_paths (reach_path_kernels.hpp) -- the RETAINED field: valid after a reach_field
-// call that finished with its cost field in this scratch, or after a reach_paths host call uploaded one; its inclusive box in map
-// voxel coordinates and the connectivity it was flooded with
-struct ReachScratch {
-  DevBuf<uint32_t> bits, flags, lists;
-  DevBuf<int32_t> cost;
-  DevBuf<unsigned long long> ctr;
-  bool field_valid = false;
-  int32_t field_lo[3] = {0, 0, 0}, field_hi[3] = {0, 0, 0};
-  int field_connectivity = 0;
-};
-
-// scratch of fiesta_hip_reach_matrix (reach_matrix_kernels.hpp), owned by a map: the cost planes of one batch of floods, the flags and
-// lists of their (flood, tile) items for both round parities, the counters, and the per-source status and reached counts; allocated
-// on first use, grown on demand, freed with the map.  (The bitmap is ReachScratch::bits; ReachScratch::cost is never touched.)
-// batch_*: what `planes` holds for fiesta_hip_leg_paths (leg_path_kernels.hpp) -- the RETAINED batch: valid after a reach_matrix call
-// that succeeded with at least one source, a non-empty box and all sources in ONE batch (plane s is source s's flood, `status` its
-// per-source status); its inclusive box in map voxel coordinates, its connectivity, the number of sources and `sites`, the
-// call's own copy of the source voxels.  batch_why says what the last call left when it left no batch.
-struct ReachMatrixScratch {
-  enum { kNoCallYet = 0, kManyBatches = 1, kNothingToKeep = 2 };
-  DevBuf<int32_t> planes, status, sites;
-  DevBuf<uint32_t> flags, lists;
-  DevBuf<unsigned long long> ctr, reached;
-  bool batch_valid = false;
-  int batch_why = kNoCallYet;
-  int32_t batch_lo[3] = {0, 0, 0}, batch_hi[3] = {0, 0, 0};
-  int batch_connectivity = 0;
-  int64_t batch_sources = 0;
-};
-
-// scratch of fiesta_hip_site_tour (tour_kernels.hpp), owned by a map: the call's header words and info, the visited sites and the
-// statuses, the compact m x m matrix, and per restart its final tour, length, moves and capped flag; allocated on first use, grown
-// on demand, freed with the map; no other call touches it
-struct TourScratch {
-  DevBuf<int32_t> head, site, status, mat, tours, stat;
-  DevBuf<long long> len;
-};
-
-// scratch of fiesta_hip_cluster_voxels (cluster_kernels.hpp), owned by a map: the voxel hash table, the per-entry union-find arrays,
-// the per-cluster accumulators and two counters; allocated on first use, grown on demand, freed with the map
-struct ClusterScratch {
-  DevBuf<unsigned long long> keys, sum, kmin, ctr;
-  DevBuf<int32_t> tidx, lab, parent, cnt, box, csize;
-  DevBuf<uint32_t> mor;
-};
-
-// scratch of fiesta_hip_split_clusters (split_kernels.hpp), owned by a map, O(n_members): three pools that one call carves into the two
-// member / part buffer sets, the per-part records, boxes and accumulators, the flag bytes, their scan and the counters
-struct SplitScratch {
-  DevBuf<int32_t> i32;
-  DevBuf<unsigned long long> u64;
-  DevBuf<uint8_t> u8;
-};
-
-// scratch of fiesta_hip_view_coverage (view_kernels.hpp), owned by a map: the ring form's expanded views, the per-view pair counts
-// and their scan, the per-view and per-group accumulators and four counters; O(views + groups), grown on demand, freed with the map
-struct ViewScratch {
-  DevBuf<int64_t> P;
-  DevBuf<int32_t> vin, vvis, group;
-  DevBuf<unsigned long long> best, ctr;
-  DevBuf<double> pos, dir;
-  DevBuf<unsigned char> call;  // one ViewCall
-};
-
-// what a map keeps between calls for them, one per map: the staged inputs of a host variant (every host-pointer call of the ABI
-// stages here), the path calls' plan / piece records, the staged outputs, and the four planner calls' own scratch
-struct PlannerScratch {
-  DevBuf<unsigned char> in, tmp, out;
-  ReachScratch reach;
-  ReachMatrixScratch reach_matrix;
-  TourScratch tour;
-  ClusterScratch cluster;
-  SplitScratch split;
-  ViewScratch view;
-};
-
-// A host variant's staged sections in one of PlannerScratch's buffers (in: what goes up, out: what comes back): add() every
-// section (8-byte aligned, in order), alloc(), then dev() / up() / back().  A section whose host pointer is null has no device
-// pointer and is never copied.  Every call synchronises before it returns, so the next call finds both buffers free.
-struct Staging {
-  template <typename T>
-  struct Sec {
-    T *host;
-    size_t off;
-  };
-  DevBuf<unsigned char> &buf;
-  hipStream_t st;
-  size_t end = 0;
-  static size_t up8(size_t b) { return (b + 7) / 8 * 8; }
-  template <typename T>
-  Sec<T> add(T *host, size_t count) {
-    const Sec<T> s{host, end};
-    end += up8(count * sizeof(T));
-    return s;
-  }
-  void alloc(size_t keep = 0) { buf.ensure(std::max<size_t>(end, 8), st, keep); }  // keep: bytes of an earlier alloc() to preserve
-  template <typename T>
-  T *dev(const Sec<T> &s) const {
-    return s.host ? (T *)(buf.p + s.off) : nullptr;
-  }
-  template <typename T>
-  void up(const Sec<T> &s, size_t count) const {
-    if (s.host && count) FIESTA_HIP_CHECK(hipMemcpyAsync(buf.p + s.off, s.host, count * sizeof(T), hipMemcpyHostToDevice, st));
-  }
-  template <typename T>
-  void back(const Sec<T> &s, size_t count) const {
-    if (s.host && count) FIESTA_HIP_CHECK(hipMemcpyAsync(s.host, buf.p + s.off, count * sizeof(T), hipMemcpyDeviceToHost, st));
-  }
-};
-
-// the planner calls' arguments as the C ABI takes them, already checked: each defined in its kernel header, built once by c_api.hip
-template <typename R>
-struct PathArgs;
-struct FrontierArgs;
-struct RayArgs;
-struct ReachArgs;
-struct ReachMatrixArgs;
-struct ReachPathArgs;
-struct LegPathArgs;
-struct CorridorArgs;
-struct PathRefineArgs;
-struct PathTimingArgs;
-struct CorridorBoundsArgs;
-struct TourArgs;
-struct ClusterArgs;
-struct SplitArgs;
-struct ViewArgs;
 
 // Device-side counters, one 64-bit word each.
 enum Counter {
@@ -287,14 +119,10 @@ class DenseMap {
   void ray_query(const RayArgs &a);
   void reach_field(const ReachArgs &a);
   void reach_matrix(const ReachMatrixArgs &a);
-  void site_tour(const TourArgs &a);
-  void reach_paths(const ReachPathArgs &a);
-  void leg_paths(const LegPathArgs &a);
   void corridor(const CorridorArgs &a);
-  void corridor_bounds(const CorridorBoundsArgs &a);
-  void cluster_voxels(const ClusterArgs &a);
-  void split_clusters(const SplitArgs &a);
   void view_coverage(const ViewArgs &a);
+  // what the calls that read no voxel take of this map (planner.hpp)
+  PlannerCtx planner_ctx() { return PlannerCtx{device_, stream_, planner_, g_.res, g_.org}; }
   int64_t count_no_obstacle();
   void slice_distances(int z_vox, double *out);        // nx * ny doubles, x-major
   // GetPointCloud / GetSliceMarker as arrays; both return the total count (may exceed cap), order unspecified

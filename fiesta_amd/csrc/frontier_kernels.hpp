@@ -19,19 +19,10 @@
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
 #include "hash_map.hpp"
+#include "planner_args.hpp"
 #include "wave_ops.hpp"
 
 namespace fiesta {
-struct FrontierArgs {  // the call's arguments as fiesta_hip_get_frontier_voxels[_dev] takes them, already checked
-  const int32_t *lo, *hi;  // both null: the whole map
-  double min_clearance;
-  int32_t *vox;
-  uint8_t *mask;
-  int64_t capacity;
-  unsigned long long *n_out_dev;  // the device variant's total
-  bool dev;
-};
-
 namespace {  // (this header is included by two translation units)
 
 struct FrontierBox {  // inclusive; dense maps: local array coordinates, already clipped; hash-block maps: map voxel coordinates

@@ -21,17 +21,11 @@
 #include "path_cost_kernels.hpp"
 #include "refine_kernels.hpp"
 #include "timing_kernels.hpp"
-#include "bounds_kernels.hpp"
 #include "frontier_kernels.hpp"
 #include "ray_query_kernels.hpp"
 #include "reach_kernels.hpp"
 #include "reach_matrix_kernels.hpp"
-#include "leg_path_kernels.hpp"
-#include "reach_path_kernels.hpp"
 #include "corridor_kernels.hpp"
-#include "tour_kernels.hpp"
-#include "cluster_kernels.hpp"
-#include "split_kernels.hpp"
 #include "view_kernels.hpp"
 #include "path_kernels.hpp"
 #include "relax_kernels.hpp"
@@ -1636,17 +1630,6 @@ void HashMap::reach_matrix(const ReachMatrixArgs &a) {
   reach_matrix_run(stream_, planner_, reach_source(tab), blo, bhi, off, a);
 }
 
-// fiesta_hip_reach_paths[_dev], fiesta_hip_cluster_voxels[_dev] and fiesta_hip_split_clusters[_dev]: nothing of the map is read but its resolution and origin
-void HashMap::reach_paths(const ReachPathArgs &a) { use_device(), reach_paths_run(stream_, planner_, g_.res, g_.org, a); }
-// fiesta_hip_leg_paths[_dev] (leg_path_kernels.hpp): the same, and the batch the last reach_matrix call retained
-void HashMap::leg_paths(const LegPathArgs &a) { use_device(), leg_paths_run(stream_, planner_, g_.res, g_.org, a); }
-void HashMap::cluster_voxels(const ClusterArgs &a) { use_device(), cluster_voxels_run(stream_, planner_, g_.res, g_.org, a); }
-void HashMap::split_clusters(const SplitArgs &a) { use_device(), split_clusters_run(stream_, planner_, g_.res, g_.org, a); }
-// fiesta_hip_corridor_bounds[_dev] (bounds_kernels.hpp): nothing of the map is read at all
-void HashMap::corridor_bounds(const CorridorBoundsArgs &a) {
-  if (a.n_paths <= 0) return;
-  use_device(), corridor_bounds_run(stream_, planner_, a);
-}
 // fiesta_hip_free_boxes[_dev] and fiesta_hip_path_corridor[_dev] (corridor_kernels.hpp): the map has no outside -- the window is the
 // caller's box clamped to +-2^30, or all of that range -- every page answers, resident or parked; reach_field's source
 void HashMap::corridor(const CorridorArgs &a) {
@@ -1663,9 +1646,6 @@ void HashMap::corridor(const CorridorArgs &a) {
   w.res = g_.res;
   corridor_run(stream_, planner_, reach_source(tab), w, a);
 }
-// fiesta_hip_site_tour[_dev] (tour_kernels.hpp): no voxel is read
-void HashMap::site_tour(const TourArgs &a) { use_device(), site_tour_run(stream_, planner_, a); }
-
 // fiesta_hip_view_coverage[_dev] (view_kernels.hpp).  The ray query's source, the frontier call's distance (map voxel
 // coordinates).  Every page answers, resident or parked.
 void HashMap::view_coverage(const ViewArgs &a) {

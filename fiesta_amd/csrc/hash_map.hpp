@@ -87,14 +87,9 @@ class HashMap {
   void ray_query(const RayArgs &a);
   void reach_field(const ReachArgs &a);
   void reach_matrix(const ReachMatrixArgs &a);
-  void site_tour(const TourArgs &a);
-  void reach_paths(const ReachPathArgs &a);
-  void leg_paths(const LegPathArgs &a);
   void corridor(const CorridorArgs &a);
-  void corridor_bounds(const CorridorBoundsArgs &a);
-  void cluster_voxels(const ClusterArgs &a);
-  void split_clusters(const SplitArgs &a);
   void view_coverage(const ViewArgs &a);
+  PlannerCtx planner_ctx() { return PlannerCtx{device_, stream_, planner_, g_.res, g_.org}; }  // as DenseMap's
   // every voxel of every allocated page, page order: vox (map voxel coordinates), d2, coc, occ; returns the count
   int64_t download(int32_t *vox, int32_t *d2, int32_t *coc, uint8_t *occ);
   void download_counts(int32_t *num_hit, int32_t *num_miss);  // same order as download()

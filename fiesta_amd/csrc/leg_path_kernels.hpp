@@ -20,21 +20,12 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "reach_path_kernels.hpp"
 
 namespace fiesta {
-struct LegPathArgs {  // the call's arguments as fiesta_hip_leg_paths[_dev] takes them, already checked
-  const int32_t *from, *to, *to_vox;  // exactly one of to / to_vox unless n_legs = 0
-  int64_t n_legs;
-  int flags, max_span;
-  int64_t capacity;
-  const fiesta_hip_leg_paths_result *res;
-  fiesta_hip_leg_paths_info *info;
-  bool dev;
-};
-
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 #ifndef FIESTA_LEG_PATH_WAVES
 #define FIESTA_LEG_PATH_WAVES 1  // waves, and so legs, per work-group (a build-time knob for tools/leg_paths_bench.py --lib: DESIGN.md 6o)

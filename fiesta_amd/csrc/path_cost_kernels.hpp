@@ -25,8 +25,6 @@
 #include "path_kernels.hpp"
 
 namespace fiesta {
-using PathCostArgs = PathArgs<fiesta_hip_path_cost_result>;
-
 namespace {  // (this header is included by two translation units)
 
 constexpr int kCostSegBlocks = 512;  // grid of k_cost_segments (a grid-stride loop over the piece records)

@@ -30,25 +30,12 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "wave_ops.hpp"
 
 namespace fiesta {
-// the arguments as fiesta_hip_path_clearance[_dev] and fiesta_hip_path_cost[_dev] take them (R: the call's result struct),
-// already checked
-template <typename R>
-struct PathArgs {
-  const double *w;
-  int64_t n_wp;
-  const int64_t *off;
-  int64_t n_paths;
-  double step, margin;
-  const R *res;
-  bool dev;
-};
-using PathClearanceArgs = PathArgs<fiesta_hip_path_result>;
-
-namespace {  // (this header is included by two translation units)
+namespace {  // (this header is included by three translation units)
 
 constexpr long long kPathPiece = 1024;        // samples per piece at least (16 per lane of the wave that evaluates it)
 constexpr int64_t kPathRecords = 1 << 18;     // piece records per call: a path gets at most max(1, kPathRecords / n_paths) pieces

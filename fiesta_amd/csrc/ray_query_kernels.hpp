@@ -18,18 +18,11 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "ray_walk.hpp"
 
 namespace fiesta {
-struct RayArgs {  // the call's arguments as fiesta_hip_ray_query[_dev] takes them, already checked
-  const double *start, *end;
-  int64_t n;
-  int stop_mask;
-  const fiesta_hip_ray_result *res;
-  bool dev;
-};
-
 namespace {  // (this header is included by two translation units)
 
 constexpr double kRayMaxCoord = 1073741824.0;  // 2^30: |start / resolution| and |end / resolution| stay below it

@@ -23,24 +23,12 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "frontier_kernels.hpp"
 #include "relax_kernels.hpp"
 
 namespace fiesta {
-struct ReachArgs {  // the call's arguments as fiesta_hip_reach_field[_dev] takes them, already checked
-  const int32_t *lo, *hi;  // the caller's box (both null: the whole array)
-  const int32_t *seeds;
-  int64_t n_seeds;
-  const int32_t *targets;
-  int64_t n_targets;
-  double min_clearance;
-  int connectivity, flags;
-  const fiesta_hip_reach_result *res;
-  fiesta_hip_reach_info *info;
-  bool dev;
-};
-
 namespace {  // (this header is included by two translation units)
 
 constexpr int64_t kReachMaxVoxels = 1ll << 28;  // of the clipped box: keeps every cost below 2^31 (5 * 2^28) and bounds the scratch

@@ -25,23 +25,11 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "reach_kernels.hpp"
 
 namespace fiesta {
-struct ReachMatrixArgs {  // the call's arguments as fiesta_hip_reach_matrix[_dev] takes them, already checked
-  const int32_t *lo, *hi;  // the caller's box (both null: the whole array)
-  const int32_t *sources;
-  int64_t n_sources;
-  const int32_t *targets;  // null with n_targets = 0: the columns are the sources
-  int64_t n_targets;
-  double min_clearance;
-  int connectivity, flags, max_fields;
-  const fiesta_hip_reach_matrix_result *res;
-  fiesta_hip_reach_matrix_info *info;
-  bool dev;
-};
-
 namespace {  // (this header is included by two translation units)
 
 constexpr int64_t kReachMatrixMaxEntries = 1ll << 28;  // of B cost planes (1 GiB of scratch), and of the matrix itself

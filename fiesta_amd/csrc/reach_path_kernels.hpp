@@ -24,23 +24,13 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "ray_walk.hpp"
 #include "wave_ops.hpp"
 
 namespace fiesta {
-struct ReachPathArgs {  // the call's arguments as fiesta_hip_reach_paths[_dev] takes them, already checked
-  const int32_t *cost;  // null: the retained field
-  const int32_t *box_lo, *box_hi;
-  const int32_t *targets;
-  int64_t n_targets;
-  int connectivity, flags, max_span;
-  int64_t capacity;
-  const fiesta_hip_reach_paths_result *res;
-  bool dev;
-};
-
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int64_t kReachPathMaxVoxels = 1ll << 28;  // of an explicit box (reach_field's bound)
 constexpr int kReachPathManhattan = 4095;           // voxel steps between the ends of a visibility test (the ray query's bound)

@@ -25,18 +25,6 @@
 #include "path_cost_kernels.hpp"
 
 namespace fiesta {
-// the arguments as fiesta_hip_path_refine[_dev] take them, already checked
-struct PathRefineArgs {
-  const double *w;
-  int64_t n_wp;
-  const int64_t *off;
-  int64_t n_paths;
-  const double *bounds;  // nullable
-  const fiesta_hip_refine_params *par;
-  const fiesta_hip_refine_result *res;
-  bool dev;
-};
-
 namespace {  // (this header is included by two translation units)
 
 constexpr int kRefineWaveMax = 128;        // paths of at most this many waypoints are refined by one wave (two waypoints per lane)

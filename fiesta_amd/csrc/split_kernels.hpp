@@ -36,26 +36,11 @@
 #include "../../include/fiesta_hip.h"
 #include "cluster_kernels.hpp"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 
 namespace fiesta {
-struct SplitArgs {  // the call's arguments as fiesta_hip_split_clusters[_dev] takes them, already checked
-  const int32_t *vox;
-  const uint8_t *mask;
-  const int32_t *key;
-  int64_t n;
-  const int64_t *offsets, *members;
-  int64_t n_clusters;
-  const int64_t *n_clusters_dev;
-  int64_t n_members;
-  int max_size, max_extent, max_depth;
-  int64_t part_capacity;
-  const fiesta_hip_split_result *res;
-  fiesta_hip_split_info *info;
-  bool dev;
-};
-
-namespace {  // (this header is included by three translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int kSplitBlock = 256, kSplitItems = 8, kSplitTile = kSplitBlock * kSplitItems;  // a work-group's share of the member scan
 constexpr int kSplitScanBlock = 1024;

@@ -27,17 +27,6 @@
 #include "refine_kernels.hpp"
 
 namespace fiesta {
-// the arguments as fiesta_hip_path_timing[_dev] take them, already checked
-struct PathTimingArgs {
-  const double *w;
-  int64_t n_wp;
-  const int64_t *off;
-  int64_t n_paths;
-  const fiesta_hip_timing_params *par;
-  const fiesta_hip_path_timing_result *res;
-  bool dev;
-};
-
 namespace {  // (this header is included by two translation units)
 
 constexpr int kTimingWaveMax = 256;  // paths of at most this many samples are timed by one wave (four samples per lane)

@@ -31,23 +31,12 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "wave_ops.hpp"
 
 namespace fiesta {
-struct TourArgs {  // the call's arguments as fiesta_hip_site_tour[_dev] takes them, already checked
-  const int32_t *cost;
-  int32_t n;
-  int64_t ld;
-  int32_t start, flags, restarts;
-  uint64_t seed;
-  int32_t max_moves;
-  const fiesta_hip_tour_result *res;  // nullable
-  fiesta_hip_tour_info *info;
-  bool dev;
-};
-
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int kTourThreads = 256;
 constexpr int kTourLdsSites = 128;  // the matrix lives in LDS up to this m

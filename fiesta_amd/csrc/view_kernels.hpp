@@ -34,26 +34,13 @@
 
 #include "../../include/fiesta_hip.h"
 #include "common.hpp"
-#include "dense_map.hpp"
+#include "planner.hpp"
+#include "planner_args.hpp"
 #include "ray_query_kernels.hpp"
 #include "ray_walk.hpp"
 #include "wave_ops.hpp"
 
 namespace fiesta {
-struct ViewArgs {  // the call's arguments as fiesta_hip_view_coverage[_dev] takes them, already checked
-  const int32_t *vox;
-  int64_t n;
-  const int64_t *offsets, *members;
-  int64_t n_groups;
-  const int64_t *n_groups_dev;
-  int64_t n_members;
-  const fiesta_hip_view_set *views;
-  const fiesta_hip_view_sensor *sensor;
-  const fiesta_hip_view_result *res;
-  fiesta_hip_view_info *info;
-  bool dev;
-};
-
 namespace {  // (this header is included by two translation units)
 
 constexpr int kViewBlock = 256, kViewMaxBlocks = 2048;

@@ -92,6 +92,30 @@ def test_hand_scheduled_kernels_do_not_spill():
     assert any("k_nn_fill_full" in k for k in guarded) and any("k_ft_x" in k for k in guarded)
 
 
+def test_map_independent_planner_kernels_are_compiled_once():
+    """The planner calls that read no voxel (reach paths, leg paths, clusters, cluster splitting, site tour, corridor bounds) are
+    compiled in planner.hip alone: each of their kernels sits in exactly one code object of the library, all in the same one.  The
+    library holds four: those of dense_map.hip, hash_map.hip, planner.hip and raycast.hip (the other sources define no kernel).
+    Held more than once are only the 26 kernels of the headers that both store units include (k_reach_*, k_rmx_*, k_view_*,
+    k_path_*, k_cost_*, k_level_next, k_zero_words).  Kernel names only are read."""
+    import sys
+    from fiesta_amd import _lib
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import check_kernel_resources
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build_hip()
+    copies = check_kernel_resources.kernel_copies(_lib.LIB_PATH)
+    families = ("k_reach_path_", "k_leg_path_", "k_cluster_", "k_split_", "k_tour_", "k_corridor_bounds", "k_bounds_fill")
+    mine = {k: v for k, v in copies.items() if any(f in k for f in families)}
+    for f in families:
+        assert any(f in k for k in mine), (f, sorted(mine))
+    assert all(len(v) == 1 for v in mine.values()), {k: v for k, v in mine.items() if len(v) != 1}
+    assert len({v[0] for v in mine.values()}) == 1, mine
+    assert len(check_kernel_resources.code_objects(_lib.LIB_PATH)) == 4
+    assert sum(len(v) > 1 for v in copies.values()) <= 26, sorted(k for k, v in copies.items() if len(v) > 1)
+
+
 def test_path_note_names_follow_the_header():
     """fiesta_hip_stats.path_notes: the names the Python statistics give the bits (`why`) are the header's FIESTA_HIP_NOTE_* in
     bit order, and the struct mirrors end in the same field."""

@@ -175,7 +175,7 @@ def test_cluster_kernels_use_no_scratch():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_kernel_resources
     res = {k: v for k, v in check_kernel_resources.kernel_resources(so).items() if "k_cluster_" in k}
-    # (the two translation units' copies carry the same name; the link pass has one instance per connectivity)
+    # (planner.hip holds the only copy of each; the link pass has one instance per connectivity)
     for kernel, copies in (("k_cluster_init", 1), ("k_cluster_insert", 1), ("k_cluster_seed", 1), ("k_cluster_link", 3), ("k_cluster_flatten", 1),
                            ("k_cluster_number", 1), ("k_cluster_reduce", 1), ("k_cluster_finish", 1)):
         assert sum(kernel in k for k in res) == copies, (kernel, sorted(res))

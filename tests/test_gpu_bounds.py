@@ -2,7 +2,7 @@
 
 The model is fiesta_amd.corridor_bounds_model (tests/test_bounds_rule.py holds it to fiesta_amd.corridor_bounds and to literal
 loops).  Every output is compared bit for bit: `bounds` as int64 views, `ok` and `box` exactly.  The call reads no voxel, so any tiny
-map serves; both stores run, because each forwards to the one function from its own translation unit.  Then the real chain on the
+map serves; both stores run, because each hands its own stream and scratch to the one function of planner.hip.  Then the real chain on the
 reach example's scene: the class method against fiesta_amd.corridor_bounds, and reach paths -> corridors -> bounds -> refinement all
 on the device against the route that computes the bounds on the host.
 """

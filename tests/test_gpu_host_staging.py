@@ -1,7 +1,7 @@
 """Staging of the older host-pointer calls (include/fiesta_hip.h: set_occupancy_vox / pos, get_distance_vox / pos, get_dist_grad,
 get_occupancy_vox / pos, download_field, download_hash, get_occupied_voxels, get_point_cloud, get_slice_marker and the host form of
 get_frontier_voxels).  Each of them moves its host arrays through sections of the two device buffers the planner calls' host variants
-use as well (dense_map.hpp: Staging); test_gpu_optional_outputs.py pins that bookkeeping for the planner calls, this file for the
+use as well (planner.hpp: Staging); test_gpu_optional_outputs.py pins that bookkeeping for the planner calls, this file for the
 rest, through the C ABI alone (ctypes on fiesta_amd._lib), on that file's map and with its sentinel / guard arrays.
 
 What is pinned: a nullable output alone equals the same output of the call that asks for everything, and nothing else is written;

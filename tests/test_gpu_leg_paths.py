@@ -383,6 +383,70 @@ def test_hash_block_map(hip_lib):
     m.close()
 
 
+def small_map(kind, walls):
+    """a 16^3 scene, all observed, `walls` occupied, on either store"""
+    import fiesta_amd
+    if kind == "dense":
+        m = new_dense((16, 16, 16))
+    else:
+        m = fiesta_amd.ESDFMap((0, 0, 0), RES, reserve_size=200000, mode="hash")
+        m.SetParameters(*P_DEFAULT)
+        m.SetOriginalRange()
+    m.SetOccupancy(np.argwhere(~walls).astype(np.int32), 0, want_ret=False)
+    m.UpdateOccupancy(True)
+    m.UpdateESDF()
+    occupy(m, np.argwhere(walls))
+    return m
+
+
+def same_bits(got, want, what):
+    assert got.keys() == want.keys(), what
+    for k in want:
+        if isinstance(want[k], np.ndarray):
+            assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape and got[k].tobytes() == want[k].tobytes(), (what, k)
+        else:
+            assert got[k] == want[k], (what, k)
+
+
+@pytest.mark.parametrize("kinds", [("dense", "hash"), ("hash", "dense")])
+def test_retained_floods_belong_to_their_map(hip_lib, kinds):
+    """Leg paths, reach paths, clusters, cluster splitting and the site tour are one function each for both stores, which reaches a
+    map's scratch through a reference: what a map retained -- the reach matrix's batch, the reach field's cost field -- is still its
+    own after another map, of the other store and alive at the same time, ran every such call on other sites in another box."""
+    wall_a = np.zeros((16, 16, 16), bool)
+    wall_a[8, 3:] = True                                     # a wall across x with a gap at low y
+    wall_b = np.zeros((16, 16, 16), bool)
+    wall_b[:, 6, :12] = True                                 # a wall across y with a gap at high z
+    a, b = small_map(kinds[0], wall_a), small_map(kinds[1], wall_b)
+    sites_a, box_a = [(2, 2, 2), (13, 13, 13), (2, 13, 8), (13, 2, 8)], ((0, 0, 0), (15, 15, 15))
+    sites_b, box_b = [(1, 1, 1), (14, 14, 1), (5, 10, 14), (10, 1, 7)], ((1, 0, 0), (15, 14, 15))
+    fr, to = [0, 1, 2, 3, 0], [1, 2, 3, 0, 2]
+    targets = np.array([(13, 13, 13), (2, 13, 8), (9, 15, 0), (8, 8, 8)], np.int32)      # (the last one is a wall voxel)
+    # map a: the floods, and what the calls read out of them
+    assert a.ReachMatrix(sites_a, lo=box_a[0], hi=box_a[1], max_fields=4)["batches"] == 1
+    legs = a.LegPaths(fr, to=to, shortcut=True)
+    assert (legs["status"] == OK).all() and (np.diff(legs["offsets"]) >= 2).all()
+    a.ReachField([sites_a[0]], lo=box_a[0], hi=box_a[1], want_cost=False)
+    paths = a.ReachPaths(targets, shortcut=True)
+    assert paths["status"].tolist() == [OK, OK, OK, BLOCKED] and paths["offsets"][-1] >= 6
+    # map b: every call of the shared unit, and the floods that fill what they read
+    mx = b.ReachMatrix(sites_b, lo=box_b[0], hi=box_b[1], max_fields=4)
+    assert mx["batches"] == 1
+    b.ReachField([sites_b[1]], lo=box_b[0], hi=box_b[1], want_cost=False)
+    blobs = np.concatenate([np.argwhere(np.ones((4, 4, 4), bool)) + 1, np.argwhere(np.ones((4, 4, 4), bool)) + 10]).astype(np.int32)
+    cl = b.ClusterVoxels(blobs)
+    assert cl["size"].tolist() == [64, 64]
+    assert b.SplitClusters(blobs, cl["offsets"], cl["members"], max_size=16)["n_parts"] == 8
+    assert b.SiteTour(mx["cost"], start=0, restarts=4)["n_visited"] == 4
+    legs_b, paths_b = b.LegPaths(fr, to=to, shortcut=True), b.ReachPaths(targets, shortcut=True)
+    assert legs_b["waypoints_vox"].tobytes() != legs["waypoints_vox"].tobytes() and paths_b["status"].tolist() != paths["status"].tolist()
+    # map a again, no new flood: the same bits
+    same_bits(a.LegPaths(fr, to=to, shortcut=True), legs, f"leg paths on the {kinds[0]} map after the {kinds[1]} map's calls")
+    same_bits(a.ReachPaths(targets, shortcut=True), paths, f"reach paths on the {kinds[0]} map after the {kinds[1]} map's calls")
+    a.close()
+    b.close()
+
+
 def test_whole_chain_on_the_device(scene_map):
     """ReachMatrixDevice -> SiteTourDevice -> LegPathsDevice (from / to: views into the order array) -> PathCorridorDevice, against the
     same chain through the host calls"""

@@ -38,9 +38,8 @@ def code_objects(so_path):
     return out
 
 
-def kernel_resources(so_path):
-    """{kernel symbol: {private_segment_fixed_size, sgpr_spill_count, vgpr_spill_count, vgpr_count}} of every gfx950 kernel."""
-    out = {}
+def _kernels(so_path):
+    """(index of the code object, kernel symbol, its resource figures) of every gfx950 kernel, code object by code object."""
     with tempfile.TemporaryDirectory() as tmp:
         for k, co in enumerate(code_objects(so_path)):
             f = os.path.join(tmp, f"co{k}")
@@ -51,7 +50,20 @@ def kernel_resources(so_path):
                 if not name:
                     continue
                 get = lambda key: int(re.search(rf"\.{key}:\s+(\d+)", blk).group(1)) if re.search(rf"\.{key}:\s+(\d+)", blk) else 0  # noqa: E731
-                out[name.group(1)] = {k2: get(k2) for k2 in ("private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count", "vgpr_count")}
+                yield k, name.group(1), {k2: get(k2) for k2 in ("private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count", "vgpr_count")}
+
+
+def kernel_resources(so_path):
+    """{kernel symbol: {private_segment_fixed_size, sgpr_spill_count, vgpr_spill_count, vgpr_count}} of every gfx950 kernel."""
+    return {name: res for _, name, res in _kernels(so_path)}
+
+
+def kernel_copies(so_path):
+    """{kernel symbol: [index of every code object that holds it]}: a kernel of a header that several translation units include is
+    compiled once per unit, and kernel_resources() shows only the last of those copies."""
+    out = {}
+    for k, name, _ in _kernels(so_path):
+        out.setdefault(name, []).append(k)
     return out
 
 
