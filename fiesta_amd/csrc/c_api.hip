@@ -8,7 +8,9 @@
 
 #include "../../include/fiesta_hip.h"
 #include "dense_map.hpp"
+#include "dense_read.hpp"
 #include "hash_map.hpp"
+#include "hash_read.hpp"
 #include "planner.hpp"
 #include "planner_args.hpp"
 #include "shard_group.hpp"
@@ -60,8 +62,8 @@ DenseMap &dense(fiesta_hip_map *m, const char *what) {
   return *m->dense;
 }
 // The planner calls: one body per host / _dev pair.  Each checks the whole-call errors of include/fiesta_hip.h on the arguments as
-// the ABI took them (the call's aggregate of planner_args.hpp), then hands the same object on: to the map's store, or -- the six
-// calls that read no voxel -- to the call's function of planner.hpp with the store's planner_ctx().
+// the ABI took them (the call's aggregate of planner_args.hpp), then hands the same object on to the call's function of planner.hpp,
+// with the store's planner_ctx() and -- the ten calls that read voxels -- its planner_view(does the call read the bitmaps?).
 
 // shared by path_clearance and path_cost (R: the call's result struct); a host batch: the CSR rules as well
 template <typename R>
@@ -76,12 +78,12 @@ void path_checks(fiesta_hip_map *m, const fiesta::PathArgs<R> &a) {
 }
 void path_clearance(fiesta_hip_map *m, const fiesta::PathClearanceArgs &a) {
   path_checks(m, a);
-  on_store(m, [&](auto &s) { s.path_clearance(a); });
+  on_store(m, [&](auto &s) { fiesta::path_clearance(s.planner_ctx(), s.planner_view(false), s.host_path_eval(), a); });
 }
 void path_cost(fiesta_hip_map *m, const fiesta::PathCostArgs &a) {
   path_checks(m, a);
   need(std::isfinite(a.margin), "path_cost: margin must be finite");
-  on_store(m, [&](auto &s) { s.path_cost(a); });
+  on_store(m, [&](auto &s) { fiesta::path_cost(s.planner_ctx(), s.planner_view(false), s.host_path_eval(), a); });
 }
 // n_out: the variant's total (host or device pointer); returns the host variant's total
 int64_t frontier_voxels(fiesta_hip_map *m, const fiesta::FrontierArgs &a, const void *n_out) {
@@ -90,14 +92,14 @@ int64_t frontier_voxels(fiesta_hip_map *m, const fiesta::FrontierArgs &a, const 
   need(!std::isnan(a.min_clearance), "get_frontier_voxels: min_clearance is NaN");
   need((a.lo == nullptr) == (a.hi == nullptr), "get_frontier_voxels: lo and hi must both be given or both be null");
   need(a.capacity >= 0, "get_frontier_voxels: negative capacity");
-  return on_store(m, [&](auto &s) { return s.frontier_voxels(a); });
+  return on_store(m, [&](auto &s) { return fiesta::frontier_voxels(s.planner_ctx(), s.planner_view(true), a); });
 }
 void ray_query(fiesta_hip_map *m, const fiesta::RayArgs &a) {
   need(m != nullptr, "null map handle");
   need(a.start && a.end && a.res, "ray_query: start, end or result is null");
   need(a.n >= 0, "ray_query: negative count");
   need(a.stop_mask >= 0 && a.stop_mask <= 7, "ray_query: stop_mask must be a subset of OCCUPIED | UNKNOWN | OUTSIDE (0..7)");
-  on_store(m, [&](auto &s) { s.ray_query(a); });
+  on_store(m, [&](auto &s) { fiesta::ray_query(s.planner_ctx(), s.planner_view(true), a); });
 }
 // none of these errors needs a device: they are checked before the handle is touched; the clipped box's volume is checked by the
 // map, before anything is launched
@@ -113,7 +115,7 @@ void reach_field(fiesta_hip_map *m, const fiesta::ReachArgs &a) {
   need(a.targets != nullptr || a.res->target_cost == nullptr, "reach_field: target_cost given without targets");
   need(m != nullptr, "null map handle");
   need(m->dense != nullptr || a.lo != nullptr, "reach_field: a hash-block map has no outside, the box is mandatory");
-  on_store(m, [&](auto &s) { s.reach_field(a); });
+  on_store(m, [&](auto &s) { fiesta::reach_field(s.planner_ctx(), s.planner_view(true), a); });
 }
 // reach_field's list and the matrix's own; none needs a device
 void reach_matrix(fiesta_hip_map *m, const fiesta::ReachMatrixArgs &a) {
@@ -131,7 +133,7 @@ void reach_matrix(fiesta_hip_map *m, const fiesta::ReachMatrixArgs &a) {
   need(a.n_sources <= cap && n_cols <= cap && a.n_sources * n_cols <= cap, "reach_matrix: the matrix holds more than 2^28 entries");
   need(m != nullptr, "null map handle");
   need(m->dense != nullptr || a.lo != nullptr, "reach_matrix: a hash-block map has no outside, the box is mandatory");
-  on_store(m, [&](auto &s) { s.reach_matrix(a); });
+  on_store(m, [&](auto &s) { fiesta::reach_matrix(s.planner_ctx(), s.planner_view(true), a); });
 }
 // none of these errors needs a device; what the matrix itself must satisfy is checked on the device, before any search
 void site_tour(fiesta_hip_map *m, const fiesta::TourArgs &a) {
@@ -208,7 +210,7 @@ void corridor(fiesta_hip_map *m, const fiesta::CorridorArgs &a) {
     }
   }
   need(m != nullptr, "null map handle");
-  on_store(m, [&](auto &st) { st.corridor(a); });
+  on_store(m, [&](auto &st) { fiesta::corridor(st.planner_ctx(), st.planner_view(true), a); });
 }
 // fiesta_hip_path_refine: none of these errors needs a device, and all are checked before the handle is touched (a host batch: the
 // CSR rules as well)
@@ -231,7 +233,7 @@ void path_refine(fiesta_hip_map *m, const fiesta::PathRefineArgs &a) {
     for (int64_t i = 0; i < a.n_paths; ++i) need(a.off[i] <= a.off[i + 1], "path_refine: offsets must be non-decreasing");
   }
   need(m != nullptr, "null map handle");
-  on_store(m, [&](auto &s) { s.path_refine(a); });
+  on_store(m, [&](auto &s) { fiesta::path_refine(s.planner_ctx(), s.planner_view(false), a); });
 }
 // fiesta_hip_path_timing: none of these errors needs a device, and all are checked before the handle is touched (a host batch: the
 // CSR rules as well)
@@ -253,7 +255,7 @@ void path_timing(fiesta_hip_map *m, const fiesta::PathTimingArgs &a) {
     for (int64_t i = 0; i < a.n_paths; ++i) need(a.off[i] <= a.off[i + 1], "path_timing: offsets must be non-decreasing");
   }
   need(m != nullptr, "null map handle");
-  on_store(m, [&](auto &s) { s.path_timing(a); });
+  on_store(m, [&](auto &s) { fiesta::path_timing(s.planner_ctx(), s.planner_view(false), a); });
 }
 // fiesta_hip_corridor_bounds: none of these errors needs a device, and all are checked before the handle is touched (a host batch:
 // the CSR rules of both offset arrays as well)
@@ -348,7 +350,7 @@ void view_coverage(fiesta_hip_map *m, const fiesta::ViewArgs &a) {
   need((s->flags & ~FIESTA_HIP_VIEW_OMNI) == 0, "view_coverage: unknown flag bits");
   need(s->min_visible >= 1, "view_coverage: min_visible must be >= 1");
   need(m != nullptr, "null map handle");
-  on_store(m, [&](auto &st) { st.view_coverage(a); });
+  on_store(m, [&](auto &st) { fiesta::view_coverage(st.planner_ctx(), st.planner_view(true), a); });
 }
 }  // namespace
 

@@ -127,6 +127,9 @@ __device__ inline void wave_append(bool pred, uint32_t value, uint32_t *list, un
   if (pred) list[base + __popcll(m & ((1ull << lane) - 1ull))] = value;
 }
 
+// 32 bits from bit s (0 .. 31) of the 64-bit word hi:lo: a bitmap row read at any z (the reach sources of dense_read.hpp / hash_read.hpp)
+__device__ inline uint32_t reach_funnel(uint32_t lo, uint32_t hi, int s) { return (uint32_t)((((unsigned long long)hi << 32) | lo) >> s); }
+
 // one thread per element unless the caller names a cap (= the kernel strides over the grid): the default must cover the
 // largest arrays (a 1024^3 shard touches 10^9 voxels at once -- a cap of 2^20 blocks silently dropped three quarters
 // of them, found by tools/c5_smoke.py)

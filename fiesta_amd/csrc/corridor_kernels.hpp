@@ -12,7 +12,7 @@
 //   k_free_boxes<SRC>        a wave per seed, grid-stride
 //   k_corridor_count<SRC>    a wave per path: checks the path, walks the voxel chain of every segment (candidate A, then B), runs the
 //                            greedy and writes the per-path outputs and the number of boxes into offsets[p + 1]
-//   k_reach_path_scan        (reach_path_kernels.hpp, through planner.hpp: reach_path_scan) offsets -> running totals
+//   k_reach_path_scan        (reach_path_kernels.hpp, as it is) offsets -> running totals
 //   k_corridor_write<SRC>    the greedy again, storing box k of path p at offsets[p] + k if that index lies below the capacity
 // A segment's chain: the reference traversal (ray_walk.hpp: dda_walk, f64) is computed redundantly by every lane; lane k & 63 keeps
 // voxel k, and every 64 voxels the lanes test theirs and a ballot finds the first that is not traversable.  The axis of every
@@ -35,9 +35,10 @@
 #include "frontier_kernels.hpp"
 #include "ray_walk.hpp"
 #include "reach_kernels.hpp"
+#include "reach_path_kernels.hpp"
 
 namespace fiesta {
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int kCorridorBlock = 256, kCorridorMaxBlocks = 4096;
 constexpr int kCorridorCoordMax = 1 << 30;
@@ -464,7 +465,7 @@ void corridor_run(hipStream_t st, PlannerScratch &P, const SRC &src, const Corri
       hipLaunchKernelGGL(k_corridor_count<SRC>, dim3(corridor_blocks(n)), dim3(kCorridorBlock), 0, st, src, w, rule, CorridorIn{a.vox, a.n_vox, a.offsets, n}, o);
       FIESTA_HIP_CHECK(hipGetLastError());
     }
-    reach_path_scan(st, r.offsets, n);
+    hipLaunchKernelGGL(k_reach_path_scan, dim3(1), dim3(256), 0, st, r.offsets, n);
     FIESTA_HIP_CHECK(hipGetLastError());
     if (n > 0 && a.capacity > 0 && (r.boxes || r.boxes_pos || r.stop || r.entry)) {
       hipLaunchKernelGGL(k_corridor_write<SRC>, dim3(corridor_blocks(n)), dim3(kCorridorBlock), 0, st, src, w, rule, CorridorIn{a.vox, a.n_vox, a.offsets, n}, o);
@@ -490,7 +491,7 @@ void corridor_run(hipStream_t st, PlannerScratch &P, const SRC &src, const Corri
   hipLaunchKernelGGL(k_corridor_count<SRC>, dim3(corridor_blocks(n)), dim3(kCorridorBlock), 0, st, src, w, rule,
                      CorridorIn{in.dev(wp), a.n_vox, in.dev(poff), n}, o);
   FIESTA_HIP_CHECK(hipGetLastError());
-  reach_path_scan(st, o.offsets, n);
+  hipLaunchKernelGGL(k_reach_path_scan, dim3(1), dim3(256), 0, st, o.offsets, n);
   FIESTA_HIP_CHECK(hipGetLastError());
   out.back(offsets, cnt + 1), out.back(status, cnt), out.back(n_chain, cnt), out.back(bseg, cnt), out.back(bvox, 3 * cnt);
   FIESTA_HIP_CHECK(hipStreamSynchronize(st));

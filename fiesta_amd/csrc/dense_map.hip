@@ -24,20 +24,11 @@
 // are appended to the next round's tile list (level-synchronous rounds, one launch per round).
 #include "dense_map.hpp"
 #include "checkpoint.hpp"
-#include "frontier_kernels.hpp"
-#include "ray_query_kernels.hpp"
-#include "reach_kernels.hpp"
-#include "reach_matrix_kernels.hpp"
-#include "corridor_kernels.hpp"
-#include "view_kernels.hpp"
+#include "dense_read.hpp"
 #include "ft_kernels.hpp"
 #include "nn_kernels.hpp"
 #include "mask_kernels.hpp"
 #include "level_kernels.hpp"
-#include "path_cost_kernels.hpp"
-#include "refine_kernels.hpp"
-#include "timing_kernels.hpp"
-#include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
 #include <algorithm>
@@ -579,73 +570,7 @@ __global__ __launch_bounds__(256) void k_invalidate(Geom g, TileGrid tg, vox_t *
 // =====================================================================================================
 // queries
 // =====================================================================================================
-// The arithmetic of the queries is written once, over any SOURCE of voxel words: the batch kernels read the field in HBM, the
-// scalar host calls of the drop-in class (one position per call: fiesta::ESDFMap::GetDistance & co., include/fiesta/ESDFMap.h)
-// read a host-side cache of 16^3-voxel bricks (DenseMap::HostBricks below) -- same code, same -ffp-contract=off, same bits.
-__host__ __device__ inline double word_distance(const Geom &g, vox_t w, int x, int y, int z) {
-  // GetDistance(Vector3i) (src/ESDFMap.cpp:477-479): unobserved (-10000) reads as +10000
-  if (w & kNoCoc) return (double)FIESTA_HIP_INFINITY;
-  const int32_t d2 = dist2(g.wrap, x + g.gx0, y + g.gy0, z + g.gz0, w);
-  return sqrt((double)d2) * g.res;  // Dist (:122-124)
-}
-struct FieldWords {  // the field itself
-  const Geom &g;
-  const vox_t *coc;
-  __device__ inline vox_t operator()(int x, int y, int z) const { return coc[g.idx(x, y, z)]; }
-};
-template <class Words>
-__host__ __device__ inline double vox_distance(const Geom &g, Words &wd, int x, int y, int z) {
-  if (!g.in_grid(x, y, z)) return (double)FIESTA_HIP_INFINITY;  // the reference reads out of bounds here
-  return word_distance(g, wd(x, y, z) & ~kAct, x, y, z);
-}
-__host__ __device__ inline bool pos_in_map(const Geom &g, double px, double py, double pz) {  // PosInMap (:46-61)
-  return !(px < g.lo[0] || py < g.lo[1] || pz < g.lo[2] || px > g.hi[0] || py > g.hi[1] || pz > g.hi[2]);
-}
-template <class Words>
-__host__ __device__ inline double query_dist_pos(const Geom &g, Words &wd, double px, double py, double pz) {  // (:467-475)
-  if (!pos_in_map(g, px, py, pz)) return (double)FIESTA_HIP_UNDEFINED;
-  return vox_distance(g, wd, (int)floor((px - g.org[0]) / g.res) - g.gx0, (int)floor((py - g.org[1]) / g.res) - g.gy0,
-                      (int)floor((pz - g.org[2]) / g.res) - g.gz0);
-}
-// GetDistWithGradTrilinear (src/ESDFMap.cpp:481-540), same operation order in f64 (compiled with -ffp-contract=off so no
-// FMA contraction changes the last bit).  grad: three doubles or null.
-template <class Words>
-__host__ __device__ inline double query_trilinear(const Geom &g, Words &wd, const double *p, double *grad) {
-  if (!pos_in_map(g, p[0], p[1], p[2])) {
-    if (grad) grad[0] = grad[1] = grad[2] = 0;
-    return -1;
-  }
-  int b[3];
-  double f[3];
-  for (int k = 0; k < 3; ++k) {
-    const double pm = p[k] - 0.5 * g.res * 1.0;
-    b[k] = (int)floor((pm - g.org[k]) / g.res);
-    const double c = (b[k] + 0.5) * g.res + g.org[k];
-    f[k] = (p[k] - c) * g.res_inv;
-  }
-  double v[2][2][2];
-  for (int ix = 0; ix < 2; ++ix)
-    for (int iy = 0; iy < 2; ++iy)
-      for (int iz = 0; iz < 2; ++iz)
-        v[ix][iy][iz] = vox_distance(g, wd, b[0] + ix - g.gx0, b[1] + iy - g.gy0, b[2] + iz - g.gz0);
-  const double v00 = (1 - f[0]) * v[0][0][0] + f[0] * v[1][0][0];
-  const double v01 = (1 - f[0]) * v[0][0][1] + f[0] * v[1][0][1];
-  const double v10 = (1 - f[0]) * v[0][1][0] + f[0] * v[1][1][0];
-  const double v11 = (1 - f[0]) * v[0][1][1] + f[0] * v[1][1][1];
-  const double v0 = (1 - f[1]) * v00 + f[1] * v10;
-  const double v1 = (1 - f[1]) * v01 + f[1] * v11;
-  if (grad) {
-    grad[2] = (v1 - v0) * g.res_inv;
-    grad[1] = ((1 - f[2]) * (v10 - v00) + f[2] * (v11 - v01)) * g.res_inv;
-    double gx = (1 - f[2]) * (1 - f[1]) * (v[1][0][0] - v[0][0][0]);
-    gx += (1 - f[2]) * f[1] * (v[1][1][0] - v[0][1][0]);
-    gx += f[2] * (1 - f[1]) * (v[1][0][1] - v[0][0][1]);
-    gx += f[2] * f[1] * (v[1][1][1] - v[0][1][1]);
-    grad[0] = gx * g.res_inv;
-  }
-  return (1 - f[2]) * v0 + f[2] * v1;
-}
-
+// (their arithmetic, over any source of voxel words, and what the planner kernels read of the map: dense_read.hpp)
 __global__ void k_query_dist_vox(Geom g, const vox_t *coc, const int32_t *vox, int64_t n, double *out) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -668,43 +593,6 @@ __global__ void k_query_trilinear(Geom g, const vox_t *coc, const double *pos, i
   dist[i] = query_trilinear(g, wd, p, grad ? gr : nullptr);
   if (grad) grad[3 * i] = gr[0], grad[3 * i + 1] = gr[1], grad[3 * i + 2] = gr[2];
 }
-// the sample evaluator of the path kernels (path_kernels.hpp): k_query_trilinear's arithmetic on the field itself
-struct DensePathEval {
-  Geom g;
-  const vox_t *coc;
-  __device__ double operator()(const double *p, double *grad) const {
-    FieldWords wd{g, coc};
-    return query_trilinear(g, wd, p, grad);
-  }
-};
-// the clearance filter of the frontier kernel (frontier_kernels.hpp): GetDistance(Vector3i) on the field itself, local coordinates
-struct DenseFrontierDist {
-  Geom g;
-  const vox_t *coc;
-  __device__ double operator()(int x, int y, int z) const {
-    FieldWords wd{g, coc};
-    return vox_distance(g, wd, x, y, z);
-  }
-};
-// the map side of the reachability flood (reach_kernels.hpp: k_reach_mask), local array coordinates: 32 voxels of the two bitmaps
-// from any z (two words and a funnel shift when z0 is no multiple of 32; past the array: zero) and the frontier filter's distance
-struct DenseReachSource {
-  Geom g;
-  const uint32_t *obs, *occ;
-  const vox_t *coc;
-  __device__ void row(int x, int y, int z0, uint32_t &o, uint32_t &c) const {
-    const int64_t wi = g.bitword(x, y, z0);
-    const int s = z0 & 31;
-    const uint32_t o0 = obs[wi], c0 = occ[wi];
-    uint32_t o1 = 0, c1 = 0;
-    if (s && (z0 >> 5) + 1 < g.nzw) o1 = obs[wi + 1], c1 = occ[wi + 1];
-    o = reach_funnel(o0, o1, s), c = reach_funnel(c0, c1, s);
-  }
-  __device__ double operator()(int x, int y, int z) const {
-    FieldWords wd{g, coc};
-    return vox_distance(g, wd, x, y, z);
-  }
-};
 // GetOccupancy x2 (src/ESDFMap.cpp:452-465)
 __global__ void k_query_occ_vox(Geom g, const uint32_t *occbits, const int32_t *vox, int64_t n, int32_t *out) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -2401,44 +2289,6 @@ void DenseMap::get_dist_grad(const double *pos, int64_t n, double *dist, double 
   res.back(d, n), res.back(gr, 3 * n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
-// what the planner kernels read of this map (each type next to its kernels), and the path calls' evaluator on the host brick cache
-auto DenseMap::ray_source() const { return DenseRaySource(g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_); }
-auto DenseMap::reach_source() const { return DenseReachSource{g_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, (const vox_t *)coc_}; }
-auto DenseMap::path_eval() const { return DensePathEval{g_, (const vox_t *)coc_}; }
-auto DenseMap::frontier_dist() const { return DenseFrontierDist{g_, (const vox_t *)coc_}; }
-auto DenseMap::host_path_eval() {
-  return [this, wd = HostWords{this}](const double *p, double *grad) mutable { return query_trilinear(g_, wd, p, grad); };
-}
-void DenseMap::path_clearance(const PathClearanceArgs &a) {
-  if (a.n_paths <= 0) return;
-  if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
-    auto ev = host_path_eval();
-    path_host(ev, a.w, a.off, a.n_paths, a.step, a.margin, *a.res);
-    return;
-  }
-  use_device();
-  path_clearance_run(stream_, planner_, path_eval(), a);
-}
-void DenseMap::path_cost(const PathCostArgs &a) {
-  if (a.n_paths <= 0) return;
-  if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
-    auto ev = host_path_eval();
-    path_cost_host(ev, a.w, a.n_wp, a.off, a.n_paths, a.step, a.margin, *a.res);
-    return;
-  }
-  use_device();
-  path_cost_run(stream_, planner_, path_eval(), a);
-}
-void DenseMap::path_refine(const PathRefineArgs &a) {
-  if (a.n_paths <= 0) return;
-  use_device();
-  path_refine_run(stream_, planner_, path_eval(), a);
-}
-void DenseMap::path_timing(const PathTimingArgs &a) {
-  if (a.n_paths <= 0) return;
-  use_device();
-  path_timing_run(stream_, planner_, path_eval(), a);
-}
 void DenseMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n <= 0) return;
   if (n <= kHostQueries) {
@@ -2527,110 +2377,17 @@ int64_t DenseMap::occupied_voxels(int32_t *vox, int64_t cap) {
   return n;
 }
 
-void DenseMap::sync_obsbits() {
-  if (!g_.sharded) return;
-  hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
-  FIESTA_HIP_CHECK(hipGetLastError());
-}
-bool DenseMap::clip_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]) const {
-  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0}, dims[3] = {g_.nx, g_.ny, g_.nz};
-  bool any = true;
-  for (int c = 0; c < 3; ++c) {
-    blo[c] = lo ? std::max<int64_t>((int64_t)lo[c] - g0[c], 0) : 0;
-    bhi[c] = hi ? std::min<int64_t>((int64_t)hi[c] - g0[c], dims[c] - 1) : dims[c] - 1;
-    any = any && blo[c] <= bhi[c];
-  }
-  return any;
-}
-
-// fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp).  dev: vox / mask / n_out_dev are device pointers and the call is
-// only enqueued; else host pointers, and the total is returned.
-int64_t DenseMap::frontier_voxels(const FrontierArgs &a) {
-  use_device();
-  unsigned long long *count = a.dev ? a.n_out_dev : &counters_[C_SCRATCH];
-  if (a.dev)
-    hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, stream_, count, 1);
-  else
-    zero_counter(C_SCRATCH);
-  FIESTA_HIP_CHECK(hipGetLastError());
-  int64_t blo[3], bhi[3];
-  const int64_t nvox = clip_box(a.lo, a.hi, blo, bhi) ? (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * (bhi[2] - blo[2] + 1) : 0;
-  const int64_t cap = std::min(a.capacity, nvox);
-  Staging res{planner_.out, stream_};  // (the host variant's)
-  const auto vox = res.add(a.vox, 3 * cap);
-  const auto mask = res.add(a.mask, cap);
-  if (!a.dev) res.alloc();
-  int32_t *dvox = a.dev ? a.vox : res.dev(vox);
-  uint8_t *dmask = a.dev ? a.mask : res.dev(mask);
-  if (nvox > 0) {
-    sync_obsbits();
-    const FrontierBox b{(int)blo[0], (int)blo[1], (int)blo[2], (int)bhi[0], (int)bhi[1], (int)bhi[2]};
-    const int64_t nwords = (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * ((bhi[2] >> 5) - (blo[2] >> 5) + 1);
-    hipLaunchKernelGGL(k_frontier_dense<DenseFrontierDist>, dim3(grid_for(nwords, 256, 8192)), dim3(256), 0, stream_, g_,
-                       (const uint32_t *)obsbits_, (const uint32_t *)occbits_, b, frontier_dist(), a.min_clearance,
-                       FrontierOut{dvox, dmask, (unsigned long long)cap, count});
+DenseView DenseMap::planner_view(bool reads_bitmaps) {
+  if (reads_bitmaps && g_.sharded) {
+    use_device();
+    hipLaunchKernelGGL(k_obs_rebuild, dim3(grid_for(nbitwords_, 256, 8192)), dim3(256), 0, stream_, g_, (const vox_t *)coc_, obsbits_, nbitwords_);
     FIESTA_HIP_CHECK(hipGetLastError());
   }
-  if (a.dev) return 0;
-  const int64_t n = (int64_t)read_counter(C_SCRATCH);
-  res.back(vox, 3 * std::min(n, cap)), res.back(mask, std::min(n, cap));
-  FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
-  return n;
+  return DenseView{g_, (const vox_t *)coc_, (const uint32_t *)obsbits_, (const uint32_t *)occbits_, {g_.gx0, g_.gy0, g_.gz0}};
 }
-
-// fiesta_hip_reach_field[_dev] (reach_kernels.hpp).  The padding bits of a row's last bitmap word lie past the clipped box and are
-// masked there.
-void DenseMap::reach_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]) {
-  use_device();
-  const bool empty = !clip_box(lo, hi, blo, bhi);
-  if (empty) blo[0] = 1, bhi[0] = 0;
-  if (!empty && (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * (bhi[2] - blo[2] + 1) > kReachMaxVoxels)  // (before anything is launched)
-    throw Error(FIESTA_HIP_ERR_INVALID, "reach: the clipped box holds more than 2^28 voxels");
-  if (!empty) sync_obsbits();
-}
-void DenseMap::reach_field(const ReachArgs &a) {
-  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0};
-  int64_t blo[3], bhi[3];
-  reach_box(a.lo, a.hi, blo, bhi);
-  reach_run(stream_, planner_, reach_source(), blo, bhi, g0, a);
-}
-// fiesta_hip_reach_matrix[_dev] (reach_matrix_kernels.hpp): reach_field's box and source
-void DenseMap::reach_matrix(const ReachMatrixArgs &a) {
-  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0};
-  int64_t blo[3], bhi[3];
-  reach_box(a.lo, a.hi, blo, bhi);
-  reach_matrix_run(stream_, planner_, reach_source(), blo, bhi, g0, a);
-}
-
-// fiesta_hip_free_boxes[_dev] and fiesta_hip_path_corridor[_dev] (corridor_kernels.hpp): the window is the caller's box clipped to the
-// array (both null: the whole array), in map voxel coordinates; reach_field's source
-void DenseMap::corridor(const CorridorArgs &a) {
-  use_device();
-  int64_t blo[3], bhi[3];
-  const bool empty = !clip_box(a.lo, a.hi, blo, bhi);
-  if (!empty) sync_obsbits();
-  const int g0[3] = {g_.gx0, g_.gy0, g_.gz0};
-  CorridorWin w{};
-  for (int c = 0; c < 3; ++c) w.lo[c] = (int)(blo[c] + g0[c]), w.hi[c] = (int)(bhi[c] + g0[c]), w.off[c] = g0[c], w.org[c] = g_.org[c];
-  if (empty) w.lo[0] = 1, w.hi[0] = 0;
-  w.res = g_.res;
-  corridor_run(stream_, planner_, reach_source(), w, a);
-}
-// fiesta_hip_view_coverage[_dev] (view_kernels.hpp).  The ray query's source, the frontier call's distance (local array
-// coordinates: a FREE voxel lies inside the array).
-void DenseMap::view_coverage(const ViewArgs &a) {
-  use_device();
-  sync_obsbits();
-  const ViewSource<DenseRaySource, DenseFrontierDist> vs{ray_source(), frontier_dist(), {g_.gx0, g_.gy0, g_.gz0}};
-  view_coverage_run(stream_, planner_, vs, a);
-}
-
-// fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp)
-void DenseMap::ray_query(const RayArgs &a) {
-  if (a.n <= 0) return;
-  use_device();
-  sync_obsbits();
-  ray_query_run(stream_, planner_, ray_source(), a);
+double DenseMap::HostPathEval::operator()(const double *p, double *grad) {
+  HostWords wd{m};
+  return query_trilinear(m->g_, wd, p, grad);
 }
 
 int64_t DenseMap::point_cloud(int vis_lower_bound, int vis_upper_bound, float *xyz, int64_t cap) {

@@ -49,6 +49,7 @@ enum Counter {
 };
 
 struct LevelEngine;  // level_kernels.hpp
+struct DenseView;    // dense_read.hpp
 
 struct Snapshot {
   DevBuf<vox_t> coc;
@@ -105,24 +106,22 @@ class DenseMap {
   void get_dist_grad(const double *pos, int64_t n, double *dist, double *grad, bool dev);
   void get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out);
   void get_occupancy_pos(const double *pos, int64_t n, int32_t *out);
-  // the planner calls: the arguments are checked and packed by the caller (c_api.hip)
-  void path_clearance(const PathArgs<fiesta_hip_path_result> &a);
-  void path_cost(const PathArgs<fiesta_hip_path_cost_result> &a);
-  void path_refine(const PathRefineArgs &a);
-  void path_timing(const PathTimingArgs &a);
   int64_t host_brick_fetches() const;  // bricks fetched for scalar queries so far (tests, bench)
 
   void download_field(int32_t *d2, int32_t *coc, uint8_t *occ, double *logodds);
   void download_counts(int32_t *num_hit, int32_t *num_miss);
   int64_t occupied_voxels(int32_t *vox, int64_t cap);  // returns the total count (may exceed cap)
-  int64_t frontier_voxels(const FrontierArgs &a);  // returns the total count (host variant; may exceed the capacity)
-  void ray_query(const RayArgs &a);
-  void reach_field(const ReachArgs &a);
-  void reach_matrix(const ReachMatrixArgs &a);
-  void corridor(const CorridorArgs &a);
-  void view_coverage(const ViewArgs &a);
-  // what the calls that read no voxel take of this map (planner.hpp)
-  PlannerCtx planner_ctx() { return PlannerCtx{device_, stream_, planner_, g_.res, g_.org}; }
+  // what the planner calls (planner.hpp) take of this map: its device, stream, scratch, resolution and origin, the C_SCRATCH counter ...
+  PlannerCtx planner_ctx() { return PlannerCtx{device_, stream_, planner_, g_.res, g_.org, &counters_[C_SCRATCH], &h_counters_[C_SCRATCH]}; }
+  // ... and, the calls that read voxels, what can be read of it (dense_read.hpp).  reads_bitmaps: the call reads obsbits_ (all but the four
+  // path calls).  A shard's ghost cells are written by the halo exchange, which does not keep obsbits_: such a call rebuilds it from the field
+  DenseView planner_view(bool reads_bitmaps);
+  // the path calls' evaluator on the host brick cache: query_trilinear over HostWords
+  struct HostPathEval {
+    DenseMap *m;
+    double operator()(const double *p, double *grad);
+  };
+  HostPathEval host_path_eval() { return HostPathEval{this}; }
   int64_t count_no_obstacle();
   void slice_distances(int z_vox, double *out);        // nx * ny doubles, x-major
   // GetPointCloud / GetSliceMarker as arrays; both return the total count (may exceed cap), order unspecified
@@ -201,18 +200,6 @@ class DenseMap {
   void reset_stats_counters(bool lists = false, bool queues = false);
   void enable_distance_tracking();
   void collect_stats(fiesta_hip_stats *st);
-  // a shard's ghost cells are written by the halo exchange, which does not keep obsbits_: bring the bitmap in line with the field
-  // (nothing to do on an unsharded map)
-  void sync_obsbits();
-  // a caller's box (null: everything) in local array coordinates, intersected with the array; false: nothing is left
-  bool clip_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]) const;
-  void reach_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]);  // the reach calls' clipped box, checked; empty: blo[0] > bhi[0]
-  // what the planner kernels read of this map; the path calls' evaluator on the host brick cache (dense_map.hip has the types)
-  auto ray_source() const;
-  auto reach_source() const;
-  auto path_eval() const;
-  auto frontier_dist() const;
-  auto host_path_eval();
 
   Geom g_;
   ProbParams pp_;

@@ -23,7 +23,7 @@
 #include "wave_ops.hpp"
 
 namespace fiesta {
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 struct FrontierBox {  // inclusive; dense maps: local array coordinates, already clipped; hash-block maps: map voxel coordinates
   int x0, y0, z0, x1, y1, z1;

@@ -8,6 +8,7 @@
 //   GetDistance / GetDistWithGradTrilinear / GetOccupancy :452-540           -> k_h_query_*
 #include "hash_map.hpp"
 #include "checkpoint.hpp"
+#include "hash_read.hpp"
 
 #include <vector>
 
@@ -18,51 +19,22 @@
 #include <cstring>
 
 #include "level_kernels.hpp"
-#include "path_cost_kernels.hpp"
-#include "refine_kernels.hpp"
-#include "timing_kernels.hpp"
-#include "frontier_kernels.hpp"
-#include "ray_query_kernels.hpp"
-#include "reach_kernels.hpp"
-#include "reach_matrix_kernels.hpp"
-#include "corridor_kernels.hpp"
-#include "view_kernels.hpp"
-#include "path_kernels.hpp"
 #include "relax_kernels.hpp"
 
 namespace fiesta {
 
 namespace {
-constexpr int kWin = HashMap::kWin, kHalf = HashMap::kHalf;
-constexpr int kNTY = HashMap::kNTY, kNTZ = HashMap::kNTZ, kNTiles = HashMap::kNTiles;
-constexpr int kPageVox = HashMap::kPageVox;
+constexpr int kHalf = HashMap::kHalf;
+constexpr int kNTiles = HashMap::kNTiles;
 constexpr int C_OUTSIDE = C_REMOTE_DEL;  // (dense shards only use that slot) a batch held a voxel outside the window
-// a caller's voxel coordinate or range bound clamped to +-2^30 (map coordinates lie well inside): kernels' differences stay in range
-inline int clamp30(int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, -(1ll << 30)), 1ll << 30); }
 
-__device__ inline int tile_id(int x, int y, int z) { return ((x >> 4) * kNTY + (y >> 4)) * kNTZ + (z >> 5); }
-__device__ inline bool in_win(int x, int y, int z) {
-  return (unsigned)x < (unsigned)kWin && (unsigned)y < (unsigned)kWin && (unsigned)z < (unsigned)kWin;
-}
-// pool address of window voxel (x,y,z); -1 if its page is not allocated
-__device__ inline int64_t vaddr(const int32_t *dir, int x, int y, int z) {
-  const int32_t p = dir[tile_id(x, y, z)];
-  return p < 0 ? -1 : (int64_t)p * kPageVox + (((x & 15) * 16 + (y & 15)) * 32 + (z & 31));
-}
 __device__ inline void vcoords(const int32_t *page_tile, uint32_t addr, int &x, int &y, int &z) {
   const int t = page_tile[addr / kPageVox], off = addr % kPageVox;
   x = (t / (kNTY * kNTZ)) * 16 + (off >> 9);
   y = ((t / kNTZ) % kNTY) * 16 + ((off >> 5) & 15);
   z = (t % kNTZ) * 32 + (off & 31);
 }
-__device__ inline bool hbit(const uint32_t *bits, int64_t addr) { return (bits[addr >> 5] >> (addr & 31)) & 1u; }
-// The window MOVES (HashMap::ensure_window): window voxel (0,0,0) is map voxel (g.gx0, g.gy0, g.gz0), a multiple of the
-// tile size.  Closest-obstacle ids are therefore stored as MAP coordinates modulo 1024 and decoded relative to the voxel
-// that holds them (common.hpp: coc_offset with wrap; reach 512 voxels) -- they stay valid when the window moves.
-__device__ inline vox_t h_pack(const Geom &g, int x, int y, int z) { return pack_coc(x + g.gx0, y + g.gy0, z + g.gz0); }
-__device__ inline int32_t h_dist2(const Geom &g, int x, int y, int z, vox_t w) {
-  return dist2(1, x + g.gx0, y + g.gy0, z + g.gz0, w);
-}
+__device__ inline vox_t h_pack(const Geom &g, int x, int y, int z) { return pack_coc(x + g.gx0, y + g.gy0, z + g.gz0); }  // (as h_dist2: hash_read.hpp)
 // window coordinates of the obstacle named by the id held at window voxel (x, y, z) (may lie outside the window)
 __device__ inline void h_obstacle(const Geom &g, int x, int y, int z, vox_t w, int &cx, int &cy, int &cz) {
   int dx, dy, dz;
@@ -380,39 +352,7 @@ __global__ __launch_bounds__(256) void k_h_invalidate(Geom g, const int32_t *dir
   }
 }
 
-// ---- queries (src/ESDFMap.cpp:452-540); an unallocated voxel reads like a freshly allocated one ----
-// The reference's hash map answers for ANY voxel it ever allocated (:732-765).  Inside the window a lookup is one load of
-// the dense directory; outside it -- pages that are parked -- a query goes through the MAP-WIDE page table: every page's
-// tile in map coordinates as a sorted 64-bit key (a few thousand entries: a binary search), so that a planner may ask for
-// a goal far from the sensor.  A parked page answers with the field it held when the window left it.
-__host__ __device__ inline unsigned long long tile_key(int tx, int ty, int tz) {
-  return ((unsigned long long)(uint32_t)(tx + (1 << 20)) << 42) | ((unsigned long long)(uint32_t)(ty + (1 << 20)) << 21) |
-         (unsigned long long)(uint32_t)(tz + (1 << 20));
-}
-// pool address of WINDOW voxel (x, y, z), which may lie outside the window; -1: no page anywhere holds it
-__device__ inline int64_t h_lookup(const Geom &g, const int32_t *dir, const PageTable &tab, int x, int y, int z) {
-  if (in_win(x, y, z)) return vaddr(dir, x, y, z);
-  const int vx = x + g.gx0, vy = y + g.gy0, vz = z + g.gz0;  // map voxel; the window origin is a whole number of tiles
-  const unsigned long long key = tile_key(vx >> 4, vy >> 4, vz >> 5);
-  int lo = 0, hi = tab.n - 1;
-  while (lo <= hi) {
-    const int mid = (lo + hi) >> 1;
-    const unsigned long long k = tab.keys[mid];
-    if (k == key) return (int64_t)tab.pages[mid] * kPageVox + (((vx & 15) * 16 + (vy & 15)) * 32 + (vz & 31));
-    if (k < key)
-      lo = mid + 1;
-    else
-      hi = mid - 1;
-  }
-  return -1;
-}
-__device__ inline double h_distance(const Geom &g, const int32_t *dir, const PageTable &tab, const vox_t *coc, int x, int y, int z) {
-  const int64_t a = h_lookup(g, dir, tab, x, y, z);
-  if (a < 0) return (double)FIESTA_HIP_INFINITY;
-  const vox_t w = coc[a] & ~kAct;
-  if (w & kNoCoc) return (double)FIESTA_HIP_INFINITY;
-  return sqrt((double)h_dist2(g, x, y, z, w)) * g.res;
-}
+// ---- queries (src/ESDFMap.cpp:452-540): the lookup, their arithmetic and what the planner kernels read of the map are hash_read.hpp ----
 __global__ void k_h_query_dist(Geom g, const int32_t *dir, PageTable tab, const vox_t *coc, const int32_t *vox, const double *pos,
                                int64_t n, double *out) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -442,41 +382,6 @@ __global__ void k_h_query_occ(Geom g, const int32_t *dir, PageTable tab, const u
   const int64_t a = h_lookup(g, dir, tab, x, y, z);
   out[i] = a < 0 ? 0 : (int)hbit(occbits, a);
 }
-// GetDistWithGradTrilinear (src/ESDFMap.cpp:481-540), f64 in the reference's operation order -- written once over a source of
-// corner distances D(map voxel x, y, z), compiled for the device (the batch kernel) and for the host (scalar calls from the brick
-// cache): the two are bit-equal
-template <class D>
-__host__ __device__ inline double h_trilinear(const Geom &g, D &&corner, const double *p, double *grad) {
-  int b[3];
-  double f[3];
-  for (int k = 0; k < 3; ++k) {
-    const double pm = p[k] - 0.5 * g.res * 1.0;
-    b[k] = (int)floor((pm - g.org[k]) / g.res);
-    const double c = (b[k] + 0.5) * g.res + g.org[k];
-    f[k] = (p[k] - c) * g.res_inv;
-  }
-  double v[2][2][2];
-  for (int ix = 0; ix < 2; ++ix)
-    for (int iy = 0; iy < 2; ++iy)
-      for (int iz = 0; iz < 2; ++iz) v[ix][iy][iz] = corner(b[0] + ix, b[1] + iy, b[2] + iz);
-  const double v00 = (1 - f[0]) * v[0][0][0] + f[0] * v[1][0][0];
-  const double v01 = (1 - f[0]) * v[0][0][1] + f[0] * v[1][0][1];
-  const double v10 = (1 - f[0]) * v[0][1][0] + f[0] * v[1][1][0];
-  const double v11 = (1 - f[0]) * v[0][1][1] + f[0] * v[1][1][1];
-  const double v0 = (1 - f[1]) * v00 + f[1] * v10;
-  const double v1 = (1 - f[1]) * v01 + f[1] * v11;
-  const double d = (1 - f[2]) * v0 + f[2] * v1;
-  if (grad) {
-    grad[2] = (v1 - v0) * g.res_inv;
-    grad[1] = ((1 - f[2]) * (v10 - v00) + f[2] * (v11 - v01)) * g.res_inv;
-    double gx = (1 - f[2]) * (1 - f[1]) * (v[1][0][0] - v[0][0][0]);
-    gx += (1 - f[2]) * f[1] * (v[1][1][0] - v[0][1][0]);
-    gx += f[2] * (1 - f[1]) * (v[1][0][1] - v[0][0][1]);
-    gx += f[2] * f[1] * (v[1][1][1] - v[0][1][1]);
-    grad[0] = gx * g.res_inv;
-  }
-  return d;
-}
 __global__ void k_h_query_trilinear(Geom g, const int32_t *dir, PageTable tab, const vox_t *coc, const double *pos, int64_t n, double *dist,
                                     double *grad) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -485,84 +390,6 @@ __global__ void k_h_query_trilinear(Geom g, const int32_t *dir, PageTable tab, c
   auto corner = [&](int vx, int vy, int vz) { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); };
   dist[i] = h_trilinear(g, corner, p, grad ? grad + 3 * i : nullptr);
 }
-// the sample evaluator of the path kernels (path_kernels.hpp): k_h_query_trilinear's arithmetic over the same page-table corners
-struct HashPathEval {
-  Geom g;
-  const int32_t *dir;
-  PageTable tab;
-  const vox_t *coc;
-  __device__ double operator()(const double *p, double *grad) const {
-    auto corner = [&](int vx, int vy, int vz) { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); };
-    return h_trilinear(g, corner, p, grad);
-  }
-};
-// the page source of the frontier kernel (frontier_kernels.hpp), MAP voxel coordinates: the queries' lookup and GetDistance(Vector3i)
-struct HashFrontierPages {
-  Geom g;
-  const int32_t *dir;
-  PageTable tab;
-  const vox_t *coc;
-  __device__ int64_t addr(int vx, int vy, int vz) const { return h_lookup(g, dir, tab, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
-  __device__ double operator()(int vx, int vy, int vz) const { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
-};
-// the map side of the reachability flood (reach_kernels.hpp: k_reach_mask), MAP voxel coordinates: 32 voxels from any z are the
-// rows of one or two tiles, each found by the queries' map-wide lookup (parked pages answer; no page: all unknown), its observed
-// bits gathered from the page's field words; the frontier filter's distance is GetDistance(Vector3i)
-struct HashReachSource {
-  Geom g;
-  const int32_t *dir;
-  PageTable tab;
-  const vox_t *coc;
-  const uint32_t *occbits;
-  __device__ void tile_row(int vx, int vy, int vz, uint32_t &o, uint32_t &c) const {  // vz: a multiple of 32
-    constexpr int kFar = 1 << 24;  // (pages lie within +-2^24 voxels of the map origin: tile_key)
-    o = c = 0u;
-    if (vx < -kFar || vx >= kFar || vy < -kFar || vy >= kFar || vz < -kFar || vz >= kFar) return;
-    const int64_t a = h_lookup(g, dir, tab, vx - g.gx0, vy - g.gy0, vz - g.gz0);
-    if (a < 0) return;
-    for (int k = 0; k < 32; ++k) o |= (uint32_t)(coc[a + k] != kUnobserved) << k;
-    c = occbits[a >> 5];
-  }
-  __device__ void row(int vx, int vy, int vz0, uint32_t &o, uint32_t &c) const {
-    const int s = vz0 & 31;
-    uint32_t o0, c0, o1 = 0, c1 = 0;
-    tile_row(vx, vy, vz0 - s, o0, c0);
-    if (s) tile_row(vx, vy, vz0 - s + 32, o1, c1);
-    o = reach_funnel(o0, o1, s), c = reach_funnel(c0, c1, s);
-  }
-  __device__ double operator()(int vx, int vy, int vz) const { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
-};
-// the voxel source of the ray query (ray_query_kernels.hpp): the queries' lookup once per TILE -- the page address of the tile the
-// ray is in stays in registers (-1: no page, every voxel of it unknown) -- then the voxel's field word and, if it is observed, the
-// occupancy word of its row
-struct HashRaySource {
-  RayGeom g;
-  Geom win;  // the window, for the lookup
-  const int32_t *dir;
-  PageTable tab;
-  const vox_t *coc;
-  const uint32_t *occbits;
-  struct Cache {
-    int tx, ty, tz;
-    int64_t base, ow;
-    uint32_t occ;
-  };
-  __device__ static Cache fresh() { return Cache{INT32_MIN, 0, 0, -1, -1, 0u}; }
-  __device__ int classify(const int *, const int *v, Cache &c) const {
-    constexpr int kFar = 1 << 28;  // (pages lie within +-2^24 voxels of the map origin: tile_key)
-    if (v[0] < -kFar || v[0] > kFar || v[1] < -kFar || v[1] > kFar || v[2] < -kFar || v[2] > kFar) return FIESTA_HIP_RAY_UNKNOWN;
-    const int tx = v[0] >> 4, ty = v[1] >> 4, tz = v[2] >> 5;
-    if (tx != c.tx || ty != c.ty || tz != c.tz) {
-      c.tx = tx, c.ty = ty, c.tz = tz;
-      c.base = h_lookup(win, dir, tab, tx * 16 - win.gx0, ty * 16 - win.gy0, tz * 32 - win.gz0);  // (the tile's first voxel: offset 0 of its page)
-    }
-    if (c.base < 0) return FIESTA_HIP_RAY_UNKNOWN;
-    const int64_t a = c.base + (((v[0] & 15) * 16 + (v[1] & 15)) * 32 + (v[2] & 31));
-    if (coc[a] == kUnobserved) return FIESTA_HIP_RAY_UNKNOWN;
-    if ((a >> 5) != c.ow) c.ow = a >> 5, c.occ = occbits[a >> 5];
-    return ((c.occ >> (a & 31)) & 1u) ? FIESTA_HIP_RAY_OCCUPIED : FIESTA_HIP_RAY_FREE;
-  }
-};
 // a brick of the host-side cache: the 16^3 distances and occupancy bits of map brick (bx, by, bz), straight into pinned memory
 __global__ __launch_bounds__(256) void k_h_fetch_brick(Geom g, const int32_t *dir, PageTable tab, const vox_t *coc, const uint32_t *occbits, int bx,
                                                        int by, int bz, double *dst) {
@@ -1355,6 +1182,15 @@ PageTable HashMap::page_table() {
   }
   return PageTable{ptab_keys_.p, ptab_pages_.p, (int)ptab_pages_built_};
 }
+HashView HashMap::planner_view(bool) {
+  use_device();
+  const PageTable tab = page_table();  // (before the call enqueues anything: a rebuild synchronises)
+  return HashView{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p, (const int32_t *)page_gtile_.p, npages_, {0, 0, 0}};
+}
+double HashMap::HostPathEval::operator()(const double *p, double *grad) {
+  auto corner = [&](int vx, int vy, int vz) { return m->host_distance(vx, vy, vz); };
+  return h_trilinear(m->g_, corner, p, grad);
+}
 
 // ---- host-side brick cache of the scalar queries (the dense map's, dense_map.hip: HostBricks, for the paged map) -----------
 // The reference's GetDistance is a hash lookup + an array read (src/ESDFMap.cpp:467-479, 732-765); a planner calls it one position
@@ -1454,52 +1290,6 @@ void HashMap::get_dist_grad(const double *pos, int64_t n, double *dist, double *
   res.back(d, n), res.back(gr, 3 * n);
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
 }
-// what the planner kernels read of this map, over a page table already fetched (each type next to its kernels), and the path
-// calls' evaluator on the host brick cache
-auto HashMap::ray_source(const PageTable &tab) const {
-  return HashRaySource{ray_geom(g_), g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p};
-}
-auto HashMap::reach_source(const PageTable &tab) const {
-  return HashReachSource{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p};
-}
-auto HashMap::path_eval(const PageTable &tab) const { return HashPathEval{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}; }
-auto HashMap::frontier_pages(const PageTable &tab) const { return HashFrontierPages{g_, (const int32_t *)dir_, tab, (const vox_t *)coc_.p}; }
-auto HashMap::host_path_eval() {
-  return [this](const double *p, double *grad) {
-    auto corner = [&](int vx, int vy, int vz) { return host_distance(vx, vy, vz); };
-    return h_trilinear(g_, corner, p, grad);
-  };
-}
-void HashMap::path_clearance(const PathClearanceArgs &a) {
-  if (a.n_paths <= 0) return;
-  if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
-    auto ev = host_path_eval();
-    path_host(ev, a.w, a.off, a.n_paths, a.step, a.margin, *a.res);
-    return;
-  }
-  use_device();
-  path_clearance_run(stream_, planner_, path_eval(page_table()), a);
-}
-void HashMap::path_cost(const PathCostArgs &a) {
-  if (a.n_paths <= 0) return;
-  if (!a.dev && path_host_samples(a.w, a.off, a.n_paths, a.step, kHostPathSamples) <= kHostPathSamples) {  // the host brick cache
-    auto ev = host_path_eval();
-    path_cost_host(ev, a.w, a.n_wp, a.off, a.n_paths, a.step, a.margin, *a.res);
-    return;
-  }
-  use_device();
-  path_cost_run(stream_, planner_, path_eval(page_table()), a);
-}
-void HashMap::path_refine(const PathRefineArgs &a) {
-  if (a.n_paths <= 0) return;
-  use_device();
-  path_refine_run(stream_, planner_, path_eval(page_table()), a);
-}
-void HashMap::path_timing(const PathTimingArgs &a) {
-  if (a.n_paths <= 0) return;
-  use_device();
-  path_timing_run(stream_, planner_, path_eval(page_table()), a);
-}
 void HashMap::get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out) {
   if (n > 0 && n <= kHostQueries) {
     for (int64_t i = 0; i < n; ++i) out[i] = host_occ(vox[3 * i], vox[3 * i + 1], vox[3 * i + 2]);
@@ -1568,99 +1358,6 @@ int64_t HashMap::point_cloud(int vis_lower_bound, int vis_upper_bound, float *xy
   res.back(pts, 3 * std::min(n, cap));
   FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
   return n;
-}
-
-// fiesta_hip_get_frontier_voxels[_dev] (frontier_kernels.hpp).  Every page, resident or parked; a null box is the whole map.
-int64_t HashMap::frontier_voxels(const FrontierArgs &a) {
-  use_device();
-  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
-  unsigned long long *count = a.dev ? a.n_out_dev : &counters_[C_SCRATCH];
-  hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, stream_, count, 1);
-  FIESTA_HIP_CHECK(hipGetLastError());
-  // (page coordinates stay within +-2^25: clamping the box there changes nothing and keeps the kernel's differences in range)
-  FrontierBox b{clamp30(INT32_MIN), clamp30(INT32_MIN), clamp30(INT32_MIN), clamp30(INT32_MAX), clamp30(INT32_MAX), clamp30(INT32_MAX)};
-  if (a.lo) b = FrontierBox{clamp30(a.lo[0]), clamp30(a.lo[1]), clamp30(a.lo[2]), clamp30(a.hi[0]), clamp30(a.hi[1]), clamp30(a.hi[2])};
-  const bool empty = b.x0 > b.x1 || b.y0 > b.y1 || b.z0 > b.z1 || npages_ == 0;
-  const int64_t cap = std::min<int64_t>(a.capacity, npages_ * kPageVox);
-  Staging res{planner_.out, stream_};  // (the host variant's)
-  const auto vox = res.add(a.vox, 3 * cap);
-  const auto mask = res.add(a.mask, cap);
-  if (!a.dev) res.alloc();
-  int32_t *dvox = a.dev ? a.vox : res.dev(vox);
-  uint8_t *dmask = a.dev ? a.mask : res.dev(mask);
-  if (!empty) {
-    hipLaunchKernelGGL(k_frontier_hash<HashFrontierPages>, dim3(grid_for(npages_, 1, 8192)), dim3(256), 0, stream_,
-                       (const int32_t *)page_gtile_.p, npages_, (const vox_t *)coc_.p, (const uint32_t *)occbits_.p, b,
-                       frontier_pages(tab), a.min_clearance, FrontierOut{dvox, dmask, (unsigned long long)cap, count});
-    FIESTA_HIP_CHECK(hipGetLastError());
-  }
-  if (a.dev) return 0;
-  const int64_t n = (int64_t)read_counter(C_SCRATCH);
-  res.back(vox, 3 * std::min(n, cap)), res.back(mask, std::min(n, cap));
-  FIESTA_HIP_CHECK(hipStreamSynchronize(stream_));
-  return n;
-}
-
-// fiesta_hip_reach_field[_dev] (reach_kernels.hpp).  The map has no outside: the box is taken as given (clamped like the frontier
-// call's); every page answers, resident or parked, and a tile without a page is unknown.
-void HashMap::reach_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]) {
-  use_device();
-  bool empty = false;
-  for (int k = 0; k < 3; ++k) blo[k] = clamp30(lo[k]), bhi[k] = clamp30(hi[k]), empty = empty || blo[k] > bhi[k];
-  if (empty) blo[0] = 1, bhi[0] = 0;
-  if (!empty) {  // (before anything is launched; each extent is below 2^32)
-    const int64_t ex = bhi[0] - blo[0] + 1, ey = bhi[1] - blo[1] + 1, ez = bhi[2] - blo[2] + 1;
-    if (ex > kReachMaxVoxels || ey > kReachMaxVoxels || ex * ey > kReachMaxVoxels || ex * ey * ez > kReachMaxVoxels)
-      throw Error(FIESTA_HIP_ERR_INVALID, "reach: the box holds more than 2^28 voxels");
-  }
-}
-void HashMap::reach_field(const ReachArgs &a) {
-  int64_t blo[3], bhi[3];
-  reach_box(a.lo, a.hi, blo, bhi);
-  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
-  const int off[3] = {0, 0, 0};
-  reach_run(stream_, planner_, reach_source(tab), blo, bhi, off, a);
-}
-// fiesta_hip_reach_matrix[_dev] (reach_matrix_kernels.hpp): reach_field's box and source; the page table is rebuilt once per call
-void HashMap::reach_matrix(const ReachMatrixArgs &a) {
-  int64_t blo[3], bhi[3];
-  reach_box(a.lo, a.hi, blo, bhi);
-  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
-  const int off[3] = {0, 0, 0};
-  reach_matrix_run(stream_, planner_, reach_source(tab), blo, bhi, off, a);
-}
-
-// fiesta_hip_free_boxes[_dev] and fiesta_hip_path_corridor[_dev] (corridor_kernels.hpp): the map has no outside -- the window is the
-// caller's box clamped to +-2^30, or all of that range -- every page answers, resident or parked; reach_field's source
-void HashMap::corridor(const CorridorArgs &a) {
-  use_device();
-  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
-  CorridorWin w{};
-  bool empty = false;
-  for (int c = 0; c < 3; ++c) {
-    w.lo[c] = a.lo ? clamp30(a.lo[c]) : clamp30(INT32_MIN), w.hi[c] = a.hi ? clamp30(a.hi[c]) : clamp30(INT32_MAX);
-    w.off[c] = 0, w.org[c] = g_.org[c];
-    empty = empty || w.lo[c] > w.hi[c];
-  }
-  if (empty) w.lo[0] = 1, w.hi[0] = 0;
-  w.res = g_.res;
-  corridor_run(stream_, planner_, reach_source(tab), w, a);
-}
-// fiesta_hip_view_coverage[_dev] (view_kernels.hpp).  The ray query's source, the frontier call's distance (map voxel
-// coordinates).  Every page answers, resident or parked.
-void HashMap::view_coverage(const ViewArgs &a) {
-  use_device();
-  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
-  const ViewSource<HashRaySource, HashFrontierPages> vs{ray_source(tab), frontier_pages(tab), {0, 0, 0}};
-  view_coverage_run(stream_, planner_, vs, a);
-}
-
-// fiesta_hip_ray_query[_dev] (ray_query_kernels.hpp).  Every page answers, resident or parked.
-void HashMap::ray_query(const RayArgs &a) {
-  if (a.n <= 0) return;
-  use_device();
-  const PageTable tab = page_table();  // (before anything is enqueued: a rebuild synchronises)
-  ray_query_run(stream_, planner_, ray_source(tab), a);
 }
 
 int64_t HashMap::slice_marker(int slice, double max_dist, double *xyz, float *rgba, int64_t cap) {

@@ -26,12 +26,8 @@
 
 namespace fiesta {
 
-// every page's tile in MAP coordinates, sorted: what a query outside the window searches (hash_map.hip: h_lookup)
-struct PageTable {
-  const unsigned long long *keys;  // (tx + 2^20) << 42 | (ty + 2^20) << 21 | (tz + 2^20)
-  const int32_t *pages;
-  int n;
-};
+struct PageTable;  // the map-wide page table of the queries, and the planner calls' view of a map: hash_read.hpp
+struct HashView;
 
 class HashMap {
  public:
@@ -78,18 +74,15 @@ class HashMap {
   void get_dist_grad(const double *pos, int64_t n, double *dist, double *grad);
   void get_occupancy_vox(const int32_t *vox, int64_t n, int32_t *out);
   void get_occupancy_pos(const double *pos, int64_t n, int32_t *out);
-  // the planner calls, as DenseMap's (reach_field: lo / hi are not null here)
-  void path_clearance(const PathArgs<fiesta_hip_path_result> &a);
-  void path_cost(const PathArgs<fiesta_hip_path_cost_result> &a);
-  void path_refine(const PathRefineArgs &a);
-  void path_timing(const PathTimingArgs &a);
-  int64_t frontier_voxels(const FrontierArgs &a);
-  void ray_query(const RayArgs &a);
-  void reach_field(const ReachArgs &a);
-  void reach_matrix(const ReachMatrixArgs &a);
-  void corridor(const CorridorArgs &a);
-  void view_coverage(const ViewArgs &a);
-  PlannerCtx planner_ctx() { return PlannerCtx{device_, stream_, planner_, g_.res, g_.org}; }  // as DenseMap's
+  // as DenseMap's; planner_view() fetches the page table before the call enqueues anything (a rebuild synchronises), whatever reads_bitmaps
+  PlannerCtx planner_ctx() { return PlannerCtx{device_, stream_, planner_, g_.res, g_.org, &counters_[C_SCRATCH], &h_counters_[C_SCRATCH]}; }
+  HashView planner_view(bool reads_bitmaps);
+  // the path calls' evaluator on the host brick cache: h_trilinear over host_distance
+  struct HostPathEval {
+    HashMap *m;
+    double operator()(const double *p, double *grad);
+  };
+  HostPathEval host_path_eval() { return HostPathEval{this}; }
   // every voxel of every allocated page, page order: vox (map voxel coordinates), d2, coc, occ; returns the count
   int64_t download(int32_t *vox, int32_t *d2, int32_t *coc, uint8_t *occ);
   void download_counts(int32_t *num_hit, int32_t *num_miss);  // same order as download()
@@ -113,13 +106,6 @@ class HashMap {
   void run_rounds(fiesta_hip_stats *st, uint32_t first_count);
   bool run_levels(fiesta_hip_stats *st, unsigned long long ni, unsigned long long nd);  // false: the rounds finish
   PageTable page_table();  // the map-wide page table of the query kernels (hash_map.hip)
-  void reach_box(const int32_t *lo, const int32_t *hi, int64_t blo[3], int64_t bhi[3]);  // the reach calls' clamped box, checked; empty: blo[0] > bhi[0]
-  // what the planner kernels read of this map, over a page table already fetched; the path calls' evaluator on the host brick cache
-  auto ray_source(const PageTable &tab) const;
-  auto reach_source(const PageTable &tab) const;
-  auto path_eval(const PageTable &tab) const;
-  auto frontier_pages(const PageTable &tab) const;
-  auto host_path_eval();
   // scalar queries (n <= kHostQueries positions per call, host pointers): a host-side cache of 16^3-voxel bricks of DISTANCES (f64,
   // as the query kernels compute them) and occupancy bits, keyed by map brick coordinates, fetched on first touch (r06: the dense
   // map's HostBricks for the paged map).  field_epoch_ is bumped by everything that may change the field or what a lookup finds.

@@ -25,7 +25,7 @@
 #include "path_kernels.hpp"
 
 namespace fiesta {
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int kCostSegBlocks = 512;  // grid of k_cost_segments (a grid-stride loop over the piece records)
 

@@ -35,7 +35,7 @@
 #include "wave_ops.hpp"
 
 namespace fiesta {
-namespace {  // (this header is included by three translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr long long kPathPiece = 1024;        // samples per piece at least (16 per lane of the wave that evaluates it)
 constexpr int64_t kPathRecords = 1 << 18;     // piece records per call: a path gets at most max(1, kPathRecords / n_paths) pieces

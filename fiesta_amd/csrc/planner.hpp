@@ -1,8 +1,8 @@
-// fiesta_amd/csrc/planner.hpp -- what a map keeps for the planner calls, and the calls that read no voxel.
+// fiesta_amd/csrc/planner.hpp -- what a map keeps for the planner calls, and the calls themselves.
 //
-// Both stores own one PlannerScratch and hand it to the planner kernel headers.  The calls that read the store through a source or
-// evaluator type are members of the stores; the six that need nothing of a map but its device, stream, scratch, resolution and
-// origin are the free functions at the end of this header, defined once in planner.hip.
+// Both stores own one PlannerScratch.  The sixteen calls are the free functions at the end of this header, defined once in
+// planner.hip, the only unit that includes the planner kernel headers: six need nothing of a map but its planner_ctx(); ten also
+// read voxels, through the store's planner_view() (dense_read.hpp: DenseView, hash_read.hpp: HashView).
 #pragma once
 #include <algorithm>
 
@@ -10,6 +10,9 @@
 #include "common.hpp"
 
 namespace fiesta {
+
+// the reach calls' limit on the voxels of their clipped box: keeps every cost below 2^31 (5 * 2^28) and bounds the scratch
+constexpr int64_t kReachMaxVoxels = 1ll << 28;
 
 // scratch of fiesta_hip_reach_field (reach_kernels.hpp), owned by a map: the box's traversability bitmap, tile flags and lists of
 // both round parities, the counters, and a cost field for calls that pass none; allocated on first use, freed with the map.
@@ -143,17 +146,45 @@ struct ClusterArgs;
 struct SplitArgs;
 struct ViewArgs;
 
-// ---- the calls that read no voxel (planner.hip) -----------------------------------------------------------------------------------
-// what such a call takes of a map, either store's planner_ctx(): its device and stream, its scratch, its resolution and origin
+// ---- the planner calls (planner.hip) ------------------------------------------------------------------------------------------------
+// what every call takes of a map, either store's planner_ctx(): its device and stream, its scratch, its resolution and origin, and
+// a counter of the map's (the C_SCRATCH slot) with its pinned host mirror, for a host variant's total
 struct PlannerCtx {
   int device;
   hipStream_t stream;
   PlannerScratch &S;
   double res;
   const double *org;
+  unsigned long long *counter, *counter_host;
 };
-// fiesta_hip_reach_paths[_dev], fiesta_hip_leg_paths[_dev] (the batch the last reach_matrix call retained), fiesta_hip_cluster_voxels[_dev]
-// and fiesta_hip_split_clusters[_dev]: nothing of the map is read but its resolution and origin
+// The calls that read voxels.  View: DenseView (dense_read.hpp) or HashView (hash_read.hpp), the store's planner_view(), which prepares
+// what the kernels read; planner.hip instantiates each call for both.  fiesta_hip_path_clearance[_dev] and fiesta_hip_path_cost[_dev] (host:
+// the store's host_path_eval(), which answers a small host batch from its brick cache), fiesta_hip_path_refine[_dev], fiesta_hip_path_timing[_dev]
+template <class View, class HostEval>
+void path_clearance(const PlannerCtx &ctx, const View &v, HostEval host, const PathArgs<fiesta_hip_path_result> &a);
+template <class View, class HostEval>
+void path_cost(const PlannerCtx &ctx, const View &v, HostEval host, const PathArgs<fiesta_hip_path_cost_result> &a);
+template <class View>
+void path_refine(const PlannerCtx &ctx, const View &v, const PathRefineArgs &a);
+template <class View>
+void path_timing(const PlannerCtx &ctx, const View &v, const PathTimingArgs &a);
+// fiesta_hip_get_frontier_voxels[_dev]: returns the host variant's total (which may exceed the capacity)
+template <class View>
+int64_t frontier_voxels(const PlannerCtx &ctx, const View &v, const FrontierArgs &a);
+// fiesta_hip_ray_query[_dev], fiesta_hip_reach_field[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_free_boxes[_dev] and
+// fiesta_hip_path_corridor[_dev], fiesta_hip_view_coverage[_dev]
+template <class View>
+void ray_query(const PlannerCtx &ctx, const View &v, const RayArgs &a);
+template <class View>
+void reach_field(const PlannerCtx &ctx, const View &v, const ReachArgs &a);
+template <class View>
+void reach_matrix(const PlannerCtx &ctx, const View &v, const ReachMatrixArgs &a);
+template <class View>
+void corridor(const PlannerCtx &ctx, const View &v, const CorridorArgs &a);
+template <class View>
+void view_coverage(const PlannerCtx &ctx, const View &v, const ViewArgs &a);
+// The calls that read no voxel.  fiesta_hip_reach_paths[_dev], fiesta_hip_leg_paths[_dev] (the batch the last reach_matrix call
+// retained), fiesta_hip_cluster_voxels[_dev] and fiesta_hip_split_clusters[_dev]: nothing of the map is read but its resolution and origin
 void reach_paths(const PlannerCtx &ctx, const ReachPathArgs &a);
 void leg_paths(const PlannerCtx &ctx, const LegPathArgs &a);
 void cluster_voxels(const PlannerCtx &ctx, const ClusterArgs &a);
@@ -161,8 +192,6 @@ void split_clusters(const PlannerCtx &ctx, const SplitArgs &a);
 // fiesta_hip_corridor_bounds[_dev] and fiesta_hip_site_tour[_dev]: nothing of the map is read at all
 void corridor_bounds(const PlannerCtx &ctx, const CorridorBoundsArgs &a);
 void site_tour(const PlannerCtx &ctx, const TourArgs &a);
-// reach_paths' offsets scan (k_reach_path_scan: offsets[1 .. n] -> running totals, offsets[0] = 0) enqueued on st, for the corridor
-// call of the store units (corridor_kernels.hpp)
-void reach_path_scan(hipStream_t st, int64_t *offsets, int64_t n);
 
 }  // namespace fiesta
+

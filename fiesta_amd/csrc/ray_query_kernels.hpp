@@ -7,9 +7,9 @@
 //   k_ray_query<SRC>  one lane per ray, grid-stride.  A walk ends at its first blocking voxel, so most of a ray is never read:
 //                     nothing is stored, the traversal hands every voxel (and "this is the last one") to the classification as it
 //                     goes.  Per voxel: the centre and its map voxel in ray_visit_code's arithmetic (raycast.hip), then SRC:
-//     DenseRaySource  the observed and the occupied bitmap; the last word pair (index, obs, occ) stays in registers, so a step along
-//                     z re-reads nothing and a step along x or y costs one word pair
-//     HashRaySource   (hash_map.hip) the map-wide page lookup of the queries; the page address of the current tile stays in
+//     DenseRaySource  (dense_read.hpp) the observed and the occupied bitmap; the last word pair (index, obs, occ) stays in registers,
+//                     so a step along z re-reads nothing and a step along x or y costs one word pair
+//     HashRaySource   (hash_read.hpp) the map-wide page lookup of the queries; the page address of the current tile stays in
 //                     registers, a voxel costs its field word and, if observed, its occupancy word (kept while the row lasts)
 // No atomics, no LDS, no scratch: every output is an integer or an f64 in a fixed operation order, the same for every launch shape.
 #pragma once
@@ -23,61 +23,12 @@
 #include "ray_walk.hpp"
 
 namespace fiesta {
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr double kRayMaxCoord = 1073741824.0;  // 2^30: |start / resolution| and |end / resolution| stay below it
 constexpr int64_t kRayMaxManhattan = 4095;     // voxel steps between the two ends
 constexpr int kRayBlock = 256, kRayMaxBlocks = 2048;  // (8 waves per SIMD of 256 CUs; larger batches stride)
 constexpr int32_t kRayNoVoxel = INT32_MIN;
-
-// what the walk needs of a map's geometry (a whole Geom as a kernel argument costs scalar registers the loop is short of)
-struct RayGeom {
-  double res, org[3];
-};
-inline RayGeom ray_geom(const Geom &g) { return RayGeom{g.res, {g.org[0], g.org[1], g.org[2]}}; }
-
-// PosInMap of a voxel CENTRE as a test on the walk voxel r itself: the centre (r + 0.5) * res never decreases as r grows (the sum is
-// exact below 2^31, the product is rounded once), so "centre >= bound" holds from some r on.  That r, by bisection over the range
-// a valid ray can reach (strict: "centre > bound"); evaluated with the kernel's own arithmetic (-ffp-contract=off on the host too).
-inline int ray_first_centre(double bound, double res, bool strict) {
-  int64_t lo = -(1ll << 30) - 2, hi = (1ll << 30) + 2;  // answer in (lo, hi]: hi if no voxel in between qualifies
-  while (hi - lo > 1) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    const double p = ((double)mid + 0.5) * res;
-    if (strict ? p > bound : p >= bound)
-      hi = mid;
-    else
-      lo = mid;
-  }
-  return (int)hi;
-}
-
-struct DenseRaySource {
-  RayGeom g;
-  int rlo[3], rhi[3];  // PosInMap(centre of walk voxel r) <=> rlo[c] <= r[c] <= rhi[c] (min_range_ / max_range_)
-  int nx, ny, nz, nzw, gx0, gy0, gz0;
-  const uint32_t *obs, *occ;
-  DenseRaySource(const Geom &G, const uint32_t *obsbits, const uint32_t *occbits)
-      : g(ray_geom(G)), nx(G.nx), ny(G.ny), nz(G.nz), nzw(G.nzw), gx0(G.gx0), gy0(G.gy0), gz0(G.gz0), obs(obsbits), occ(occbits) {
-    for (int c = 0; c < 3; ++c) rlo[c] = ray_first_centre(G.lo[c], G.res, false), rhi[c] = ray_first_centre(G.hi[c], G.res, true) - 1;
-  }
-  struct Cache {
-    int64_t w;
-    uint32_t obs, occ;
-  };
-  __device__ static Cache fresh() { return Cache{-1, 0u, 0u}; }
-  // r: the walk voxel, v: its centre's map voxel
-  __device__ int classify(const int *r, const int *v, Cache &c) const {
-    if (r[0] < rlo[0] || r[1] < rlo[1] || r[2] < rlo[2] || r[0] > rhi[0] || r[1] > rhi[1] || r[2] > rhi[2]) return FIESTA_HIP_RAY_OUTSIDE;  // PosInMap
-    const int64_t x = (int64_t)v[0] - gx0, y = (int64_t)v[1] - gy0, z = (int64_t)v[2] - gz0;
-    if ((uint64_t)x >= (uint64_t)nx || (uint64_t)y >= (uint64_t)ny || (uint64_t)z >= (uint64_t)nz) return FIESTA_HIP_RAY_OUTSIDE;
-    const int64_t w = (x * ny + y) * nzw + (z >> 5);  // Geom::bitword
-    if (w != c.w) c.w = w, c.obs = obs[w], c.occ = occ[w];
-    const int bit = (int)z & 31;
-    if (!((c.obs >> bit) & 1u)) return FIESTA_HIP_RAY_UNKNOWN;
-    return ((c.occ >> bit) & 1u) ? FIESTA_HIP_RAY_OCCUPIED : FIESTA_HIP_RAY_FREE;
-  }
-};
 
 // SRC: RayGeom g; Cache, fresh(), classify(walk voxel, map voxel of its centre, cache) -> FIESTA_HIP_RAY_* class
 template <class SRC>

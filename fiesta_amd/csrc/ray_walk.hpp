@@ -12,6 +12,12 @@ namespace fiesta {
 constexpr int kMaxRayVoxels = 1500;  // src/raycast.cpp:127-130
 constexpr int kMaxRaySteps = 8192;   // the traversal's own loop bound
 
+// what the walk needs of a map's geometry (a whole Geom as a kernel argument costs scalar registers the loop is short of)
+struct RayGeom {
+  double res, org[3];
+};
+inline RayGeom ray_geom(const Geom &g) { return RayGeom{g.res, {g.org[0], g.org[1], g.org[2]}}; }
+
 __device__ inline int sgn_i(int v) { return v == 0 ? 0 : (v < 0 ? -1 : 1); }            // signum (:6-8)
 __device__ inline double wrap1(double v) { return fmod(fmod(v, 1.0) + 1.0, 1.0); }      // mod (:10-12)
 __device__ inline double first_crossing(double s, double ds) {                          // intbound (:14-23)

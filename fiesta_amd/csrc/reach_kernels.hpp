@@ -29,9 +29,8 @@
 #include "relax_kernels.hpp"
 
 namespace fiesta {
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
-constexpr int64_t kReachMaxVoxels = 1ll << 28;  // of the clipped box: keeps every cost below 2^31 (5 * 2^28) and bounds the scratch
 constexpr int kReachBig = INT32_MAX - 8;        // "no cost yet" inside LDS: kReachBig + 5 does not overflow, real costs stay below it
 constexpr int kReachPitchZ = 34, kReachPitchY = 18 * 34, kReachLds = 18 * 18 * 34;
 constexpr int kReachChain = 8;                  // rounds enqueued between two reads of the counters
@@ -52,8 +51,6 @@ struct ReachRound {
   unsigned long long *ctr;
   int cur, next, clear;  // R_LIST*: this round's length, the next round's, the one to zero (consumed by the round before)
 };
-
-__device__ inline uint32_t reach_funnel(uint32_t lo, uint32_t hi, int s) { return (uint32_t)((((unsigned long long)hi << 32) | lo) >> s); }
 
 // SRC: void row(int x, int y, int z0, uint32_t &obs, uint32_t &occ) -- observed / occupied bits of voxels (x, y, z0 + k), k < 32 (no
 //      voxel there: both 0) -- and double operator()(int x, int y, int z): GetDistance(Vector3i) of that voxel (frontier_filter's DIST)

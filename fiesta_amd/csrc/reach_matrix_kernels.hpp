@@ -30,7 +30,7 @@
 #include "reach_kernels.hpp"
 
 namespace fiesta {
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int64_t kReachMatrixMaxEntries = 1ll << 28;  // of B cost planes (1 GiB of scratch), and of the matrix itself
 

@@ -25,7 +25,7 @@
 #include "path_cost_kernels.hpp"
 
 namespace fiesta {
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int kRefineWaveMax = 128;        // paths of at most this many waypoints are refined by one wave (two waypoints per lane)
 constexpr int64_t kRefineGridX = 1 << 15;  // work-groups per grid row: path p is work-group (p % 2^15, p / 2^15)

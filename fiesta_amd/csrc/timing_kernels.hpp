@@ -27,7 +27,7 @@
 #include "refine_kernels.hpp"
 
 namespace fiesta {
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int kTimingWaveMax = 256;  // paths of at most this many samples are timed by one wave (four samples per lane)
 

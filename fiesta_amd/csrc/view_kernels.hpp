@@ -41,7 +41,7 @@
 #include "wave_ops.hpp"
 
 namespace fiesta {
-namespace {  // (this header is included by two translation units)
+namespace {  // (planner.hip alone includes this header; the namespace is part of the kernels' symbol names)
 
 constexpr int kViewBlock = 256, kViewMaxBlocks = 2048;
 constexpr int kViewBatch = 4;                         // tiles per batch
