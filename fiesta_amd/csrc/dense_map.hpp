@@ -215,7 +215,7 @@ class DenseMap {
   unsigned long long *cnt_ = nullptr;  // 8 B/voxel, cold: hits<<32 | observations (num_hit_/num_miss_)
   uint32_t *occbits_ = nullptr;        // 1 bit/voxel: Exist(idx)
   uint32_t *rbits_ = nullptr;          // 1 bit/voxel: voxel joined the frontier during the current update
-  uint32_t *obsbits_ = nullptr;        // 1 bit/voxel: observed at least once (k_fuse; rebuilt from the field after a restore / load)
+  uint32_t *obsbits_ = nullptr;        // 1 bit/voxel: observed at least once (k_fuse; copied by snapshot save / restore; rebuilt from the field after a load, on a shard by planner_view)
   uint32_t *latebits_ = nullptr;       // 1 bit/voxel: first observed while obstacles existed and not reached by a wave since (C_LATE counts them)
   uint32_t *gocc_ = nullptr;           // sharded maps: 1 bit/voxel of the GLOBAL grid, replicated on every shard
   int64_t ngoccwords_ = 0;
