@@ -7,6 +7,7 @@ from ._lib import FiestaHipError, LIB_PATH, device_count, load  # noqa: F401
 from .esdf_map import (D2_INF, INFINITY, UNDEFINED, ESDFMap, frontier_model, path_cost_model, path_samples, ray_query_model,  # noqa: F401
                        ray_walk, ray_walks, signed_distance)
 from .cluster_model import cluster_model, cluster_stencil  # noqa: F401
+from .skeleton_model import skeleton_model  # noqa: F401
 from .split_model import SPLIT_INVALID, SPLIT_MAX_DEPTH, SPLIT_OK, split_model  # noqa: F401
 from .view_model import VIEW_OMNI, view_coverage_model, view_ring  # noqa: F401
 from .reach_model import (LEG_BAD_INDEX, LEG_NO_SOURCE, REACH_PATHS_SHORTCUT, REACH_THROUGH_UNKNOWN, leg_paths_model,  # noqa: F401
@@ -23,5 +24,5 @@ from .timing_model import (TIMING_INVALID, TIMING_MAX_SAMPLES, TIMING_MAX_WAYPOI
 __all__ = ["path_timing_model", "TIMING_OK", "TIMING_INVALID", "TIMING_TOO_LONG", "TIMING_MAX_WAYPOINTS", "TIMING_MAX_SAMPLES", "path_refine_model", "path_refine_gradient", "corridor_bounds", "corridor_bounds_model", "BOUNDS_VOID_BROKEN","REFINE_OK", "REFINE_INVALID", "REFINE_MAX_WAYPOINTS",
            "REFINE_MAX_ITERATIONS", "free_box_model", "corridor_chain", "corridor_model", "CORRIDOR_THROUGH_UNKNOWN", "CORRIDOR_MAX_GROW", "CORRIDOR_STOP_BLOCKED",
            "CORRIDOR_STOP_EDGE", "CORRIDOR_STOP_LIMIT", "FREE_BOX_OK", "FREE_BOX_OUTSIDE", "FREE_BOX_BLOCKED", "CORRIDOR_OK", "CORRIDOR_INVALID",
-           "CORRIDOR_BLOCKED", "tour_model", "best_move", "TOUR_CLOSED", "ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "reach_model", "reach_matrix_model", "REACH_THROUGH_UNKNOWN", "reach_moves", "reach_paths_model", "leg_paths_model", "LEG_NO_SOURCE", "LEG_BAD_INDEX", "reach_visible", "reach_walk", "REACH_PATHS_SHORTCUT", "cluster_model", "cluster_stencil", "split_model", "SPLIT_OK", "SPLIT_INVALID", "SPLIT_MAX_DEPTH", "view_coverage_model", "view_ring", "VIEW_OMNI", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
+           "CORRIDOR_BLOCKED", "tour_model", "best_move", "TOUR_CLOSED", "ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "reach_model", "reach_matrix_model", "REACH_THROUGH_UNKNOWN", "reach_moves", "reach_paths_model", "leg_paths_model", "LEG_NO_SOURCE", "LEG_BAD_INDEX", "reach_visible", "reach_walk", "REACH_PATHS_SHORTCUT", "cluster_model", "cluster_stencil", "skeleton_model", "split_model", "SPLIT_OK", "SPLIT_INVALID", "SPLIT_MAX_DEPTH", "view_coverage_model", "view_ring", "VIEW_OMNI", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",
            "D2_INF"]

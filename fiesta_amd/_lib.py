@@ -85,6 +85,11 @@ class RayResult(C.Structure):
                 ("hit_dist", C.c_void_p), ("counts", C.c_void_p)]
 
 
+class SkeletonResult(C.Structure):
+    """fiesta_hip_skeleton_result: one array per output of fiesta_hip_get_skeleton_voxels, every pointer nullable"""
+    _fields_ = [("vox", C.c_void_p), ("mask", C.c_void_p), ("d2", C.c_void_p), ("sep2", C.c_void_p)]
+
+
 class ReachResult(C.Structure):
     """fiesta_hip_reach_result: one array per output of fiesta_hip_reach_field, every pointer nullable"""
     _fields_ = [("cost", C.c_void_p), ("target_cost", C.c_void_p)]
@@ -323,6 +328,8 @@ def load():
         "fiesta_hip_path_cost_dev": (C.c_int, [vp, vp, i64, vp, i64, dbl, dbl, vp]),
         "fiesta_hip_get_frontier_voxels": (C.c_int, [vp, vp, vp, dbl, vp, vp, i64, vp]),
         "fiesta_hip_get_frontier_voxels_dev": (C.c_int, [vp, vp, vp, dbl, vp, vp, i64, vp]),
+        "fiesta_hip_get_skeleton_voxels": (C.c_int, [vp, vp, vp, i32, dbl, i64, vp, vp]),
+        "fiesta_hip_get_skeleton_voxels_dev": (C.c_int, [vp, vp, vp, i32, dbl, i64, vp, vp]),
         "fiesta_hip_ray_query": (C.c_int, [vp, vp, vp, i64, i32, vp]),
         "fiesta_hip_ray_query_dev": (C.c_int, [vp, vp, vp, i64, i32, vp]),
         "fiesta_hip_reach_field": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, dbl, i32, i32, vp, vp]),

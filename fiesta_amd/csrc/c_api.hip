@@ -63,7 +63,7 @@ DenseMap &dense(fiesta_hip_map *m, const char *what) {
 }
 // The planner calls: one body per host / _dev pair.  Each checks the whole-call errors of include/fiesta_hip.h on the arguments as
 // the ABI took them (the call's aggregate of planner_args.hpp), then hands the same object on to the call's function of planner.hpp,
-// with the store's planner_ctx() and -- the ten calls that read voxels -- its planner_view(does the call read the bitmaps?).
+// with the store's planner_ctx() and -- the eleven calls that read voxels -- its planner_view(does the call read the bitmaps?).
 
 // shared by path_clearance and path_cost (R: the call's result struct); a host batch: the CSR rules as well
 template <typename R>
@@ -93,6 +93,17 @@ int64_t frontier_voxels(fiesta_hip_map *m, const fiesta::FrontierArgs &a, const 
   need((a.lo == nullptr) == (a.hi == nullptr), "get_frontier_voxels: lo and hi must both be given or both be null");
   need(a.capacity >= 0, "get_frontier_voxels: negative capacity");
   return on_store(m, [&](auto &s) { return fiesta::frontier_voxels(s.planner_ctx(), s.planner_view(true), a); });
+}
+// as frontier_voxels; none of these errors needs a device
+int64_t skeleton_voxels(fiesta_hip_map *m, const fiesta::SkeletonArgs &a, const void *n_out) {
+  need(a.res != nullptr, "get_skeleton_voxels: result is null");
+  need(n_out != nullptr, "get_skeleton_voxels: n_out is null");
+  need(a.min_sep2 >= 1, "get_skeleton_voxels: min_sep2 must be at least 1");
+  need(!std::isnan(a.min_clearance), "get_skeleton_voxels: min_clearance is NaN");
+  need((a.lo == nullptr) == (a.hi == nullptr), "get_skeleton_voxels: lo and hi must both be given or both be null");
+  need(a.capacity >= 0, "get_skeleton_voxels: negative capacity");
+  need(m != nullptr, "null map handle");
+  return on_store(m, [&](auto &s) { return fiesta::skeleton_voxels(s.planner_ctx(), s.planner_view(true), a); });
 }
 void ray_query(fiesta_hip_map *m, const fiesta::RayArgs &a) {
   need(m != nullptr, "null map handle");
@@ -711,6 +722,14 @@ int fiesta_hip_get_frontier_voxels(fiesta_hip_map *m, const int32_t lo[3], const
 int fiesta_hip_get_frontier_voxels_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance, int32_t *vox_dev,
                                        uint8_t *mask_dev, int64_t capacity, unsigned long long *n_out_dev) {
   return guarded([&] { frontier_voxels(m, {lo, hi, min_clearance, vox_dev, mask_dev, capacity, n_out_dev, true}, n_out_dev); });
+}
+int fiesta_hip_get_skeleton_voxels(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], int32_t min_sep2, double min_clearance,
+                                   int64_t capacity, const fiesta_hip_skeleton_result *result, int64_t *n_out) {
+  return guarded([&] { *n_out = skeleton_voxels(m, {lo, hi, min_sep2, min_clearance, capacity, result, nullptr, false}, n_out); });
+}
+int fiesta_hip_get_skeleton_voxels_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], int32_t min_sep2, double min_clearance,
+                                       int64_t capacity, const fiesta_hip_skeleton_result *result, unsigned long long *n_out_dev) {
+  return guarded([&] { skeleton_voxels(m, {lo, hi, min_sep2, min_clearance, capacity, result, n_out_dev, true}, n_out_dev); });
 }
 int fiesta_hip_ray_query(fiesta_hip_map *m, const double *start, const double *end, int64_t n, int32_t stop_mask,
                          const fiesta_hip_ray_result *r) {

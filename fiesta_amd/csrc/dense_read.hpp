@@ -172,6 +172,7 @@ struct DenseView {
 
   DensePathEval path_eval() const { return DensePathEval{g, coc}; }
   DenseFrontierDist frontier() const { return DenseFrontierDist{g, coc}; }
+  const vox_t *field() const { return coc; }  // the skeleton kernel's word source: the field itself, z fastest (Geom::idx)
   DenseReachSource reach_source() const { return DenseReachSource{g, obs, occ, coc}; }
   DenseRaySource ray_source() const { return DenseRaySource(g, obs, occ); }
   // a caller's box (null: everything) in local array coordinates, intersected with the array; false: nothing is left

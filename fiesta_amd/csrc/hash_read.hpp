@@ -130,6 +130,11 @@ struct HashFrontierPages {
   const vox_t *coc;
   __device__ int64_t addr(int vx, int vy, int vz) const { return h_lookup(g, dir, tab, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
   __device__ double operator()(int vx, int vy, int vz) const { return h_distance(g, dir, tab, coc, vx - g.gx0, vy - g.gy0, vz - g.gz0); }
+  // the same value for a caller that already holds the voxel's word (kAct masked): h_distance without its lookup
+  __device__ double word_distance(int vx, int vy, int vz, vox_t w) const {
+    if (w & kNoCoc) return (double)FIESTA_HIP_INFINITY;
+    return sqrt((double)dist2(1, vx, vy, vz, w)) * g.res;
+  }
 };
 // the map side of the reachability flood (reach_kernels.hpp: k_reach_mask), MAP voxel coordinates: 32 voxels from any z are the
 // rows of one or two tiles, each found by the queries' map-wide lookup (parked pages answer; no page: all unknown), its observed
@@ -204,6 +209,7 @@ struct HashView {
 
   HashPathEval path_eval() const { return HashPathEval{g, dir, tab, coc}; }
   HashFrontierPages frontier() const { return HashFrontierPages{g, dir, tab, coc}; }
+  const vox_t *field() const { return coc; }  // the skeleton kernel's word source: the page pool, kPageVox words per page
   HashReachSource reach_source() const { return HashReachSource{g, dir, tab, coc, occbits}; }
   HashRaySource ray_source() const { return HashRaySource{ray_geom(g), g, dir, tab, coc, occbits}; }
   // the reach calls' clamped box (lo / hi are not null here), checked before anything is launched; empty: blo[0] > bhi[0]

@@ -16,6 +16,7 @@
 #include "reach_matrix_kernels.hpp"
 #include "reach_path_kernels.hpp"
 #include "refine_kernels.hpp"
+#include "skeleton_kernels.hpp"
 #include "split_kernels.hpp"
 #include "timing_kernels.hpp"
 #include "tour_kernels.hpp"
@@ -107,6 +108,48 @@ int64_t frontier_voxels(const PlannerCtx &ctx, const View &v, const FrontierArgs
   return n;
 }
 
+// The skeleton call's store side, next to the frontier call's: the same box (frontier_box), the store's stencil kernel over it
+static void skeleton_launch(hipStream_t st, const DenseView &v, const FrontierBox &b, const SkeletonArgs &a, const SkeletonOut &out) {
+  const int64_t nrows = (int64_t)(b.x1 - b.x0 + 1) * (b.y1 - b.y0 + 1);  // a wave each, four to a work-group
+  hipLaunchKernelGGL(k_skeleton_dense, dim3(grid_for(nrows, 4, 2048)), dim3(256), 0, st, v.g, v.field(), v.obs, v.occ, b,
+                     a.min_sep2, a.min_clearance, out);
+}
+static void skeleton_launch(hipStream_t st, const HashView &v, const FrontierBox &b, const SkeletonArgs &a, const SkeletonOut &out) {
+  hipLaunchKernelGGL(k_skeleton_hash<HashFrontierPages>, dim3(grid_for(v.npages, 1, 8192)), dim3(256), 0, st, v.page_gtile, v.npages, v.field(),
+                     v.occbits, b, v.frontier(), a.min_sep2, a.min_clearance, out);
+}
+// dev: the result's arrays and n_out_dev are device pointers and the call is only enqueued; else host pointers, and the total is returned
+template <class View>
+int64_t skeleton_voxels(const PlannerCtx &ctx, const View &v, const SkeletonArgs &a) {
+  use_device(ctx);
+  unsigned long long *count = a.dev ? a.n_out_dev : ctx.counter;
+  hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, ctx.stream, count, 1);
+  FIESTA_HIP_CHECK(hipGetLastError());
+  FrontierBox b;
+  bool empty;
+  const FrontierArgs box{a.lo, a.hi, a.min_clearance, nullptr, nullptr, a.capacity, nullptr, a.dev};
+  const int64_t cap = std::min(a.capacity, frontier_box(v, box, b, empty));
+  Staging res{ctx.S.out, ctx.stream};  // (the host variant's)
+  const auto vox = res.add(a.res->vox, 3 * cap);
+  const auto mask = res.add(a.res->mask, cap);
+  const auto d2 = res.add(a.res->d2, cap);
+  const auto sep2 = res.add(a.res->sep2, cap);
+  if (!a.dev) res.alloc();
+  const SkeletonOut out = a.dev ? SkeletonOut{a.res->vox, a.res->mask, a.res->d2, a.res->sep2, (unsigned long long)cap, count}
+                                : SkeletonOut{res.dev(vox), res.dev(mask), res.dev(d2), res.dev(sep2), (unsigned long long)cap, count};
+  if (!empty) {
+    skeleton_launch(ctx.stream, v, b, a, out);
+    FIESTA_HIP_CHECK(hipGetLastError());
+  }
+  if (a.dev) return 0;
+  FIESTA_HIP_CHECK(hipMemcpyAsync(ctx.counter_host, ctx.counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx.stream));
+  FIESTA_HIP_CHECK(hipStreamSynchronize(ctx.stream));
+  const int64_t n = (int64_t)*ctx.counter_host, m = std::min(n, cap);
+  res.back(vox, 3 * m), res.back(mask, m), res.back(d2, m), res.back(sep2, m);
+  FIESTA_HIP_CHECK(hipStreamSynchronize(ctx.stream));
+  return n;
+}
+
 template <class View>
 void ray_query(const PlannerCtx &ctx, const View &v, const RayArgs &a) {
   if (a.n <= 0) return;
@@ -151,6 +194,7 @@ void view_coverage(const PlannerCtx &ctx, const View &v, const ViewArgs &a) {
   template void path_refine(const PlannerCtx &, const VIEW &, const PathRefineArgs &);                                                   \
   template void path_timing(const PlannerCtx &, const VIEW &, const PathTimingArgs &);                                                   \
   template int64_t frontier_voxels(const PlannerCtx &, const VIEW &, const FrontierArgs &);                                              \
+  template int64_t skeleton_voxels(const PlannerCtx &, const VIEW &, const SkeletonArgs &);                                              \
   template void ray_query(const PlannerCtx &, const VIEW &, const RayArgs &);                                                            \
   template void reach_field(const PlannerCtx &, const VIEW &, const ReachArgs &);                                                        \
   template void reach_matrix(const PlannerCtx &, const VIEW &, const ReachMatrixArgs &);                                                 \

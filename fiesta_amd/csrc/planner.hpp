@@ -1,7 +1,7 @@
 // fiesta_amd/csrc/planner.hpp -- what a map keeps for the planner calls, and the calls themselves.
 //
-// Both stores own one PlannerScratch.  The sixteen calls are the free functions at the end of this header, defined once in
-// planner.hip, the only unit that includes the planner kernel headers: six need nothing of a map but its planner_ctx(); ten also
+// Both stores own one PlannerScratch.  The seventeen calls are the free functions at the end of this header, defined once in
+// planner.hip, the only unit that includes the planner kernel headers: six need nothing of a map but its planner_ctx(); eleven also
 // read voxels, through the store's planner_view() (dense_read.hpp: DenseView, hash_read.hpp: HashView).
 #pragma once
 #include <algorithm>
@@ -132,6 +132,7 @@ struct Staging {
 template <typename R>
 struct PathArgs;
 struct FrontierArgs;
+struct SkeletonArgs;
 struct RayArgs;
 struct ReachArgs;
 struct ReachMatrixArgs;
@@ -171,6 +172,9 @@ void path_timing(const PlannerCtx &ctx, const View &v, const PathTimingArgs &a);
 // fiesta_hip_get_frontier_voxels[_dev]: returns the host variant's total (which may exceed the capacity)
 template <class View>
 int64_t frontier_voxels(const PlannerCtx &ctx, const View &v, const FrontierArgs &a);
+// fiesta_hip_get_skeleton_voxels[_dev]: returns the host variant's total (which may exceed the capacity)
+template <class View>
+int64_t skeleton_voxels(const PlannerCtx &ctx, const View &v, const SkeletonArgs &a);
 // fiesta_hip_ray_query[_dev], fiesta_hip_reach_field[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_free_boxes[_dev] and
 // fiesta_hip_path_corridor[_dev], fiesta_hip_view_coverage[_dev]
 template <class View>

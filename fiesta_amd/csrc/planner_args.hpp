@@ -32,6 +32,16 @@ struct FrontierArgs {  // the call's arguments as fiesta_hip_get_frontier_voxels
   bool dev;
 };
 
+struct SkeletonArgs {  // the call's arguments as fiesta_hip_get_skeleton_voxels[_dev] takes them, already checked
+  const int32_t *lo, *hi;  // both null: the whole map
+  int32_t min_sep2;
+  double min_clearance;
+  int64_t capacity;
+  const fiesta_hip_skeleton_result *res;
+  unsigned long long *n_out_dev;  // the device variant's total
+  bool dev;
+};
+
 struct RayArgs {  // the call's arguments as fiesta_hip_ray_query[_dev] takes them, already checked
   const double *start, *end;
   int64_t n;

@@ -743,6 +743,44 @@ class ESDFMap:
                                                            C.c_void_p(mask_dev_ptr or None), int(capacity),
                                                            C.c_void_p(n_out_dev_ptr or None)))
 
+    SKELETON_FIELDS = (("vox", np.int32, (3,)), ("mask", np.uint8, ()), ("d2", np.int32, ()), ("sep2", np.int32, ()))
+
+    def GetSkeletonVoxels(self, lo=None, hi=None, min_sep2=9, min_clearance=0.0, want=("vox", "mask", "d2", "sep2")) -> dict:
+        """fiesta_hip_get_skeleton_voxels: the free voxels on the distance field's ridge -- a 6-neighbour names a closest obstacle at
+        least sqrt(min_sep2) voxels from the voxel's own and the bisector of the two passes between them -- inside the inclusive
+        map-voxel box [lo, hi] (both None: the whole map), optionally only those with GetDistance >= min_clearance.  A dict of the
+        arrays named in `want` (vox (n, 3) int32, mask (n,) uint8: the ridge-neighbour bits, d2 (n,) int32, sep2 (n,) int32: the
+        largest separation over the mask's bits) and "n", unordered; skeleton_model is the definition"""
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        unknown = set(want) - {f[0] for f in self.SKELETON_FIELDS}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        blo = None if lo is None else np.ascontiguousarray(lo, np.int32).reshape(3)
+        bhi = None if hi is None else np.ascontiguousarray(hi, np.int32).reshape(3)
+        n = C.c_int64(0)
+        res = _lib.SkeletonResult(None, None, None, None)
+        check(self._lib.fiesta_hip_get_skeleton_voxels(self._h, _p(blo), _p(bhi), int(min_sep2), float(min_clearance), 0, C.byref(res),
+                                                       C.byref(n)))
+        out = {name: np.empty((n.value,) + shape, dt) for name, dt, shape in self.SKELETON_FIELDS if name in want}
+        if n.value and out:
+            res = _lib.SkeletonResult(*[out[name].ctypes.data if name in out else None for name, _, _ in self.SKELETON_FIELDS])
+            total = C.c_int64(0)
+            check(self._lib.fiesta_hip_get_skeleton_voxels(self._h, _p(blo), _p(bhi), int(min_sep2), float(min_clearance), n.value,
+                                                           C.byref(res), C.byref(total)))
+        out["n"] = int(n.value)
+        return out
+
+    def GetSkeletonVoxelsDevice(self, lo, hi, min_sep2, min_clearance, capacity: int, n_out_dev_ptr: int, vox_dev_ptr: int = 0,
+                                mask_dev_ptr: int = 0, d2_dev_ptr: int = 0, sep2_dev_ptr: int = 0):
+        """fiesta_hip_get_skeleton_voxels_dev: the outputs and the 64-bit counter resident on the device (0: that array is not
+        written), lo / hi host triples or None; only enqueued on the map's stream, the call zeroes the counter itself"""
+        blo = None if lo is None else np.ascontiguousarray(lo, np.int32).reshape(3)
+        bhi = None if hi is None else np.ascontiguousarray(hi, np.int32).reshape(3)
+        res = _lib.SkeletonResult(vox_dev_ptr or None, mask_dev_ptr or None, d2_dev_ptr or None, sep2_dev_ptr or None)
+        check(self._lib.fiesta_hip_get_skeleton_voxels_dev(self._h, _p(blo), _p(bhi), int(min_sep2), float(min_clearance), int(capacity),
+                                                           C.byref(res), C.c_void_p(n_out_dev_ptr or None)))
+
     def RayQuery(self, start, end, stop_mask=7) -> dict:
         """fiesta_hip_ray_query: per segment start -> end (metres, (n, 3) or one triple) the first voxel of its walk whose class is in
         `stop_mask` (RAY_OCCUPIED | RAY_UNKNOWN | RAY_OUTSIDE), its index, class, map voxel and distance, the number of voxels visited

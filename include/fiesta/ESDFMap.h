@@ -260,6 +260,37 @@ class ESDFMap {
   void GetFrontierVoxels(double min_clearance, std::vector<Eigen::Vector3i> &out, std::vector<uint8_t> *mask = nullptr) {
     FrontierVoxels(nullptr, nullptr, min_clearance, out, mask);
   }
+  // Skeleton voxels (fiesta_hip_get_skeleton_voxels, include/fiesta_hip.h): the free voxels on the distance field's ridge -- a
+  // 6-neighbour names a closest obstacle at least sqrt(min_sep2) voxels from the voxel's own, and the bisector of the two passes
+  // between them -- inside the inclusive voxel box [lo, hi] (both null: the whole map), optionally only those with GetDistance >=
+  // min_clearance.  Entry i of every vector describes vox[i]: the ridge-neighbour bits (bit 0 -x, 1 +x, 2 -y, 3 +y, 4 -z, 5 +z), the
+  // voxel's own squared distance in voxels, the largest separation (squared) over the mask's bits.  Order unspecified.  min_sep2 up
+  // to 4 marks the neighbourhood of every flat surface; prune by angle from sep2 and d2.  ClusterVoxels with d2 as the key names each
+  // cluster's narrowest member: the bottleneck of the passage.
+  struct SkeletonVoxels {
+    std::vector<Eigen::Vector3i> vox;
+    std::vector<uint8_t> mask;
+    std::vector<int32_t> d2, sep2;
+    size_t count() const { return vox.size(); }
+  };
+  SkeletonVoxels GetSkeletonVoxels(const Eigen::Vector3i *lo, const Eigen::Vector3i *hi, int32_t min_sep2, double min_clearance = 0.0) {
+    if ((lo == nullptr) != (hi == nullptr)) throw std::invalid_argument("GetSkeletonVoxels: lo and hi must both be given or both be null");
+    Flush();
+    int32_t a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
+    for (int c = 0; lo && c < 3; ++c) a[c] = (*lo)(c), b[c] = (*hi)(c);
+    const int32_t *pa = lo ? a : nullptr, *pb = lo ? b : nullptr;
+    int64_t n = 0;
+    const fiesta_hip_skeleton_result none{nullptr, nullptr, nullptr, nullptr};
+    ck(fiesta_hip_get_skeleton_voxels(h_, pa, pb, min_sep2, min_clearance, 0, &none, &n));  // sizes the buffers
+    SkeletonVoxels out;
+    std::vector<int32_t> vox((size_t)3 * n + 1);  // (one spare entry in every array: never a null pointer)
+    out.mask.assign((size_t)n + 1, 0), out.d2.assign((size_t)n + 1, 0), out.sep2.assign((size_t)n + 1, 0);
+    const fiesta_hip_skeleton_result r{vox.data(), out.mask.data(), out.d2.data(), out.sep2.data()};
+    if (n) ck(fiesta_hip_get_skeleton_voxels(h_, pa, pb, min_sep2, min_clearance, n, &r, &n));
+    out.mask.resize((size_t)n), out.d2.resize((size_t)n), out.sep2.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) out.vox.push_back(Eigen::Vector3i(vox[3 * i], vox[3 * i + 1], vox[3 * i + 2]));
+    return out;
+  }
   // Ray queries (fiesta_hip_ray_query, include/fiesta_hip.h): what a sensor ray from `start` to `end` would cross, read-only.  The
   // walk is the ray cast's; a voxel is FREE, OCCUPIED, UNKNOWN (never observed) or OUTSIDE (dense maps), and the query stops at
   // the first voxel whose class is in stop_mask (FIESTA_HIP_RAY_OCCUPIED | _UNKNOWN | _OUTSIDE).  Line of sight through known free

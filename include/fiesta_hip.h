@@ -442,6 +442,54 @@ int fiesta_hip_get_frontier_voxels(fiesta_hip_map *m, const int32_t lo[3], const
 int fiesta_hip_get_frontier_voxels_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance,
                                        int32_t *vox_dev, uint8_t *mask_dev, int64_t capacity, unsigned long long *n_out_dev);
 
+/* ---- skeleton voxels: the distance field's ridge between obstacles, compacted on the device ----
+ * Where is the robot equally far from two different obstacles?  Every field word names its voxel's closest obstacle; where two
+ * neighbouring voxels name obstacles that lie apart, the field has a ridge: the generalised Voronoi skeleton of free space -- the
+ * middle of corridors, doorways and gaps, the routes of maximum clearance, the topology of free space as a sparse voxel set.  No
+ * reference counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.
+ * For a voxel v of the map, in map voxel coordinates:
+ *   observed(v), free(v)  exactly as for fiesta_hip_get_frontier_voxels.
+ *   site(v)      defined iff observed(v) and the field word carries an obstacle: 0 <= d2 < INT32_MAX in fiesta_hip_download_field /
+ *                fiesta_hip_download_hash.  ("Observed, no obstacle" has no site, whatever stale link the word keeps.)  Its value is
+ *                the stored closest obstacle in map voxel coordinates, the coc triple those dumps report.
+ *   ridge(v, n)  for a 6-neighbour n of v with a = site(v) and b = site(n) both defined, sep2 = |a - b|^2 and
+ *                g(x) = |x - b|^2 - |x - a|^2 (linear in x: the signed side of the bisector plane of a and b):
+ *                  sep2 >= min_sep2  and  g(v) >= 0  and  g(n) <= 0  and  g(v) <= -g(n)
+ *                -- the bisector passes between the two voxels and v is at least as close to it as n (a tie marks both).  A pair that
+ *                the field's own inexactness puts on the wrong side of its bisector is skipped.  Integers only.  A neighbour
+ *                outside a dense map's array, not observed or without a site gives no ridge.  The query box below does not clip the
+ *                neighbour test.
+ *   r(v)         the six-bit mask of the neighbours with ridge(v, n).  bit 0: -x, bit 1: +x, bit 2: -y, bit 3: +y, bit 4: -z, bit 5: +z.
+ *   skeleton(v)  free(v), site(v) defined, r(v) != 0, v inside the inclusive voxel box [lo, hi], and -- only if min_clearance > 0 --
+ *                GetDistance(Vector3i v) >= min_clearance, with the very f64 value the voxel query returns.  The field is read as
+ *                it stands, like every query: after UpdateOccupancy and before UpdateESDF occupancy is new and the sites are old.
+ * min_sep2 >= 1.  Adjacent voxels of one flat surface are distinct sites 1, 2 or 4 apart (squared): values up to 4 mark the whole
+ * neighbourhood of any flat surface; 9 or more keeps the ridges between separate obstacles.  Callers who prune by ANGLE do so from
+ * the returned sep2 and d2 (the sites subtend an angle of 2 asin(sqrt(sep2 / d2) / 2) at v, roughly); the call itself does not.
+ * lo / hi are HOST pointers in both variants; both NULL, clipping and empty boxes exactly as for fiesta_hip_get_frontier_voxels.
+ * At most `capacity` entries are written.  Entry k of every array of the result describes the same voxel; each array is nullable.
+ * *n_out is the total whatever the capacity (call with capacity 0 to size the buffers).  Order is unspecified; the SET of
+ * (v, r(v), d2, sep2) rows is exact and the same for every launch shape.  A map created as a shard answers for its own array;
+ * there is no shard-group call.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable): min_sep2 < 1, min_clearance is NaN, exactly
+ * one of lo / hi is NULL, capacity is negative, result or n_out is NULL.
+ * fiesta_hip_get_skeleton_voxels      host arrays; stages, runs, synchronises, copies min(total, capacity) entries back.
+ * fiesta_hip_get_skeleton_voxels_dev  the result's arrays and n_out_dev are device pointers; only enqueued on the map's stream, no
+ *                                     host round trip: the call zeroes *n_out_dev itself.  The counter feeds
+ *                                     fiesta_hip_cluster_voxels_dev; with d2 as the key every cluster comes with its narrowest
+ *                                     member, the bottleneck of the passage. */
+typedef struct fiesta_hip_skeleton_result { /* every pointer nullable */
+  int32_t *vox;                             /* per entry x 3, map voxel coordinates */
+  uint8_t *mask;                            /* per entry: r(v) */
+  int32_t *d2;                              /* per entry: the voxel's own squared distance, in voxels */
+  int32_t *sep2;                            /* per entry: the largest sep2 over the set bits of r(v) */
+} fiesta_hip_skeleton_result;
+int fiesta_hip_get_skeleton_voxels(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], int32_t min_sep2, double min_clearance,
+                                   int64_t capacity, const fiesta_hip_skeleton_result *result, int64_t *n_out);
+int fiesta_hip_get_skeleton_voxels_dev(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], int32_t min_sep2,
+                                       double min_clearance, int64_t capacity, const fiesta_hip_skeleton_result *result,
+                                       unsigned long long *n_out_dev);
+
 /* ---- ray queries: what a sensor ray from start to end would cross, read-only and batched ----
  * Line of sight for path shortcutting and any-angle search (occupied AND unknown must block, which the distance field cannot tell
  * apart), the information gain of a candidate view (unknown voxels along its rays up to the first obstacle -- the question after
