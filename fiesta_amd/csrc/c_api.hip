@@ -63,7 +63,7 @@ DenseMap &dense(fiesta_hip_map *m, const char *what) {
 }
 // The planner calls: one body per host / _dev pair.  Each checks the whole-call errors of include/fiesta_hip.h on the arguments as
 // the ABI took them (the call's aggregate of planner_args.hpp), then hands the same object on to the call's function of planner.hpp,
-// with the store's planner_ctx() and -- the eleven calls that read voxels -- its planner_view(does the call read the bitmaps?).
+// with the store's planner_ctx() and -- the twelve calls that read voxels -- its planner_view(does the call read the bitmaps?).
 
 // shared by path_clearance and path_cost (R: the call's result struct); a host batch: the CSR rules as well
 template <typename R>
@@ -84,6 +84,19 @@ void path_cost(fiesta_hip_map *m, const fiesta::PathCostArgs &a) {
   path_checks(m, a);
   need(std::isfinite(a.margin), "path_cost: margin must be finite");
   on_store(m, [&](auto &s) { fiesta::path_cost(s.planner_ctx(), s.planner_view(false), s.host_path_eval(), a); });
+}
+// fiesta_hip_body_query: none of these errors needs a device; the sphere table is a host pointer in both variants and is checked here
+void body_query(fiesta_hip_map *m, const fiesta::BodyArgs &a) {
+  need(m != nullptr, "null map handle");
+  need(a.n_spheres >= 1 && a.n_spheres <= FIESTA_HIP_BODY_MAX_SPHERES, "body_query: n_spheres must be 1 .. 1024");
+  need(a.n_poses >= 0, "body_query: negative count");
+  need(a.spheres != nullptr, "body_query: spheres is null");
+  need(a.poses != nullptr || a.n_poses == 0, "body_query: poses is null");
+  need(a.res != nullptr, "body_query: result is null");
+  for (int64_t i = 0; i < 4 * (int64_t)a.n_spheres; ++i) need(std::isfinite(a.spheres[i]), "body_query: a sphere's centre or radius is not finite");
+  for (int32_t i = 0; i < a.n_spheres; ++i) need(a.spheres[4 * i + 3] >= 0, "body_query: a sphere's radius is negative");
+  need(std::isfinite(a.margin), "body_query: margin must be finite");
+  on_store(m, [&](auto &s) { fiesta::body_query(s.planner_ctx(), s.planner_view(false), a); });
 }
 // n_out: the variant's total (host or device pointer); returns the host variant's total
 int64_t frontier_voxels(fiesta_hip_map *m, const fiesta::FrontierArgs &a, const void *n_out) {
@@ -714,6 +727,14 @@ int fiesta_hip_get_occupied_voxels(fiesta_hip_map *m, int32_t *vox, int64_t capa
     need(n_out != nullptr && capacity >= 0, "bad argument");
     *n_out = dense(m, "get_occupied_voxels").occupied_voxels(vox, capacity);
   });
+}
+int fiesta_hip_body_query(fiesta_hip_map *m, const double *spheres, int32_t n_spheres, const double *poses, int64_t n_poses, double margin,
+                          const fiesta_hip_body_result *result) {
+  return guarded([&] { body_query(m, {spheres, n_spheres, poses, n_poses, margin, result, false}); });
+}
+int fiesta_hip_body_query_dev(fiesta_hip_map *m, const double *spheres, int32_t n_spheres, const double *poses_dev, int64_t n_poses, double margin,
+                              const fiesta_hip_body_result *result) {
+  return guarded([&] { body_query(m, {spheres, n_spheres, poses_dev, n_poses, margin, result, true}); });
 }
 int fiesta_hip_get_frontier_voxels(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance, int32_t *vox,
                                    uint8_t *mask, int64_t capacity, int64_t *n_out) {

@@ -1,7 +1,7 @@
 // fiesta_amd/csrc/planner.hpp -- what a map keeps for the planner calls, and the calls themselves.
 //
-// Both stores own one PlannerScratch.  The seventeen calls are the free functions at the end of this header, defined once in
-// planner.hip, the only unit that includes the planner kernel headers: six need nothing of a map but its planner_ctx(); eleven also
+// Both stores own one PlannerScratch.  The eighteen calls are the free functions at the end of this header, defined once in
+// planner.hip, the only unit that includes the planner kernel headers: six need nothing of a map but its planner_ctx(); twelve also
 // read voxels, through the store's planner_view() (dense_read.hpp: DenseView, hash_read.hpp: HashView).
 #pragma once
 #include <algorithm>
@@ -131,6 +131,7 @@ struct Staging {
 // (Named only: raycast.hip sees the stores' headers and keeps a RayArgs of its own.)
 template <typename R>
 struct PathArgs;
+struct BodyArgs;
 struct FrontierArgs;
 struct SkeletonArgs;
 struct RayArgs;
@@ -169,6 +170,9 @@ template <class View>
 void path_refine(const PlannerCtx &ctx, const View &v, const PathRefineArgs &a);
 template <class View>
 void path_timing(const PlannerCtx &ctx, const View &v, const PathTimingArgs &a);
+// fiesta_hip_body_query[_dev]: the path calls' evaluator at the sphere centres of a body (always on the device)
+template <class View>
+void body_query(const PlannerCtx &ctx, const View &v, const BodyArgs &a);
 // fiesta_hip_get_frontier_voxels[_dev]: returns the host variant's total (which may exceed the capacity)
 template <class View>
 int64_t frontier_voxels(const PlannerCtx &ctx, const View &v, const FrontierArgs &a);

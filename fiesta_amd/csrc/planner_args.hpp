@@ -22,6 +22,16 @@ struct PathArgs {
 using PathClearanceArgs = PathArgs<fiesta_hip_path_result>;
 using PathCostArgs = PathArgs<fiesta_hip_path_cost_result>;
 
+struct BodyArgs {  // the call's arguments as fiesta_hip_body_query[_dev] takes them, already checked
+  const double *spheres;  // a host pointer in both variants: cx, cy, cz, r per sphere
+  int32_t n_spheres;
+  const double *poses;
+  int64_t n_poses;
+  double margin;
+  const fiesta_hip_body_result *res;
+  bool dev;
+};
+
 struct FrontierArgs {  // the call's arguments as fiesta_hip_get_frontier_voxels[_dev] takes them, already checked
   const int32_t *lo, *hi;  // both null: the whole map
   double min_clearance;

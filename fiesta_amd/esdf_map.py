@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, LegPathsInfo, LegPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, TimingParams, TimingResult, BoundsResult, Stats, TourInfo, TourResult, check
+from ._lib import BodyResult, ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, LegPathsInfo, LegPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, TimingParams, TimingResult, BoundsResult, Stats, TourInfo, TourResult, check
 from .refine_model import BOUNDS_VOID_BROKEN
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
@@ -99,6 +99,11 @@ def path_samples(waypoints, offsets, step):
 # fiesta_hip_path_cost_result, in struct order: (name, dtype, one row per "path" or per "waypoint", row shape)
 PATH_COST_FIELDS = (("cost", np.float64, "path", ()), ("grad", np.float64, "waypoint", (3,)), ("length", np.float64, "path", ()),
                     ("n_below", np.int64, "path", ()), ("n_samples", np.int64, "path", ()))
+
+
+# fiesta_hip_body_result, in struct order: (name, dtype, row shape; "K": one entry per sphere): one row per pose
+BODY_FIELDS = (("min_clearance", np.float64, ()), ("min_sphere", np.int32, ()), ("min_pos", np.float64, (3,)), ("min_grad", np.float64, (3,)),
+               ("n_below", np.int32, ()), ("cost", np.float64, ()), ("grad", np.float64, (6,)), ("sphere_clearance", np.float64, ("K",)))
 
 
 # fiesta_hip_refine_result, in struct order: (name, dtype, one row per "path" or per "waypoint", row shape)
@@ -628,6 +633,31 @@ class ESDFMap:
         res = PathCostResult(*[int(out.get(name, 0)) or None for name, _, _, _ in PATH_COST_FIELDS])
         check(self._lib.fiesta_hip_path_cost_dev(self._h, C.c_void_p(waypoints_dev_ptr), int(n_waypoints), C.c_void_p(offsets_dev_ptr),
                                                  int(n_paths), float(step), float(margin), C.byref(res)))
+
+    def BodyQuery(self, spheres, poses, margin) -> dict:
+        """fiesta_hip_body_query: a body of spheres ((K, 4): body-frame centre and radius) at a batch of poses ((N, 7): px, py, pz, qw,
+        qx, qy, qz; the quaternion need not be normalised).  Per pose the minimum of d - r over the spheres (d: GetDistWithGradTrilinear
+        at the sphere's world centre), the sphere that attains it, its position and gradient, the number of spheres below `margin`,
+        the penalty sum (margin - (d - r))^2 and its derivative with respect to the position and to a small world-frame rotation,
+        and every sphere's clearance -- a dict of numpy arrays named as the fields of fiesta_hip_body_result;
+        fiesta_amd.body_query_model is the definition"""
+        sph = np.ascontiguousarray(spheres, dtype=np.float64).reshape(-1, 4)
+        P = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        n, k = len(P), len(sph)
+        out = {name: np.empty((n,) + tuple(k if d == "K" else d for d in shape), dtype) for name, dtype, shape in BODY_FIELDS}
+        res = BodyResult(*[out[name].ctypes.data for name, _, _ in BODY_FIELDS])
+        check(self._lib.fiesta_hip_body_query(self._h, _p(sph), k, _p(P), n, float(margin), C.byref(res)))
+        return out
+
+    def BodyQueryDevice(self, spheres, poses_dev_ptr: int, n_poses: int, margin, out=None):
+        """fiesta_hip_body_query_dev: `spheres` is a host array as in BodyQuery, the poses (n_poses x 7 f64) and the outputs are
+        resident on the device (`out` maps field names of fiesta_hip_body_result to device pointers, missing fields are not
+        written); only enqueued on the map's stream"""
+        sph = np.ascontiguousarray(spheres, dtype=np.float64).reshape(-1, 4)
+        out = out or {}
+        res = BodyResult(*[int(out.get(name, 0)) or None for name, _, _ in BODY_FIELDS])
+        check(self._lib.fiesta_hip_body_query_dev(self._h, _p(sph), len(sph), C.c_void_p(poses_dev_ptr), int(n_poses), float(margin),
+                                                  C.byref(res)))
 
     def PathRefine(self, waypoints, offsets, bounds=None, *, margin, w_obstacle, w_smooth, alpha, max_step, tolerance=0.0,
                    iterations) -> dict:

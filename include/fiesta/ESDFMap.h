@@ -193,6 +193,56 @@ class ESDFMap {
                      const fiesta_hip_path_cost_result &result) {
     ck(fiesta_hip_path_cost(h_, waypoints, n_waypoints, offsets, n_paths, step, margin, &result));
   }
+  // Body queries (fiesta_hip_body_query; no reference counterpart): the robot as a set of spheres -- body-frame centre cx, cy, cz and
+  // radius r each -- checked at a batch of poses: position pos[i] (metres) and rotation rot[i] = qw, qx, qy, qz (it need not be
+  // normalised).  Per pose: the minimum of d - r over the spheres (d: GetDistWithGradTrilinear at the sphere's world centre), the
+  // lowest sphere that attains it, that sphere's position and gradient, the spheres below `margin`, the penalty sum (margin - (d - r))^2
+  // over those, its derivative with respect to the position (grad[0..2]) and to a small world-frame rotation about the body origin
+  // (grad[3..5]), and every sphere's clearance (row-major, spheres.size() per pose).  An invalid pose (a non-finite number, a zero
+  // quaternion) reads NaN / -1 and a gradient of 0.  Always answered on the device.  The formulas: include/fiesta_hip.h.
+  // (The rotation is four plain doubles and a sphere an array of four: the vector types of this header have three components.)
+  typedef std::vector<std::array<double, 4>> BodySpheres;
+  struct BodyResult {
+    std::vector<double> min_clearance;
+    std::vector<int32_t> min_sphere;
+    std::vector<Eigen::Vector3d> min_pos, min_grad;
+    std::vector<int32_t> n_below;
+    std::vector<double> cost;
+    std::vector<std::array<double, 6>> grad;
+    std::vector<double> sphere_clearance;
+    size_t count() const { return min_clearance.size(); }
+  };
+  BodyResult BodyQueryBatch(const BodySpheres &spheres, const std::vector<Eigen::Vector3d> &pos, const std::vector<std::array<double, 4>> &rot,
+                            double margin) {
+    if (pos.size() != rot.size()) throw std::invalid_argument("BodyQueryBatch: pos and rot differ in length");
+    const size_t n = pos.size(), k = spheres.size();
+    std::vector<double> sph(4 * k + 4), poses(7 * n + 7), mp(3 * n + 3), mg(3 * n + 3), g(6 * n + 6);  // (spare rows: never a null pointer)
+    for (size_t i = 0; i < k; ++i)
+      for (int c = 0; c < 4; ++c) sph[4 * i + c] = spheres[i][c];
+    for (size_t i = 0; i < n; ++i) {
+      for (int c = 0; c < 3; ++c) poses[7 * i + c] = pos[i](c);
+      for (int c = 0; c < 4; ++c) poses[7 * i + 3 + c] = rot[i][c];
+    }
+    BodyResult out;
+    out.min_clearance.resize(n + 1), out.min_sphere.resize(n + 1), out.n_below.resize(n + 1), out.cost.resize(n + 1);
+    out.sphere_clearance.resize(n * k + 1);
+    const fiesta_hip_body_result r{out.min_clearance.data(), out.min_sphere.data(), mp.data(), mg.data(), out.n_below.data(), out.cost.data(),
+                                   g.data(), out.sphere_clearance.data()};
+    ck(fiesta_hip_body_query(h_, sph.data(), (int32_t)k, poses.data(), (int64_t)n, margin, &r));
+    out.min_clearance.resize(n), out.min_sphere.resize(n), out.n_below.resize(n), out.cost.resize(n), out.sphere_clearance.resize(n * k);
+    out.min_pos.resize(n), out.min_grad.resize(n), out.grad.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      out.min_pos[i] = Eigen::Vector3d(mp[3 * i], mp[3 * i + 1], mp[3 * i + 2]);
+      out.min_grad[i] = Eigen::Vector3d(mg[3 * i], mg[3 * i + 1], mg[3 * i + 2]);
+      for (int c = 0; c < 6; ++c) out.grad[i][c] = g[6 * i + c];
+    }
+    return out;
+  }
+  // The scalar convenience: does the body keep `margin` from every obstacle at this pose?  (false for an invalid pose)
+  bool IsPoseFree(const BodySpheres &spheres, const Eigen::Vector3d &pos, const std::array<double, 4> &rot, double margin) {
+    return BodyQueryBatch(spheres, {pos}, {rot}, margin).min_clearance[0] >= margin;
+  }
+
   // Sample `index` of the polyline by the header's rule, on the host (bit for bit what the library evaluates there); NaN if the
   // path has no such sample or is invalid.  Header-only, so compiled with the includer's flags: the exactness include/fiesta_hip.h
   // promises holds only without floating-point contraction -- build the including file with -ffp-contract=off.  g++'s default

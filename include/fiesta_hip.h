@@ -134,8 +134,8 @@ const char *fiesta_hip_last_error(void);
  * fiesta_hip_reach_paths[_dev] came later without a new number, and so did fiesta_hip_cluster_voxels[_dev],
  * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_site_tour[_dev], fiesta_hip_free_boxes[_dev],
  * fiesta_hip_path_corridor[_dev], fiesta_hip_path_refine[_dev], fiesta_hip_corridor_bounds[_dev],
- * fiesta_hip_split_clusters[_dev], fiesta_hip_leg_paths[_dev] and fiesta_hip_path_timing[_dev]: detect them by symbol lookup
- * (dlsym). */
+ * fiesta_hip_split_clusters[_dev], fiesta_hip_leg_paths[_dev], fiesta_hip_path_timing[_dev], fiesta_hip_get_skeleton_voxels[_dev]
+ * and fiesta_hip_body_query[_dev]: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -407,6 +407,74 @@ int fiesta_hip_path_cost(fiesta_hip_map *m, const double *waypoints, int64_t n_w
                          double step, double margin, const fiesta_hip_path_cost_result *result);
 int fiesta_hip_path_cost_dev(fiesta_hip_map *m, const double *waypoints_dev, int64_t n_waypoints, const int64_t *offsets_dev,
                              int64_t n_paths, double step, double margin, const fiesta_hip_path_cost_result *result);
+
+/* ---- body queries, batched: a robot body given as a set of spheres, checked at many poses ----
+ * Every call above treats the robot as a point (its size is one scalar: margin, min_clearance).  A sampling planner checks a
+ * candidate POSE of a body that is not round -- does anything touch, how close is it, where; an optimiser that models the body as
+ * spheres needs per pose the summed obstacle penalty and its derivative with respect to the pose, a force and a torque.  No
+ * reference counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.
+ * Input:
+ *   spheres    f64 x 4 per sphere: the body-frame centre cx, cy, cz and the radius r; n_spheres in 1 .. FIESTA_HIP_BODY_MAX_SPHERES.
+ *              A HOST pointer in BOTH variants (a property of the robot, small, validated by the call); the call copies it to the
+ *              map's scratch on the map's stream, and the caller may reuse it as soon as the call returns.
+ *   poses      f64 x 7 per pose: px, py, pz (metres), qw, qx, qy, qz.  The quaternion need not be normalised.
+ *   margin     finite.
+ * Per pose, in f64, each operation rounded once (the library is built with -ffp-contract=off), in exactly this order:
+ *   s  = ((qw*qw + qx*qx) + qy*qy) + qz*qz;   k = 2.0 / s
+ *   the pose is VALID iff its seven numbers are finite, s > 0 and k is finite
+ *   xx=qx*qx  yy=qy*qy  zz=qz*qz  xy=qx*qy  xz=qx*qz  yz=qy*qz  wx=qw*qx  wy=qw*qy  wz=qw*qz
+ *   R00 = 1.0 - k*(yy+zz)   R01 = k*(xy-wz)         R02 = k*(xz+wy)
+ *   R10 = k*(xy+wz)         R11 = 1.0 - k*(xx+zz)   R12 = k*(yz-wx)
+ *   R20 = k*(xz-wy)         R21 = k*(yz+wx)         R22 = 1.0 - k*(xx+yy)
+ * Per sphere i of a valid pose:
+ *   a[c] = (Rc0*cx + Rc1*cy) + Rc2*cz;   x[c] = p[c] + a[c]
+ *   (d, g) = fiesta_hip_get_dist_grad's value and gradient at x, bit for bit (the path calls' evaluator)
+ *   s_i = d - r
+ *   if s_i < margin:  e = margin - s_i;  phi = e*e;  psi = -2.0*e;  gamma[c] = psi*g[c]     else phi = 0, gamma = 0   (path cost's penalty)
+ *   t[0] = a[1]*gamma[2] - a[2]*gamma[1];  t[1] = a[2]*gamma[0] - a[0]*gamma[2];  t[2] = a[0]*gamma[1] - a[1]*gamma[0]
+ * A sphere centre outside a dense map or in never-observed space reads what the point query reads there (-1 with gradient 0; the
+ * +10000 corners): no special case, exactly as in path cost.
+ * Outputs; every pointer of the result is nullable:
+ *   min_clearance     per pose: the minimum over i of s_i
+ *   min_sphere        per pose: the LOWEST i that attains it (compared with <)
+ *   min_pos, min_grad per pose (x3): x and g of that sphere
+ *   n_below           per pose: spheres with s_i < margin (strictly)
+ *   cost              per pose: sum phi
+ *   grad (x6)         per pose: sum gamma -- the derivative of cost with respect to p -- then sum t, the derivative with respect to a
+ *                     small world-frame rotation vector theta about the body origin, R <- exp([theta]x) R
+ *   sphere_clearance  per pose x sphere, row-major: s_i (per-link costs; callers with a penalty of their own)
+ * Every TERM above (x, s_i, phi, gamma, t) is bit-identical on the device and in fiesta_amd.body_query_model (numpy), and
+ * sphere_clearance, min_clearance, min_sphere, min_pos, min_grad and n_below are exact.  Only the order in which the n_spheres terms
+ * are added into cost and grad is left free; it is FIXED BY n_spheres ALONE (a team of T lanes per pose, T the smallest power of
+ * two >= n_spheres and at most 64: lane t adds spheres t, t + T, ... in that order, then a butterfly over the team), so the bits
+ * of a pose's outputs depend neither on n_poses, nor on the pose's place in the batch, nor on the variant, the launch shape or
+ * scheduling.  Against another order of summation cost and grad differ by at most path cost's bound (n + 16) * 2^-52 * a, n =
+ * n_spheres, a = the sum of the absolute values of the output's terms.  No floating-point atomics.
+ * Invalid pose: min_clearance, cost, its min_pos / min_grad and its sphere_clearance row NaN; min_sphere and n_below -1; its grad
+ * row 0.  The other poses are unaffected.  Validity is decided on the device.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable, fiesta_hip_last_error() names the cause): a
+ * null map; n_spheres outside 1 .. 1024; n_poses < 0; a null spheres; a null poses with n_poses > 0; a null result; a sphere whose
+ * centre or radius is not finite or whose radius is < 0; a margin that is not finite.  n_poses = 0 does nothing.
+ * The call is read-only and reads the field as it stands: before fiesta_hip_update_esdf has run it answers from the old field
+ * (the path calls' rule).
+ * fiesta_hip_body_query      poses and results are host pointers; stages, runs, synchronises.  Always on the device.
+ * fiesta_hip_body_query_dev  poses and every result array are device pointers (the struct itself and spheres are host objects);
+ *                            only enqueued on the map's stream. */
+#define FIESTA_HIP_BODY_MAX_SPHERES 1024
+typedef struct fiesta_hip_body_result {
+  double *min_clearance;
+  int32_t *min_sphere;
+  double *min_pos;
+  double *min_grad;
+  int32_t *n_below;
+  double *cost;
+  double *grad;
+  double *sphere_clearance;
+} fiesta_hip_body_result;
+int fiesta_hip_body_query(fiesta_hip_map *m, const double *spheres, int32_t n_spheres, const double *poses, int64_t n_poses, double margin,
+                          const fiesta_hip_body_result *result);
+int fiesta_hip_body_query_dev(fiesta_hip_map *m, const double *spheres, int32_t n_spheres, const double *poses_dev, int64_t n_poses,
+                              double margin, const fiesta_hip_body_result *result);
 
 /* ---- frontier voxels: observed-free voxels that border never-observed space, compacted on the device ----
  * What an exploration planner asks after every frame: where does known free space end, and which of those places can the robot
