@@ -63,7 +63,7 @@ DenseMap &dense(fiesta_hip_map *m, const char *what) {
 }
 // The planner calls: one body per host / _dev pair.  Each checks the whole-call errors of include/fiesta_hip.h on the arguments as
 // the ABI took them (the call's aggregate of planner_args.hpp), then hands the same object on to the call's function of planner.hpp,
-// with the store's planner_ctx() and -- the twelve calls that read voxels -- its planner_view(does the call read the bitmaps?).
+// with the store's planner_ctx() and -- the thirteen calls that read voxels -- its planner_view(does the call read the bitmaps?).
 
 // shared by path_clearance and path_cost (R: the call's result struct); a host batch: the CSR rules as well
 template <typename R>
@@ -97,6 +97,26 @@ void body_query(fiesta_hip_map *m, const fiesta::BodyArgs &a) {
   for (int32_t i = 0; i < a.n_spheres; ++i) need(a.spheres[4 * i + 3] >= 0, "body_query: a sphere's radius is negative");
   need(std::isfinite(a.margin), "body_query: margin must be finite");
   on_store(m, [&](auto &s) { fiesta::body_query(s.planner_ctx(), s.planner_view(false), a); });
+}
+// fiesta_hip_articulated_query: as body_query; the sphere table and its frame indices are host pointers in both variants
+void articulated_query(fiesta_hip_map *m, const fiesta::ArticulatedArgs &a) {
+  need(m != nullptr, "null map handle");
+  need(a.n_spheres >= 1 && a.n_spheres <= FIESTA_HIP_BODY_MAX_SPHERES, "articulated_query: n_spheres must be 1 .. 1024");
+  need(a.n_frames >= 1 && a.n_frames <= FIESTA_HIP_BODY_MAX_FRAMES, "articulated_query: n_frames must be 1 .. 64");
+  need(a.n_configs >= 0, "articulated_query: negative count");
+  need(a.spheres != nullptr, "articulated_query: spheres is null");
+  need(a.sphere_frame != nullptr, "articulated_query: sphere_frame is null");
+  need(a.frame_poses != nullptr || a.n_configs == 0, "articulated_query: frame_poses is null");
+  need(a.res != nullptr, "articulated_query: result is null");
+  for (int64_t i = 0; i < 4 * (int64_t)a.n_spheres; ++i)
+    need(std::isfinite(a.spheres[i]), "articulated_query: a sphere's centre or radius is not finite");
+  for (int32_t i = 0; i < a.n_spheres; ++i) need(a.spheres[4 * i + 3] >= 0, "articulated_query: a sphere's radius is negative");
+  for (int32_t i = 0; i < a.n_spheres; ++i)
+    need(a.sphere_frame[i] >= 0 && a.sphere_frame[i] < a.n_frames, "articulated_query: a frame index is outside 0 .. n_frames - 1");
+  for (int32_t i = 1; i < a.n_spheres; ++i)
+    need(a.sphere_frame[i] >= a.sphere_frame[i - 1], "articulated_query: the spheres are not grouped by frame (sphere_frame decreases)");
+  need(std::isfinite(a.margin), "articulated_query: margin must be finite");
+  on_store(m, [&](auto &s) { fiesta::articulated_query(s.planner_ctx(), s.planner_view(false), a); });
 }
 // n_out: the variant's total (host or device pointer); returns the host variant's total
 int64_t frontier_voxels(fiesta_hip_map *m, const fiesta::FrontierArgs &a, const void *n_out) {
@@ -735,6 +755,15 @@ int fiesta_hip_body_query(fiesta_hip_map *m, const double *spheres, int32_t n_sp
 int fiesta_hip_body_query_dev(fiesta_hip_map *m, const double *spheres, int32_t n_spheres, const double *poses_dev, int64_t n_poses, double margin,
                               const fiesta_hip_body_result *result) {
   return guarded([&] { body_query(m, {spheres, n_spheres, poses_dev, n_poses, margin, result, true}); });
+}
+int fiesta_hip_articulated_query(fiesta_hip_map *m, const double *spheres, const int32_t *sphere_frame, int32_t n_spheres, int32_t n_frames,
+                                 const double *frame_poses, int64_t n_configs, double margin, const fiesta_hip_articulated_result *result) {
+  return guarded([&] { articulated_query(m, {spheres, sphere_frame, n_spheres, n_frames, frame_poses, n_configs, margin, result, false}); });
+}
+int fiesta_hip_articulated_query_dev(fiesta_hip_map *m, const double *spheres, const int32_t *sphere_frame, int32_t n_spheres, int32_t n_frames,
+                                     const double *frame_poses_dev, int64_t n_configs, double margin,
+                                     const fiesta_hip_articulated_result *result) {
+  return guarded([&] { articulated_query(m, {spheres, sphere_frame, n_spheres, n_frames, frame_poses_dev, n_configs, margin, result, true}); });
 }
 int fiesta_hip_get_frontier_voxels(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance, int32_t *vox,
                                    uint8_t *mask, int64_t capacity, int64_t *n_out) {

@@ -4,6 +4,7 @@
 
 #include "dense_read.hpp"
 #include "hash_read.hpp"
+#include "articulated_kernels.hpp"
 #include "body_kernels.hpp"
 #include "bounds_kernels.hpp"
 #include "cluster_kernels.hpp"
@@ -59,6 +60,11 @@ template <class View>
 void body_query(const PlannerCtx &ctx, const View &v, const BodyArgs &a) {
   if (a.n_poses <= 0) return;
   use_device(ctx), body_query_run(ctx.stream, ctx.S, v.path_eval(), a);
+}
+template <class View>
+void articulated_query(const PlannerCtx &ctx, const View &v, const ArticulatedArgs &a) {
+  if (a.n_configs <= 0) return;
+  use_device(ctx), articulated_query_run(ctx.stream, ctx.S, v.path_eval(), a);
 }
 
 // The frontier call's store side: frontier_box gives the kernel's box, whether it is empty and (returned) the most entries it can yield,
@@ -200,6 +206,7 @@ void view_coverage(const PlannerCtx &ctx, const View &v, const ViewArgs &a) {
   template void path_refine(const PlannerCtx &, const VIEW &, const PathRefineArgs &);                                                   \
   template void path_timing(const PlannerCtx &, const VIEW &, const PathTimingArgs &);                                                   \
   template void body_query(const PlannerCtx &, const VIEW &, const BodyArgs &);                                                          \
+  template void articulated_query(const PlannerCtx &, const VIEW &, const ArticulatedArgs &);                                            \
   template int64_t frontier_voxels(const PlannerCtx &, const VIEW &, const FrontierArgs &);                                              \
   template int64_t skeleton_voxels(const PlannerCtx &, const VIEW &, const SkeletonArgs &);                                              \
   template void ray_query(const PlannerCtx &, const VIEW &, const RayArgs &);                                                            \

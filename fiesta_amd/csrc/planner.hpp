@@ -1,7 +1,7 @@
 // fiesta_amd/csrc/planner.hpp -- what a map keeps for the planner calls, and the calls themselves.
 //
-// Both stores own one PlannerScratch.  The eighteen calls are the free functions at the end of this header, defined once in
-// planner.hip, the only unit that includes the planner kernel headers: six need nothing of a map but its planner_ctx(); twelve also
+// Both stores own one PlannerScratch.  The nineteen calls are the free functions at the end of this header, defined once in
+// planner.hip, the only unit that includes the planner kernel headers: six need nothing of a map but its planner_ctx(); thirteen also
 // read voxels, through the store's planner_view() (dense_read.hpp: DenseView, hash_read.hpp: HashView).
 #pragma once
 #include <algorithm>
@@ -132,6 +132,7 @@ struct Staging {
 template <typename R>
 struct PathArgs;
 struct BodyArgs;
+struct ArticulatedArgs;
 struct FrontierArgs;
 struct SkeletonArgs;
 struct RayArgs;
@@ -173,6 +174,9 @@ void path_timing(const PlannerCtx &ctx, const View &v, const PathTimingArgs &a);
 // fiesta_hip_body_query[_dev]: the path calls' evaluator at the sphere centres of a body (always on the device)
 template <class View>
 void body_query(const PlannerCtx &ctx, const View &v, const BodyArgs &a);
+// fiesta_hip_articulated_query[_dev]: the same at the spheres of several frames, one pose per frame (always on the device)
+template <class View>
+void articulated_query(const PlannerCtx &ctx, const View &v, const ArticulatedArgs &a);
 // fiesta_hip_get_frontier_voxels[_dev]: returns the host variant's total (which may exceed the capacity)
 template <class View>
 int64_t frontier_voxels(const PlannerCtx &ctx, const View &v, const FrontierArgs &a);

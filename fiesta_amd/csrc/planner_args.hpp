@@ -32,6 +32,17 @@ struct BodyArgs {  // the call's arguments as fiesta_hip_body_query[_dev] takes 
   bool dev;
 };
 
+struct ArticulatedArgs {  // the call's arguments as fiesta_hip_articulated_query[_dev] takes them, already checked
+  const double *spheres;        // host pointers in both variants: cx, cy, cz, r per sphere (in its frame) and the sphere's frame,
+  const int32_t *sphere_frame;  // non-decreasing, 0 .. n_frames - 1
+  int32_t n_spheres, n_frames;
+  const double *frame_poses;  // n_configs x n_frames x 7
+  int64_t n_configs;
+  double margin;
+  const fiesta_hip_articulated_result *res;
+  bool dev;
+};
+
 struct FrontierArgs {  // the call's arguments as fiesta_hip_get_frontier_voxels[_dev] takes them, already checked
   const int32_t *lo, *hi;  // both null: the whole map
   double min_clearance;

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BodyResult, ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, LegPathsInfo, LegPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, TimingParams, TimingResult, BoundsResult, Stats, TourInfo, TourResult, check
+from ._lib import ArticulatedResult, BodyResult,ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, LegPathsInfo, LegPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, TimingParams, TimingResult, BoundsResult, Stats, TourInfo, TourResult, check
 from .refine_model import BOUNDS_VOID_BROKEN
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
@@ -104,6 +104,11 @@ PATH_COST_FIELDS = (("cost", np.float64, "path", ()), ("grad", np.float64, "wayp
 # fiesta_hip_body_result, in struct order: (name, dtype, row shape; "K": one entry per sphere): one row per pose
 BODY_FIELDS = (("min_clearance", np.float64, ()), ("min_sphere", np.int32, ()), ("min_pos", np.float64, (3,)), ("min_grad", np.float64, (3,)),
                ("n_below", np.int32, ()), ("cost", np.float64, ()), ("grad", np.float64, (6,)), ("sphere_clearance", np.float64, ("K",)))
+# fiesta_hip_articulated_result, in struct order: (name, dtype, row shape; "K": one entry per sphere, "F": per frame): one row per configuration
+ARTICULATED_FIELDS = (("min_clearance", np.float64, ()), ("min_sphere", np.int32, ()), ("min_pos", np.float64, (3,)),
+                      ("min_grad", np.float64, (3,)), ("n_below", np.int32, ()), ("cost", np.float64, ()),
+                      ("frame_clearance", np.float64, ("F",)), ("frame_cost", np.float64, ("F",)), ("frame_grad", np.float64, ("F", 6)),
+                      ("sphere_clearance", np.float64, ("K",)))
 
 
 # fiesta_hip_refine_result, in struct order: (name, dtype, one row per "path" or per "waypoint", row shape)
@@ -658,6 +663,38 @@ class ESDFMap:
         res = BodyResult(*[int(out.get(name, 0)) or None for name, _, _ in BODY_FIELDS])
         check(self._lib.fiesta_hip_body_query_dev(self._h, _p(sph), len(sph), C.c_void_p(poses_dev_ptr), int(n_poses), float(margin),
                                                   C.byref(res)))
+
+    def ArticulatedQuery(self, spheres, sphere_frame, frame_poses, margin) -> dict:
+        """fiesta_hip_articulated_query: spheres on frames ((K, 4): centre in the frame of its own link and radius; sphere_frame (K,):
+        the sphere's frame, non-decreasing) at a batch of configurations, one pose per frame (frame_poses (N, F, 7): px, py, pz, qw,
+        qx, qy, qz; F is read from its shape).  Per configuration BodyQuery's minimum, sphere, position, gradient, count and cost over
+        all spheres; per configuration and frame the minimum clearance, the cost and its derivative with respect to that frame's
+        position and to a small world-frame rotation about its origin; and every sphere's clearance -- a dict of numpy arrays named
+        as the fields of fiesta_hip_articulated_result; fiesta_amd.articulated_query_model is the definition"""
+        sph = np.ascontiguousarray(spheres, dtype=np.float64).reshape(-1, 4)
+        frm = np.ascontiguousarray(sphere_frame, dtype=np.int32).reshape(-1)
+        P = np.ascontiguousarray(frame_poses, dtype=np.float64)
+        if P.ndim != 3 or P.shape[2] != 7 or len(frm) != len(sph):
+            raise ValueError("ArticulatedQuery: frame_poses must be (N, F, 7) and sphere_frame hold one index per sphere")
+        n, f, k = P.shape[0], P.shape[1], len(sph)
+        dims = {"K": k, "F": f}
+        out = {name: np.empty((n,) + tuple(dims.get(d, d) for d in shape), dtype) for name, dtype, shape in ARTICULATED_FIELDS}
+        res = ArticulatedResult(*[out[name].ctypes.data for name, _, _ in ARTICULATED_FIELDS])
+        check(self._lib.fiesta_hip_articulated_query(self._h, _p(sph), _p(frm), k, f, _p(P), n, float(margin), C.byref(res)))
+        return out
+
+    def ArticulatedQueryDevice(self, spheres, sphere_frame, n_frames: int, frame_poses_dev_ptr: int, n_configs: int, margin, out=None):
+        """fiesta_hip_articulated_query_dev: `spheres` and `sphere_frame` are host arrays as in ArticulatedQuery, the frame poses
+        (n_configs x n_frames x 7 f64) and the outputs are resident on the device (`out` maps field names of
+        fiesta_hip_articulated_result to device pointers, missing fields are not written); only enqueued on the map's stream"""
+        sph = np.ascontiguousarray(spheres, dtype=np.float64).reshape(-1, 4)
+        frm = np.ascontiguousarray(sphere_frame, dtype=np.int32).reshape(-1)
+        if len(frm) != len(sph):
+            raise ValueError("ArticulatedQueryDevice: sphere_frame must hold one index per sphere")
+        out = out or {}
+        res = ArticulatedResult(*[int(out.get(name, 0)) or None for name, _, _ in ARTICULATED_FIELDS])
+        check(self._lib.fiesta_hip_articulated_query_dev(self._h, _p(sph), _p(frm), len(sph), int(n_frames), C.c_void_p(frame_poses_dev_ptr),
+                                                         int(n_configs), float(margin), C.byref(res)))
 
     def PathRefine(self, waypoints, offsets, bounds=None, *, margin, w_obstacle, w_smooth, alpha, max_step, tolerance=0.0,
                    iterations) -> dict:

@@ -242,6 +242,62 @@ class ESDFMap {
   bool IsPoseFree(const BodySpheres &spheres, const Eigen::Vector3d &pos, const std::array<double, 4> &rot, double margin) {
     return BodyQueryBatch(spheres, {pos}, {rot}, margin).min_clearance[0] >= margin;
   }
+  // Articulated body queries (fiesta_hip_articulated_query; no reference counterpart): spheres on FRAMES -- the links of an arm, a
+  // drone and its slung load, the robots of a formation.  sphere_frame[i] is the frame of sphere i, non-decreasing over the table
+  // (the spheres are grouped by frame; a frame may own none), a sphere's centre is given in the frame of its own link.  frame_poses
+  // holds one pose per configuration and frame, configuration-major, seven doubles each: px, py, pz, qw, qx, qy, qz (it need not be
+  // normalised); the number of configurations is frame_poses.size() / (7 * n_frames).  Forward kinematics is the caller's.  Per
+  // configuration: BodyQueryBatch's minimum, sphere, position, gradient, count and cost over all spheres.  Per configuration and
+  // frame (row-major, n_frames per configuration): the minimum clearance of the frame's spheres (+inf without spheres), their cost,
+  // and its derivative with respect to the frame's position (frame_grad[..][0..2]) and to a small world-frame rotation about the
+  // frame's origin (frame_grad[..][3..5]) -- what a caller multiplies with its geometric Jacobian.  An invalid configuration (a
+  // non-finite number or a zero quaternion in ANY of its frame poses) reads NaN / -1 and gradients of 0.  Self-collision between
+  // the links is not checked.  Always answered on the device.  The formulas: include/fiesta_hip.h.
+  struct ArticulatedResult {
+    std::vector<double> min_clearance;
+    std::vector<int32_t> min_sphere;
+    std::vector<Eigen::Vector3d> min_pos, min_grad;
+    std::vector<int32_t> n_below;
+    std::vector<double> cost;
+    std::vector<double> frame_clearance, frame_cost;
+    std::vector<std::array<double, 6>> frame_grad;
+    std::vector<double> sphere_clearance;
+    size_t count() const { return min_clearance.size(); }
+  };
+  ArticulatedResult ArticulatedQueryBatch(const BodySpheres &spheres, const std::vector<int32_t> &sphere_frame, int n_frames,
+                                          const std::vector<double> &frame_poses, double margin) {
+    if (sphere_frame.size() != spheres.size()) throw std::invalid_argument("ArticulatedQueryBatch: spheres and sphere_frame differ in length");
+    if (n_frames < 1 || frame_poses.size() % (7 * (size_t)n_frames)) throw std::invalid_argument("ArticulatedQueryBatch: frame_poses is not n x n_frames x 7");
+    const size_t k = spheres.size(), f = (size_t)n_frames, n = frame_poses.size() / (7 * f);
+    std::vector<double> sph(4 * k + 4), poses(frame_poses), mp(3 * n + 3), mg(3 * n + 3), g(6 * n * f + 6);  // (spare rows: never a null pointer)
+    std::vector<int32_t> frm(sphere_frame);
+    poses.resize(7 * n * f + 7), frm.resize(k + 1);
+    for (size_t i = 0; i < k; ++i)
+      for (int c = 0; c < 4; ++c) sph[4 * i + c] = spheres[i][c];
+    ArticulatedResult out;
+    out.min_clearance.resize(n + 1), out.min_sphere.resize(n + 1), out.n_below.resize(n + 1), out.cost.resize(n + 1);
+    out.frame_clearance.resize(n * f + 1), out.frame_cost.resize(n * f + 1), out.sphere_clearance.resize(n * k + 1);
+    const fiesta_hip_articulated_result r{out.min_clearance.data(), out.min_sphere.data(), mp.data(), mg.data(), out.n_below.data(), out.cost.data(),
+                                          out.frame_clearance.data(), out.frame_cost.data(), g.data(), out.sphere_clearance.data()};
+    ck(fiesta_hip_articulated_query(h_, sph.data(), frm.data(), (int32_t)k, (int32_t)n_frames, poses.data(), (int64_t)n, margin, &r));
+    out.min_clearance.resize(n), out.min_sphere.resize(n), out.n_below.resize(n), out.cost.resize(n), out.sphere_clearance.resize(n * k);
+    out.frame_clearance.resize(n * f), out.frame_cost.resize(n * f);
+    out.min_pos.resize(n), out.min_grad.resize(n), out.frame_grad.resize(n * f);
+    for (size_t i = 0; i < n; ++i) {
+      out.min_pos[i] = Eigen::Vector3d(mp[3 * i], mp[3 * i + 1], mp[3 * i + 2]);
+      out.min_grad[i] = Eigen::Vector3d(mg[3 * i], mg[3 * i + 1], mg[3 * i + 2]);
+    }
+    for (size_t i = 0; i < n * f; ++i)
+      for (int c = 0; c < 6; ++c) out.frame_grad[i][c] = g[6 * i + c];
+    return out;
+  }
+  // The scalar convenience: does the body keep `margin` from every obstacle in this ONE configuration (frame_poses: n_frames x 7)?
+  // (false for an invalid configuration)
+  bool IsConfigurationFree(const BodySpheres &spheres, const std::vector<int32_t> &sphere_frame, int n_frames,
+                           const std::vector<double> &frame_poses, double margin) {
+    if (n_frames < 1 || frame_poses.size() != 7 * (size_t)n_frames) throw std::invalid_argument("IsConfigurationFree: frame_poses is not n_frames x 7");
+    return ArticulatedQueryBatch(spheres, sphere_frame, n_frames, frame_poses, margin).min_clearance[0] >= margin;
+  }
 
   // Sample `index` of the polyline by the header's rule, on the host (bit for bit what the library evaluates there); NaN if the
   // path has no such sample or is invalid.  Header-only, so compiled with the includer's flags: the exactness include/fiesta_hip.h

@@ -134,8 +134,8 @@ const char *fiesta_hip_last_error(void);
  * fiesta_hip_reach_paths[_dev] came later without a new number, and so did fiesta_hip_cluster_voxels[_dev],
  * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_site_tour[_dev], fiesta_hip_free_boxes[_dev],
  * fiesta_hip_path_corridor[_dev], fiesta_hip_path_refine[_dev], fiesta_hip_corridor_bounds[_dev],
- * fiesta_hip_split_clusters[_dev], fiesta_hip_leg_paths[_dev], fiesta_hip_path_timing[_dev], fiesta_hip_get_skeleton_voxels[_dev]
- * and fiesta_hip_body_query[_dev]: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_split_clusters[_dev], fiesta_hip_leg_paths[_dev], fiesta_hip_path_timing[_dev], fiesta_hip_get_skeleton_voxels[_dev],
+ * fiesta_hip_body_query[_dev] and fiesta_hip_articulated_query[_dev]: detect them by symbol lookup (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -475,6 +475,81 @@ int fiesta_hip_body_query(fiesta_hip_map *m, const double *spheres, int32_t n_sp
                           const fiesta_hip_body_result *result);
 int fiesta_hip_body_query_dev(fiesta_hip_map *m, const double *spheres, int32_t n_spheres, const double *poses_dev, int64_t n_poses,
                               double margin, const fiesta_hip_body_result *result);
+
+/* ---- articulated body queries, batched: spheres on frames, one pose per frame and configuration ----
+ * The body call above moves one rigid set of spheres.  An arm, a drone with a gimbal or a slung load, a formation of several robots
+ * is a set of rigid links -- FRAMES -- each with spheres of its own.  Here every sphere names its frame, a CONFIGURATION gives one
+ * pose per frame, and one call returns per configuration what the body call returns per pose and, per frame, the clearance, the
+ * penalty and the force and torque on that frame -- what a caller multiplies with its geometric Jacobian.  Forward kinematics is
+ * the caller's: it needs sin / cos, whose bits differ between hosts and the device.  Self-collision between the links is not
+ * checked.  No reference counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.
+ * Input:
+ *   spheres       f64 x 4 per sphere: the centre cx, cy, cz in the frame of its own link and the radius r; n_spheres in
+ *                 1 .. FIESTA_HIP_BODY_MAX_SPHERES.
+ *   sphere_frame  i32 per sphere: its frame, in 0 .. n_frames - 1, NON-DECREASING over the table (the spheres are grouped by frame;
+ *                 fiesta_amd.group_spheres_by_frame sorts a table that is not).  A frame may own no sphere.
+ *                 Both are HOST pointers in BOTH variants, as the body call's table: copied on the map's stream, free for reuse
+ *                 as soon as the call returns.
+ *   n_frames      F, in 1 .. FIESTA_HIP_BODY_MAX_FRAMES.
+ *   frame_poses   f64 x 7 per configuration and frame, configuration-major (n_configs x F x 7): px, py, pz (metres), qw, qx, qy, qz.
+ *                 The quaternions need not be normalised.
+ *   margin        finite.
+ * Per configuration n and frame f the rotation R and the validity of the pose are the body call's rule above, operation by
+ * operation (s, k = 2.0 / s, the nine products, R00 .. R22); p is the pose's position.  A configuration is VALID iff all F frame
+ * poses are valid by that rule, the poses of frames that own no sphere included.
+ * Per sphere i of frame f of a valid configuration, with R, p of frame f, the body call's terms verbatim:
+ *   a[c] = (Rc0*cx + Rc1*cy) + Rc2*cz;   x[c] = p[c] + a[c];   (d, g) = the point query at x;   s_i = d - r
+ *   phi, gamma[c] = path cost's penalty of s_i against margin;   t = a x gamma, component by component as written above
+ * Outputs; every pointer of the result is nullable:
+ *   min_clearance     per configuration: the minimum over ALL spheres of s_i
+ *   min_sphere        per configuration: the LOWEST i that attains it (compared with <), whatever its frame
+ *   min_pos, min_grad per configuration (x3): x and g of that sphere
+ *   n_below           per configuration: spheres with s_i < margin (strictly)
+ *   cost              per configuration: sum phi over all spheres
+ *   frame_clearance   per configuration x frame: the minimum of s_i over the frame's spheres; +inf for a frame without spheres
+ *   frame_cost        per configuration x frame: sum phi over the frame's spheres (0 without spheres)
+ *   frame_grad (x6)   per configuration x frame: sum gamma, then sum t, over the frame's spheres (0 without spheres): the derivative
+ *                     of the configuration's cost with respect to frame f's position and to a small world-frame rotation vector
+ *                     theta about frame f's origin, R_f <- exp([theta]x) R_f, the other frames fixed
+ *   sphere_clearance  per configuration x sphere, row-major: s_i
+ * Every TERM is bit-identical on the device and in fiesta_amd.articulated_query_model (numpy); min_clearance, min_sphere, min_pos,
+ * min_grad, n_below, frame_clearance and sphere_clearance are exact.  Only the order in which terms are added into cost, frame_cost
+ * and frame_grad is left free; it is FIXED BY n_spheres AND sphere_frame ALONE (a team of T lanes per configuration, T as in the body
+ * call; per pass of T consecutive spheres and per frame present in it a butterfly over the team, the passes of a frame added in
+ * order; cost is the frame costs added in frame order), so the bits of a configuration's outputs depend neither on n_configs, nor
+ * on its place in the batch, nor on the variant, the launch shape or scheduling.  Against another order of summation they differ by
+ * at most (n + 16) * 2^-52 * a, n = the number of summed terms (the frame's sphere count; n_spheres for cost), a = the sum of the
+ * absolute values of the output's terms.  No floating-point atomics.
+ * Invalid configuration: min_clearance, cost, its min_pos / min_grad and its frame_clearance, frame_cost and sphere_clearance rows
+ * NaN; min_sphere and n_below -1; its frame_grad rows 0.  The other configurations are unaffected.  Validity is decided on the device.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable, fiesta_hip_last_error() names the cause): a
+ * null map; n_spheres outside 1 .. 1024; n_frames outside 1 .. 64; n_configs < 0; a null spheres or sphere_frame; a null
+ * frame_poses with n_configs > 0; a null result; a sphere whose centre or radius is not finite or whose radius is < 0; a frame index
+ * outside 0 .. n_frames - 1; frame indices that decrease (not grouped by frame); a margin that is not finite.  n_configs = 0 does
+ * nothing.
+ * The call is read-only and reads the field as it stands: before fiesta_hip_update_esdf has run it answers from the old field
+ * (the path calls' rule).
+ * fiesta_hip_articulated_query      frame poses and results are host pointers; stages, runs, synchronises.  Always on the device.
+ * fiesta_hip_articulated_query_dev  frame poses and every result array are device pointers (the struct itself, spheres and
+ *                                   sphere_frame are host objects); only enqueued on the map's stream. */
+#define FIESTA_HIP_BODY_MAX_FRAMES 64
+typedef struct fiesta_hip_articulated_result {
+  double *min_clearance;
+  int32_t *min_sphere;
+  double *min_pos;
+  double *min_grad;
+  int32_t *n_below;
+  double *cost;
+  double *frame_clearance;
+  double *frame_cost;
+  double *frame_grad;
+  double *sphere_clearance;
+} fiesta_hip_articulated_result;
+int fiesta_hip_articulated_query(fiesta_hip_map *m, const double *spheres, const int32_t *sphere_frame, int32_t n_spheres, int32_t n_frames,
+                                 const double *frame_poses, int64_t n_configs, double margin, const fiesta_hip_articulated_result *result);
+int fiesta_hip_articulated_query_dev(fiesta_hip_map *m, const double *spheres, const int32_t *sphere_frame, int32_t n_spheres,
+                                     int32_t n_frames, const double *frame_poses_dev, int64_t n_configs, double margin,
+                                     const fiesta_hip_articulated_result *result);
 
 /* ---- frontier voxels: observed-free voxels that border never-observed space, compacted on the device ----
  * What an exploration planner asks after every frame: where does known free space end, and which of those places can the robot
