@@ -8,6 +8,7 @@ from .esdf_map import (D2_INF, INFINITY, UNDEFINED, ESDFMap, frontier_model, pat
                        ray_walk, ray_walks, signed_distance)
 from .body_model import BODY_MAX_SPHERES, body_query_model, body_rotation  # noqa: F401
 from .articulated_model import BODY_MAX_FRAMES, articulated_query_model, group_spheres_by_frame  # noqa: F401
+from .sweep_model import body_reach, body_sweep_model, sweep_poses  # noqa: F401
 from .cluster_model import cluster_model, cluster_stencil  # noqa: F401
 from .skeleton_model import skeleton_model  # noqa: F401
 from .split_model import SPLIT_INVALID, SPLIT_MAX_DEPTH, SPLIT_OK, split_model  # noqa: F401
@@ -23,7 +24,7 @@ from .tour_model import TOUR_CLOSED, best_move, tour_model  # noqa: F401
 from .timing_model import (TIMING_INVALID, TIMING_MAX_SAMPLES, TIMING_MAX_WAYPOINTS, TIMING_OK, TIMING_TOO_LONG,  # noqa: F401
                            path_timing_model)
 
-__all__ = ["articulated_query_model", "group_spheres_by_frame", "BODY_MAX_FRAMES", "body_query_model","body_rotation", "BODY_MAX_SPHERES", "path_timing_model", "TIMING_OK", "TIMING_INVALID", "TIMING_TOO_LONG", "TIMING_MAX_WAYPOINTS", "TIMING_MAX_SAMPLES", "path_refine_model", "path_refine_gradient", "corridor_bounds", "corridor_bounds_model", "BOUNDS_VOID_BROKEN","REFINE_OK", "REFINE_INVALID", "REFINE_MAX_WAYPOINTS",
+__all__ = ["body_reach", "sweep_poses", "body_sweep_model", "articulated_query_model", "group_spheres_by_frame", "BODY_MAX_FRAMES", "body_query_model","body_rotation", "BODY_MAX_SPHERES", "path_timing_model", "TIMING_OK", "TIMING_INVALID", "TIMING_TOO_LONG", "TIMING_MAX_WAYPOINTS", "TIMING_MAX_SAMPLES", "path_refine_model", "path_refine_gradient", "corridor_bounds", "corridor_bounds_model", "BOUNDS_VOID_BROKEN","REFINE_OK", "REFINE_INVALID", "REFINE_MAX_WAYPOINTS",
            "REFINE_MAX_ITERATIONS", "free_box_model", "corridor_chain", "corridor_model", "CORRIDOR_THROUGH_UNKNOWN", "CORRIDOR_MAX_GROW", "CORRIDOR_STOP_BLOCKED",
            "CORRIDOR_STOP_EDGE", "CORRIDOR_STOP_LIMIT", "FREE_BOX_OK", "FREE_BOX_OUTSIDE", "FREE_BOX_BLOCKED", "CORRIDOR_OK", "CORRIDOR_INVALID",
            "CORRIDOR_BLOCKED", "tour_model", "best_move", "TOUR_CLOSED", "ESDFMap", "signed_distance", "path_samples", "path_cost_model", "frontier_model", "ray_walk", "ray_walks", "ray_query_model", "reach_model", "reach_matrix_model", "REACH_THROUGH_UNKNOWN", "reach_moves", "reach_paths_model", "leg_paths_model", "LEG_NO_SOURCE", "LEG_BAD_INDEX", "reach_visible", "reach_walk", "REACH_PATHS_SHORTCUT", "cluster_model", "cluster_stencil", "skeleton_model", "split_model", "SPLIT_OK", "SPLIT_INVALID", "SPLIT_MAX_DEPTH", "view_coverage_model", "view_ring", "VIEW_OMNI", "FiestaHipError", "device_count", "load", "LIB_PATH", "UNDEFINED", "INFINITY",

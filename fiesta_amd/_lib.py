@@ -92,6 +92,13 @@ class ArticulatedResult(C.Structure):
                 ("frame_grad", C.c_void_p), ("sphere_clearance", C.c_void_p)]
 
 
+class SweepResult(C.Structure):
+    """fiesta_hip_sweep_result: one array per output of fiesta_hip_body_sweep, every pointer nullable"""
+    _fields_ = [("min_clearance", C.c_void_p), ("min_sample", C.c_void_p), ("min_sphere", C.c_void_p), ("min_pose", C.c_void_p),
+                ("min_pos", C.c_void_p), ("min_grad", C.c_void_p), ("first_below", C.c_void_p), ("first_below_sphere", C.c_void_p),
+                ("first_below_pose", C.c_void_p), ("n_below", C.c_void_p), ("n_samples", C.c_void_p)]
+
+
 class RayResult(C.Structure):
     """fiesta_hip_ray_result: one array per output of fiesta_hip_ray_query, every pointer nullable"""
     _fields_ = [("n_visited", C.c_void_p), ("hit_index", C.c_void_p), ("hit_class", C.c_void_p), ("hit_vox", C.c_void_p),
@@ -343,6 +350,8 @@ def load():
         "fiesta_hip_body_query_dev": (C.c_int, [vp, vp, i32, vp, i64, dbl, vp]),
         "fiesta_hip_articulated_query": (C.c_int, [vp, vp, vp, i32, i32, vp, i64, dbl, vp]),
         "fiesta_hip_articulated_query_dev": (C.c_int, [vp, vp, vp, i32, i32, vp, i64, dbl, vp]),
+        "fiesta_hip_body_sweep": (C.c_int, [vp, vp, i32, vp, i64, vp, i64, dbl, dbl, vp]),
+        "fiesta_hip_body_sweep_dev": (C.c_int, [vp, vp, i32, vp, i64, vp, i64, dbl, dbl, vp]),
         "fiesta_hip_get_frontier_voxels": (C.c_int, [vp, vp, vp, dbl, vp, vp, i64, vp]),
         "fiesta_hip_get_frontier_voxels_dev": (C.c_int, [vp, vp, vp, dbl, vp, vp, i64, vp]),
         "fiesta_hip_get_skeleton_voxels": (C.c_int, [vp, vp, vp, i32, dbl, i64, vp, vp]),

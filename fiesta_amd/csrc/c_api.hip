@@ -63,7 +63,7 @@ DenseMap &dense(fiesta_hip_map *m, const char *what) {
 }
 // The planner calls: one body per host / _dev pair.  Each checks the whole-call errors of include/fiesta_hip.h on the arguments as
 // the ABI took them (the call's aggregate of planner_args.hpp), then hands the same object on to the call's function of planner.hpp,
-// with the store's planner_ctx() and -- the thirteen calls that read voxels -- its planner_view(does the call read the bitmaps?).
+// with the store's planner_ctx() and -- the fourteen calls that read voxels -- its planner_view(does the call read the bitmaps?).
 
 // shared by path_clearance and path_cost (R: the call's result struct); a host batch: the CSR rules as well
 template <typename R>
@@ -117,6 +117,21 @@ void articulated_query(fiesta_hip_map *m, const fiesta::ArticulatedArgs &a) {
     need(a.sphere_frame[i] >= a.sphere_frame[i - 1], "articulated_query: the spheres are not grouped by frame (sphere_frame decreases)");
   need(std::isfinite(a.margin), "articulated_query: margin must be finite");
   on_store(m, [&](auto &s) { fiesta::articulated_query(s.planner_ctx(), s.planner_view(false), a); });
+}
+// fiesta_hip_body_sweep: the body query's errors on the table and the margin, path clearance's on step, offsets and null pointers
+void body_sweep(fiesta_hip_map *m, const fiesta::SweepArgs &a) {
+  need(m && a.spheres && a.poses && a.off && a.res, "null argument");
+  need(a.n_spheres >= 1 && a.n_spheres <= FIESTA_HIP_BODY_MAX_SPHERES, "body_sweep: n_spheres must be 1 .. 1024");
+  need(a.n_poses >= 0 && a.n_paths >= 0, "negative count");
+  for (int64_t i = 0; i < 4 * (int64_t)a.n_spheres; ++i) need(std::isfinite(a.spheres[i]), "body_sweep: a sphere's centre or radius is not finite");
+  for (int32_t i = 0; i < a.n_spheres; ++i) need(a.spheres[4 * i + 3] >= 0, "body_sweep: a sphere's radius is negative");
+  need(std::isfinite(a.step) && a.step > 0, "body_sweep: step must be finite and > 0");
+  need(std::isfinite(a.margin), "body_sweep: margin must be finite");
+  if (!a.dev) {
+    need(a.off[0] == 0 && a.off[a.n_paths] == a.n_poses, "body_sweep: offsets[0] must be 0 and offsets[n_paths] = n_poses");
+    for (int64_t p = 0; p < a.n_paths; ++p) need(a.off[p] <= a.off[p + 1], "body_sweep: offsets must be non-decreasing");
+  }
+  on_store(m, [&](auto &s) { fiesta::body_sweep(s.planner_ctx(), s.planner_view(false), a); });
 }
 // n_out: the variant's total (host or device pointer); returns the host variant's total
 int64_t frontier_voxels(fiesta_hip_map *m, const fiesta::FrontierArgs &a, const void *n_out) {
@@ -764,6 +779,15 @@ int fiesta_hip_articulated_query_dev(fiesta_hip_map *m, const double *spheres, c
                                      const double *frame_poses_dev, int64_t n_configs, double margin,
                                      const fiesta_hip_articulated_result *result) {
   return guarded([&] { articulated_query(m, {spheres, sphere_frame, n_spheres, n_frames, frame_poses_dev, n_configs, margin, result, true}); });
+}
+int fiesta_hip_body_sweep(fiesta_hip_map *m, const double *spheres, int32_t n_spheres, const double *poses, int64_t n_poses,
+                          const int64_t *offsets, int64_t n_paths, double step, double margin, const fiesta_hip_sweep_result *result) {
+  return guarded([&] { body_sweep(m, {spheres, n_spheres, poses, n_poses, offsets, n_paths, step, margin, result, false}); });
+}
+int fiesta_hip_body_sweep_dev(fiesta_hip_map *m, const double *spheres, int32_t n_spheres, const double *poses_dev, int64_t n_poses,
+                              const int64_t *offsets_dev, int64_t n_paths, double step, double margin,
+                              const fiesta_hip_sweep_result *result) {
+  return guarded([&] { body_sweep(m, {spheres, n_spheres, poses_dev, n_poses, offsets_dev, n_paths, step, margin, result, true}); });
 }
 int fiesta_hip_get_frontier_voxels(fiesta_hip_map *m, const int32_t lo[3], const int32_t hi[3], double min_clearance, int32_t *vox,
                                    uint8_t *mask, int64_t capacity, int64_t *n_out) {

@@ -20,6 +20,7 @@
 #include "refine_kernels.hpp"
 #include "skeleton_kernels.hpp"
 #include "split_kernels.hpp"
+#include "sweep_kernels.hpp"
 #include "timing_kernels.hpp"
 #include "tour_kernels.hpp"
 #include "view_kernels.hpp"
@@ -65,6 +66,11 @@ template <class View>
 void articulated_query(const PlannerCtx &ctx, const View &v, const ArticulatedArgs &a) {
   if (a.n_configs <= 0) return;
   use_device(ctx), articulated_query_run(ctx.stream, ctx.S, v.path_eval(), a);
+}
+template <class View>
+void body_sweep(const PlannerCtx &ctx, const View &v, const SweepArgs &a) {
+  if (a.n_paths <= 0) return;
+  use_device(ctx), body_sweep_run(ctx.stream, ctx.S, v.path_eval(), a);
 }
 
 // The frontier call's store side: frontier_box gives the kernel's box, whether it is empty and (returned) the most entries it can yield,
@@ -207,6 +213,7 @@ void view_coverage(const PlannerCtx &ctx, const View &v, const ViewArgs &a) {
   template void path_timing(const PlannerCtx &, const VIEW &, const PathTimingArgs &);                                                   \
   template void body_query(const PlannerCtx &, const VIEW &, const BodyArgs &);                                                          \
   template void articulated_query(const PlannerCtx &, const VIEW &, const ArticulatedArgs &);                                            \
+  template void body_sweep(const PlannerCtx &, const VIEW &, const SweepArgs &);                                                         \
   template int64_t frontier_voxels(const PlannerCtx &, const VIEW &, const FrontierArgs &);                                              \
   template int64_t skeleton_voxels(const PlannerCtx &, const VIEW &, const SkeletonArgs &);                                              \
   template void ray_query(const PlannerCtx &, const VIEW &, const RayArgs &);                                                            \

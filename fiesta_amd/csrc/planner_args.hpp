@@ -43,6 +43,18 @@ struct ArticulatedArgs {  // the call's arguments as fiesta_hip_articulated_quer
   bool dev;
 };
 
+struct SweepArgs {  // the call's arguments as fiesta_hip_body_sweep[_dev] takes them, already checked
+  const double *spheres;  // a host pointer in both variants: cx, cy, cz, r per sphere
+  int32_t n_spheres;
+  const double *poses;  // the waypoint poses, n_poses x 7
+  int64_t n_poses;
+  const int64_t *off;
+  int64_t n_paths;
+  double step, margin;
+  const fiesta_hip_sweep_result *res;
+  bool dev;
+};
+
 struct FrontierArgs {  // the call's arguments as fiesta_hip_get_frontier_voxels[_dev] takes them, already checked
   const int32_t *lo, *hi;  // both null: the whole map
   double min_clearance;

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ArticulatedResult, BodyResult,ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, LegPathsInfo, LegPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, TimingParams, TimingResult, BoundsResult, Stats, TourInfo, TourResult, check
+from ._lib import ArticulatedResult, BodyResult, SweepResult, ClusterInfo, ClusterResult, SplitInfo, SplitResult, ViewInfo, ViewResult, ViewSensor, ViewSet, Config, FiestaHipError, PathCostResult, PathResult, RaycastParams, RayResult, ReachInfo, ReachMatrixInfo, ReachMatrixResult, ReachPathsResult, LegPathsInfo, LegPathsResult, ReachResult, CorridorResult, FreeBoxesResult, RefineParams, RefineResult, TimingParams, TimingResult, BoundsResult, Stats, TourInfo, TourResult, check
 from .refine_model import BOUNDS_VOID_BROKEN
 
 UNDEFINED = -10000   # undefined_  (src/ESDFMap.cpp:182)
@@ -109,6 +109,12 @@ ARTICULATED_FIELDS = (("min_clearance", np.float64, ()), ("min_sphere", np.int32
                       ("min_grad", np.float64, (3,)), ("n_below", np.int32, ()), ("cost", np.float64, ()),
                       ("frame_clearance", np.float64, ("F",)), ("frame_cost", np.float64, ("F",)), ("frame_grad", np.float64, ("F", 6)),
                       ("sphere_clearance", np.float64, ("K",)))
+
+# fiesta_hip_sweep_result, in struct order: (name, dtype, row shape): one row per path
+SWEEP_FIELDS = (("min_clearance", np.float64, ()), ("min_sample", np.int64, ()), ("min_sphere", np.int32, ()), ("min_pose", np.float64, (7,)),
+                ("min_pos", np.float64, (3,)), ("min_grad", np.float64, (3,)), ("first_below", np.int64, ()),
+                ("first_below_sphere", np.int32, ()), ("first_below_pose", np.float64, (7,)), ("n_below", np.int64, ()),
+                ("n_samples", np.int64, ()))
 
 
 # fiesta_hip_refine_result, in struct order: (name, dtype, one row per "path" or per "waypoint", row shape)
@@ -695,6 +701,32 @@ class ESDFMap:
         res = ArticulatedResult(*[int(out.get(name, 0)) or None for name, _, _ in ARTICULATED_FIELDS])
         check(self._lib.fiesta_hip_articulated_query_dev(self._h, _p(sph), _p(frm), len(sph), int(n_frames), C.c_void_p(frame_poses_dev_ptr),
                                                          int(n_configs), float(margin), C.byref(res)))
+
+    def BodySweep(self, spheres, poses, offsets, step, margin) -> dict:
+        """fiesta_hip_body_sweep: a body of spheres ((K, 4): body-frame centre and radius) moved along polylines of waypoint poses
+        ((N, 7): px, py, pz, qw, qx, qy, qz; CSR `offsets` over the pose rows).  The poses between two waypoints are sampled by the
+        header's rule (at most `step` metres of travel of any sphere centre per sample for turns up to 90 degrees), each is evaluated
+        as BodyQuery evaluates a pose; per path the minimum clearance with its sample, sphere, pose, position and gradient, the
+        first sample with a sphere below `margin`, the count of such samples and the sample count -- a dict of numpy arrays named as
+        the fields of fiesta_hip_sweep_result; fiesta_amd.body_sweep_model is the definition"""
+        sph = np.ascontiguousarray(spheres, dtype=np.float64).reshape(-1, 4)
+        P = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        n = len(off) - 1
+        out = {name: np.empty((max(n, 0),) + shape, dtype) for name, dtype, shape in SWEEP_FIELDS}
+        res = SweepResult(*[out[name].ctypes.data for name, _, _ in SWEEP_FIELDS])
+        check(self._lib.fiesta_hip_body_sweep(self._h, _p(sph), len(sph), _p(P), len(P), _p(off), n, float(step), float(margin), C.byref(res)))
+        return out
+
+    def BodySweepDevice(self, spheres, poses_dev_ptr: int, n_poses: int, offsets_dev_ptr: int, n_paths: int, step, margin, out=None):
+        """fiesta_hip_body_sweep_dev: `spheres` is a host array as in BodySweep, the waypoint poses (n_poses x 7 f64), the offsets
+        (n_paths + 1 int64) and the outputs are resident on the device (`out` maps field names of fiesta_hip_sweep_result to device
+        pointers, missing fields are not written); only enqueued on the map's stream"""
+        sph = np.ascontiguousarray(spheres, dtype=np.float64).reshape(-1, 4)
+        out = out or {}
+        res = SweepResult(*[int(out.get(name, 0)) or None for name, _, _ in SWEEP_FIELDS])
+        check(self._lib.fiesta_hip_body_sweep_dev(self._h, _p(sph), len(sph), C.c_void_p(poses_dev_ptr), int(n_poses),
+                                                  C.c_void_p(offsets_dev_ptr), int(n_paths), float(step), float(margin), C.byref(res)))
 
     def PathRefine(self, waypoints, offsets, bounds=None, *, margin, w_obstacle, w_smooth, alpha, max_step, tolerance=0.0,
                    iterations) -> dict:

@@ -299,6 +299,60 @@ class ESDFMap {
     return ArticulatedQueryBatch(spheres, sphere_frame, n_frames, frame_poses, margin).min_clearance[0] >= margin;
   }
 
+  // Body sweeps (fiesta_hip_body_sweep; no reference counterpart): the body of BodyQueryBatch moved along polylines of waypoint poses
+  // (px, py, pz, qw, qx, qy, qz each) -- path p is the poses offsets[p] .. offsets[p + 1] - 1.  The poses between two waypoints are sampled on the
+  // device (positions as PathSample's, rotations along the shorter arc, `step` metres of travel of any sphere centre per sample for
+  // turns up to 90 degrees) and each is evaluated as BodyQueryBatch evaluates a pose.  Per path: the minimum of d - r over all samples
+  // and spheres with its sample index, sphere, pose (position, then qw, qx, qy, qz), sphere position and gradient; the first sample
+  // with a sphere below `margin`, that sphere and that pose (-1 / NaN if none); the number of such samples; the sample count (0: an
+  // empty path, -1: an invalid one -- an invalid waypoint pose, a segment of more than 2^24 samples).  A sampled check, as
+  // PathClearanceBatch is.  Always answered on the device.  The formulas: include/fiesta_hip.h.
+  struct SweepResult {
+    std::vector<double> min_clearance;
+    std::vector<int64_t> min_sample;
+    std::vector<int32_t> min_sphere;
+    std::vector<std::array<double, 7>> min_pose;
+    std::vector<Eigen::Vector3d> min_pos, min_grad;
+    std::vector<int64_t> first_below;
+    std::vector<int32_t> first_below_sphere;
+    std::vector<std::array<double, 7>> first_below_pose;
+    std::vector<int64_t> n_below, n_samples;
+    size_t count() const { return min_clearance.size(); }
+  };
+  typedef std::vector<std::array<double, 7>> BodyPoses;
+  SweepResult BodySweepBatch(const BodySpheres &spheres, const BodyPoses &waypoints, const std::vector<int64_t> &offsets, double step,
+                             double margin) {
+    if (offsets.empty()) throw std::invalid_argument("BodySweepBatch: offsets needs n_paths + 1 entries");
+    const size_t n = offsets.size() - 1, np = waypoints.size(), k = spheres.size();
+    std::vector<double> sph(4 * k + 4), poses(7 * np + 7), mq(7 * n + 7), mp(3 * n + 3), mg(3 * n + 3), fq(7 * n + 7);  // (spare rows: never a null pointer)
+    for (size_t i = 0; i < k; ++i)
+      for (int c = 0; c < 4; ++c) sph[4 * i + c] = spheres[i][c];
+    for (size_t i = 0; i < np; ++i)
+      for (int c = 0; c < 7; ++c) poses[7 * i + c] = waypoints[i][c];
+    SweepResult out;
+    out.min_clearance.resize(n + 1), out.min_sample.resize(n + 1), out.min_sphere.resize(n + 1), out.first_below.resize(n + 1);
+    out.first_below_sphere.resize(n + 1), out.n_below.resize(n + 1), out.n_samples.resize(n + 1);
+    const fiesta_hip_sweep_result r{out.min_clearance.data(), out.min_sample.data(),         out.min_sphere.data(), mq.data(),
+                                    mp.data(),                mg.data(),                     out.first_below.data(), out.first_below_sphere.data(),
+                                    fq.data(),                out.n_below.data(),            out.n_samples.data()};
+    ck(fiesta_hip_body_sweep(h_, sph.data(), (int32_t)k, poses.data(), (int64_t)np, offsets.data(), (int64_t)n, step, margin, &r));
+    out.min_clearance.resize(n), out.min_sample.resize(n), out.min_sphere.resize(n), out.first_below.resize(n);
+    out.first_below_sphere.resize(n), out.n_below.resize(n), out.n_samples.resize(n);
+    out.min_pose.resize(n), out.min_pos.resize(n), out.min_grad.resize(n), out.first_below_pose.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      out.min_pos[i] = Eigen::Vector3d(mp[3 * i], mp[3 * i + 1], mp[3 * i + 2]);
+      out.min_grad[i] = Eigen::Vector3d(mg[3 * i], mg[3 * i + 1], mg[3 * i + 2]);
+      for (int c = 0; c < 7; ++c) out.min_pose[i][c] = mq[7 * i + c], out.first_below_pose[i][c] = fq[7 * i + c];
+    }
+    return out;
+  }
+  // The scalar convenience: does the body keep `margin` from every obstacle along this ONE polyline of poses, sampled every `step`?
+  // (false for an empty or an invalid polyline)
+  bool IsMotionFree(const BodySpheres &spheres, const BodyPoses &waypoints, double step, double margin) {
+    const SweepResult r = BodySweepBatch(spheres, waypoints, {0, (int64_t)waypoints.size()}, step, margin);
+    return r.n_samples[0] > 0 && r.first_below[0] < 0;
+  }
+
   // Sample `index` of the polyline by the header's rule, on the host (bit for bit what the library evaluates there); NaN if the
   // path has no such sample or is invalid.  Header-only, so compiled with the includer's flags: the exactness include/fiesta_hip.h
   // promises holds only without floating-point contraction -- build the including file with -ffp-contract=off.  g++'s default

@@ -135,7 +135,8 @@ const char *fiesta_hip_last_error(void);
  * fiesta_hip_view_coverage[_dev], fiesta_hip_reach_matrix[_dev], fiesta_hip_site_tour[_dev], fiesta_hip_free_boxes[_dev],
  * fiesta_hip_path_corridor[_dev], fiesta_hip_path_refine[_dev], fiesta_hip_corridor_bounds[_dev],
  * fiesta_hip_split_clusters[_dev], fiesta_hip_leg_paths[_dev], fiesta_hip_path_timing[_dev], fiesta_hip_get_skeleton_voxels[_dev],
- * fiesta_hip_body_query[_dev] and fiesta_hip_articulated_query[_dev]: detect them by symbol lookup (dlsym). */
+ * fiesta_hip_body_query[_dev], fiesta_hip_articulated_query[_dev] and fiesta_hip_body_sweep[_dev]: detect them by symbol lookup
+ * (dlsym). */
 int fiesta_hip_version(void);
 /* Number of usable gfx950 devices (0 on a box without a GPU; never an error). */
 int fiesta_hip_device_count(void);
@@ -550,6 +551,82 @@ int fiesta_hip_articulated_query(fiesta_hip_map *m, const double *spheres, const
 int fiesta_hip_articulated_query_dev(fiesta_hip_map *m, const double *spheres, const int32_t *sphere_frame, int32_t n_spheres,
                                      int32_t n_frames, const double *frame_poses_dev, int64_t n_configs, double margin,
                                      const fiesta_hip_articulated_result *result);
+
+/* ---- body sweeps, batched: a sphere-set body checked along polylines of poses ----
+ * Path clearance answers "is this path free for a point", the body query "is this pose free for a body".  A sampling planner asks of
+ * every edge it tries whether the MOTION is free for the BODY: a rod-shaped drone that yaws while it flies through a door.  This call
+ * samples the poses between the waypoint poses, evaluates each as the body query does and reduces per path.  No reference
+ * counterpart.  fiesta_hip_version() is still 101: detect these two calls by symbol lookup.
+ * Input:
+ *   spheres, n_spheres   the body query's table, a HOST pointer in both variants, with the same validation
+ *   poses      f64 x 7 per WAYPOINT pose: px, py, pz (metres), qw, qx, qy, qz.  The quaternions need not be normalised.
+ *   offsets    n_paths + 1 int64: path p is the pose rows offsets[p] .. offsets[p + 1] - 1 (the CSR rules of path clearance)
+ *   step       metres, finite and > 0;   margin   finite
+ * The table's reach, computed on the host (fiesta_amd.body_reach is the same rule in numpy):
+ *   reach = max over i of sqrt((cx*cx + cy*cy) + cz*cz)
+ * Per waypoint pose: validity is the body query's rule verbatim -- seven finite numbers, s = ((qw*qw + qx*qx) + qy*qy) + qz*qz > 0,
+ * k = 2.0 / s finite -- then   n = sqrt(s);   u[c] = q[c] / n.
+ * Per segment j of a path, between the waypoints (a, u0) and (b, u1); in f64, each operation rounded once (the library is built with
+ * -ffp-contract=off), in exactly this order:
+ *   d[c] = b[c] - a[c];   L = sqrt(d0*d0 + d1*d1 + d2*d2)                       (left to right: the path rule)
+ *   dot = ((u0w*u1w + u0x*u1x) + u0y*u1y) + u0z*u1z;   v = u1 if dot >= 0, else -u1   (the shorter arc)
+ *   e[c] = v[c] - u0[c];   ch = sqrt(((e0*e0 + e1*e1) + e2*e2) + e3*e3);   W = (2.25 * reach) * ch
+ *   S = max(1, (int64)ceil((L + W) / step));   Sd = (double)S
+ *   sample k = 0 .. S-1:   t = (double)k / Sd;   r = 1.0 - t;   p[c] = a[c] + d[c]*t;   q[c] = r*u0[c] + t*v[c]
+ * After the last segment comes one final sample: the last waypoint's position with its own u.  A path of one pose has exactly that
+ * sample.  Sample indices run in this order.
+ * A sample's pose (p, q) goes through the body query's rule verbatim: R from q with k = 2 / |q|^2, then per sphere a = R c,
+ * x = p + a, (d, g) = fiesta_hip_get_dist_grad's value and gradient at x bit for bit, s_i = d - r_i.
+ * Why W: the segment rotates by theta = 4 asin(ch / 2); q(t) is normalised linear interpolation, which follows slerp's arc at a speed
+ * proportional to 1 / |q(t)|^2 (with dot >= 0, |q(t)|^2 >= 1/2: every sample of a valid path is a valid pose).  2.25 ch >= theta up
+ * to 90 degrees and exceeds it by at most 12.5 %: there no sphere centre moves farther than step between consecutive samples; up
+ * to 180 degrees at most 1.26 step.  A segment without rotation has W = 0 and path clearance's positions bit for bit.
+ * This is a SAMPLED check, as path clearance is: no continuous guarantee.
+ * Outputs, one row per path; every pointer of the result is nullable:
+ *   min_clearance        the minimum of s_i over all samples and spheres
+ *   min_sample (i64)     the lowest sample index that attains it
+ *   min_sphere (i32)     the lowest sphere that attains it in that sample (compared with <, as the body query)
+ *   min_pose (x7)        that sample's (p, q) by the rule
+ *   min_pos, min_grad (x3)  x and g of that sphere there
+ *   first_below (i64)    the lowest sample index with any s_i < margin (strictly), -1 if none
+ *   first_below_sphere (i32)  the lowest such sphere in that sample, -1 if none
+ *   first_below_pose (x7)     that sample's pose, NaN if none
+ *   n_below (i64)        samples with at least one sphere below the margin
+ *   n_samples (i64)      the path's sample count
+ * Every output is exact -- bits and NaN pattern -- on the device and in fiesta_amd.body_sweep_model (numpy): nothing is summed.  The
+ * results depend neither on the batch, nor on the path's place in it, nor on the variant, the launch shape or scheduling; no atomics.
+ * Empty path: n_samples 0, min_clearance +inf, the indices -1, poses and positions NaN, min_grad 0, n_below 0.
+ * Invalid path: n_samples -1, min_clearance NaN, the indices -1, poses and positions NaN, min_grad 0, n_below -1.  A path is invalid
+ * for an invalid waypoint pose, a segment with (L + W) / step > 2^24, or -- device variant -- offsets out of order or out of range by
+ * path clearance's rules.  The other paths are unaffected.  Validity is decided on the device.
+ * Whole-call errors (FIESTA_HIP_ERR_INVALID, nothing launched, the map stays usable, fiesta_hip_last_error() names the cause): the
+ * body query's on the table and the margin (n_spheres outside 1 .. 1024, a null spheres, a sphere that is not finite or has a
+ * negative radius, a margin that is not finite); path clearance's on step, offsets and null pointers (a null map, poses, offsets or
+ * result; negative counts; a step that is not finite or <= 0; host variant: offsets[0] != 0, offsets[n_paths] != n_poses, offsets
+ * that decrease).  n_paths = 0 does nothing.
+ * The call is read-only and reads the field as it stands: before fiesta_hip_update_esdf has run it answers from the old field
+ * (the path calls' rule).
+ * fiesta_hip_body_sweep      poses, offsets and results are host pointers; stages, runs, synchronises.  Always on the device.
+ * fiesta_hip_body_sweep_dev  poses, offsets and every result array are device pointers (the struct itself and spheres are host
+ *                            objects); only enqueued on the map's stream. */
+typedef struct fiesta_hip_sweep_result {
+  double *min_clearance;
+  int64_t *min_sample;
+  int32_t *min_sphere;
+  double *min_pose;
+  double *min_pos;
+  double *min_grad;
+  int64_t *first_below;
+  int32_t *first_below_sphere;
+  double *first_below_pose;
+  int64_t *n_below;
+  int64_t *n_samples;
+} fiesta_hip_sweep_result;
+int fiesta_hip_body_sweep(fiesta_hip_map *m, const double *spheres, int32_t n_spheres, const double *poses, int64_t n_poses,
+                          const int64_t *offsets, int64_t n_paths, double step, double margin, const fiesta_hip_sweep_result *result);
+int fiesta_hip_body_sweep_dev(fiesta_hip_map *m, const double *spheres, int32_t n_spheres, const double *poses_dev, int64_t n_poses,
+                              const int64_t *offsets_dev, int64_t n_paths, double step, double margin,
+                              const fiesta_hip_sweep_result *result);
 
 /* ---- frontier voxels: observed-free voxels that border never-observed space, compacted on the device ----
  * What an exploration planner asks after every frame: where does known free space end, and which of those places can the robot
